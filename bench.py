@@ -8,7 +8,11 @@ the same per-GPU batch on its own GPU (utterances shard with no exchange step ->
 scaling, no collective on the data path; torch.distributed is used for the timing barrier
 and the max-over-ranks only).
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  `value` is the config-2 rate above; beside it
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and reports `value` (the
+config-2 rate above), `ms_per_step`, `tflops_algorithmic` and the configuration; with --dump-outputs DIR it also writes
+the embeddings of the last timed step to DIR/embeddings.npy (float32; same arguments -> same inputs, so two builds can
+be compared output for output).  Everything else is measured only with --full:
+  parity       : parity_rel_l2_max of a few utterances of the timed batch against the float64 oracle;
   roofline     : dominant kernel (tdnn3_conv GEMM), algorithmic FLOPs / hipEvent-measured mean launch duration
                  over a second pass of the same K steps (the events cost 6-9 % of a step, so the region `value`
                  is taken from carries none), against the dense MFMA peak;
@@ -57,10 +61,15 @@ def parse_args():
     ap.add_argument("--network", default="tdnn", choices=["tdnn", "extended_tdnn", "resnet_18"],
                     help="tdnn = BASELINE configs 1-4; resnet_18 = config 5 (use --dim 40 --batch 64)")
     ap.add_argument("--varlen", action="store_true", help="T ~ U[200,1000] per-GPU batch (config-4 shape as the main workload)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline figure: parity, per-kernel timing / roofline, reps, graph replay, "
+                         "bf16x3 rate, config 4, e2e, cli, launcher, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the embeddings of the last timed step to DIR/embeddings.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full; 0 = skip)")
     ap.add_argument("--cpu-nj", type=int, default=0, help="processes of the cpu_baseline leg (0 = min(host cores, 32))")
-    ap.add_argument("--no-profile", action="store_true", help="skip per-kernel hipEvent timing")
-    ap.add_argument("--no-extra", action="store_true", help="only the main timed region (no reps / e2e / cli / config4 legs)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip per-kernel hipEvent timing")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no reps / e2e / cli / config4 legs")
     ap.add_argument("--prewarm", type=float, default=0.5, help="seconds of untimed forwards before the warm-up steps (clock ramp)")
     ap.add_argument("--reps", type=int, default=5, help="extra repetitions of the timed region (value_reps)")
     ap.add_argument("--c4-utts", type=int, default=8192, help="config 4: size of the fixed utterance set")
@@ -72,7 +81,24 @@ def parse_args():
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses device 0 (with --dist-backend gloo)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the forward from a captured hipGraph (per-kernel events are then not recorded)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, emb):
+    """DIR/embeddings.npy: the embeddings of the last timed step, float32.  Above DUMP_LIMIT_BYTES a fixed, seeded sample
+    of rows (kept in batch order) is written instead."""
+    os.makedirs(path, exist_ok=True)
+    emb = np.ascontiguousarray(emb, dtype=np.float32)
+    if emb.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // emb[0].nbytes
+        emb = emb[np.sort(np.random.RandomState(0).choice(len(emb), keep, replace=False))]
+    np.save(os.path.join(path, "embeddings.npy"), emb)
 
 
 def pmc_traffic(kernel, precision, args):
@@ -419,13 +445,15 @@ def main():
     # bracketed (its per-kernel averages agree with the rocprofv3 trace in profiles/).
     # barrier + synchronize, exactly K steps, barrier + synchronize, max over ranks
     elapsed = sharding.timed_steps(step, args.steps, sync_dev, dist=d, device=red_dev)
+    emb = out.cpu().numpy() if rank == 0 else None         # what the last timed step computed
+    if emb is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, emb)
     kernels = []
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         tr.profile_begin(max_events=2 * 48 * (args.steps + 1))
         sharding.timed_steps(step, args.steps, sync_dev, dist=d, device=red_dev)
         kernels, _ = tr.profile_end()
-    emb = out.cpu().numpy() if rank == 0 else None
-    extra = not args.no_extra
+    extra = args.full and not args.no_extra
     # extra legs (never `value`): repetitions of the same region, the same K steps replayed from a captured hipGraph
     reps = []
     if extra and args.reps > 0:
@@ -493,7 +521,22 @@ def main():
     result = None
     if rank == 0:
         total_utts = n_gpus * args.batch * args.steps
-        value = total_utts / elapsed
+        flops_step = float(info["flops"])
+        result = {
+            "metric": "utterances/sec x-vector extraction (30-dim x 300-frame)",
+            "value": round(total_utts / elapsed, 1), "unit": "utterances/s", "n_gpus": n_gpus, "steps": args.steps,
+            "warmup": args.warmup, "prewarm_s": args.prewarm, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"f32": "f32", "bf16x3": "bf16x3(f32-split)", "f16x3": "f16x3(f32-split)", "f16f6": "f16+fp6-cross(f32-split)"}[precision], "data": "synthetic",
+            "config": {"workload": "%s x-vector (%s), %s, %d utt/GPU/step of %s frames x %d dims"
+                       % (args.network, params.embedding_node, args.pooling, args.batch,
+                          "U[200,1000]" if args.varlen else str(args.frames), args.dim),
+                       "batch_per_gpu": args.batch, "frames": "varlen" if args.varlen else args.frames,
+                       "node": params.embedding_node, "precision": precision, "parallelism": "utterance-shard x%d" % n_gpus,
+                       "launch": "hipGraph replay" if args.graph else "stream launches"},
+            "tflops_algorithmic": round(flops_step * args.steps * n_gpus / elapsed / 1e12, 2),
+        }
+    if rank == 0 and args.full:
         # parity spot check against the float64 oracle on a few utterances of this batch
         from oracle import ref_numpy
         idx = list(range(0, args.batch, max(1, args.batch // 4)))[:(2 if args.network == "resnet_18" else 4)]
@@ -521,20 +564,7 @@ def main():
                 roof["mfma_issue_frac"] = round(3 * tf / peak, 4)
                 roof["note"] = ("split precision: 3 MFMAs per algorithmic product, so the ceiling of `frac` is 1/3; "
                                 "mfma_issue_frac = issued MFMA FLOPs / bf16 dense peak")
-        flops_step = float(info["flops"])
-        result = {
-            "metric": "utterances/sec x-vector extraction (30-dim x 300-frame)",
-            "value": round(value, 1), "unit": "utterances/s", "n_gpus": n_gpus, "steps": args.steps,
-            "warmup": args.warmup, "prewarm_s": args.prewarm, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"f32": "f32", "bf16x3": "bf16x3(f32-split)", "f16x3": "f16x3(f32-split)", "f16f6": "f16+fp6-cross(f32-split)"}[precision], "data": "synthetic",
-            "config": {"workload": "%s x-vector (%s), %s, %d utt/GPU/step of %s frames x %d dims"
-                       % (args.network, params.embedding_node, args.pooling, args.batch,
-                          "U[200,1000]" if args.varlen else str(args.frames), args.dim),
-                       "batch_per_gpu": args.batch, "frames": "varlen" if args.varlen else args.frames,
-                       "node": params.embedding_node, "precision": precision, "parallelism": "utterance-shard x%d" % n_gpus,
-                       "launch": "hipGraph replay" if args.graph else "stream launches"},
-            "tflops_algorithmic": round(flops_step * args.steps * n_gpus / elapsed / 1e12, 2),
+        result.update({
             "graph_replay_value": round(graph_rate, 1) if graph_rate else None,
             "parity_rel_l2_max": max(errs),
             "kernels": [{"name": k["name"], "ms": round(k["ms"], 4),
@@ -543,7 +573,7 @@ def main():
                         for k in kernels],
             "kernels_note": "per-kernel hipEvent times of a second region of the same %d steps (all launches bracketed)" % args.steps,
             "roofline": roof,
-        }
+        })
         if reps:
             rates = sorted(total_utts / r for r in reps)
             result["value_reps"] = {"n": len(rates), "min": round(rates[0], 1), "median": round(rates[len(rates) // 2], 1),
@@ -558,6 +588,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         torch.cuda.synchronize(dev)
+    if rank == 0 and args.full:
         result["cli"] = None
         if extra and n_gpus == 1 and tdnn_default and not args.varlen and args.cli_utts > 0:
             try:
@@ -574,6 +605,7 @@ def main():
             result["cpu_baseline"] = cpu_baseline(weights, params, args.dim, args.frames, args.cpu_seconds, args.cpu_nj)
         else:
             result["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(result))
 
 

@@ -9,6 +9,7 @@ import os
 
 import numpy as np
 import pytest
+import torch
 
 from oracle import ref_numpy, ref_torch
 from tf_kaldi_speaker_amd import synth
@@ -134,13 +135,20 @@ def test_tf_same_padding_stride2_is_asymmetric():
 
 
 def test_full_size_tdnn_restatements_agree():
+    """Full-size TDNN (512 / 1500 channels).  The two formulations run in float64 must agree to rounding (1e-12, as the
+    other float64 checks here).  In fp32 the embedding is a 3000-term affine with heavy cancellation, so its error is set
+    by the host BLAS's summation order (1.7e-7 .. 1.3e-6 across MKL code paths and thread counts); it is held to the
+    2e-6 of the other fp32 restatement checks."""
     p = dict(synth.TDNN_STAT_PARAMS)
     w = synth.synth_weights(p, 30, seed=0)
     feats = np.stack(synth.synth_features(1, 60, 30, seed=1))
     a = ref_numpy.predict(feats, w, p, 30)
-    b = ref_torch.TorchTdnn(w, p).predict(feats, 30)
     assert a.shape == (1, 512)
-    assert np.linalg.norm(a - b) / np.linalg.norm(a) < 1e-6
+    b64 = ref_torch.TorchTdnn(w, p, dtype=torch.float64).predict(feats, 30)
+    assert np.linalg.norm(a - b64) / np.linalg.norm(a) < 1e-12
+    b = ref_torch.TorchTdnn(w, p).predict(feats, 30)
+    assert b.dtype == np.float32
+    assert np.linalg.norm(a - b) / np.linalg.norm(a) < 2e-6
 
 
 def test_conv_is_valid_cross_correlation_no_flip():

@@ -10,8 +10,8 @@ ok() { [ "$1" -eq 0 ] || [ "$1" -eq 1 ]; }          # 0 = fine, 1 = test failure
 step pytest; timeout -k 10 900 python -m pytest tests -m gpu -q "$@" > $out/pytest.txt 2>&1; rc=$?; tail -n 30 $out/pytest.txt; ok $rc || exit $rc
 step layers_f16f6; timeout -k 10 200 python tools/layer_times.py tdnn f16f6 2>&1 | grep -v amdgpu.ids > $out/layers_f16f6.txt; rc=$?; ok $rc || exit $rc
 step layers_bf16x3; timeout -k 10 200 python tools/layer_times.py tdnn bf16x3 2>&1 | grep -v amdgpu.ids > $out/layers_bf16x3.txt; rc=$?; ok $rc || exit $rc
-step bench; timeout -k 10 300 python bench.py --cpu-seconds 0 --no-extra > $out/bench_f16f6.json 2> $out/bench.err; rc=$?; ok $rc || exit $rc
-step pmc; timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $out/pmc -- python bench.py --cpu-seconds 0 --no-extra --steps 3 --warmup 1 --no-profile > $out/pmc.log 2>&1; rc=$?; ok $rc || exit $rc
+step bench; timeout -k 10 300 python bench.py --full --cpu-seconds 0 --no-extra > $out/bench_f16f6.json 2> $out/bench.err; rc=$?; ok $rc || exit $rc
+step pmc; timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $out/pmc -- python bench.py --full --cpu-seconds 0 --no-extra --steps 3 --warmup 1 --no-profile > $out/pmc.log 2>&1; rc=$?; ok $rc || exit $rc
 python profiles/summarize_pmc.py $(find $out/pmc -name "*counter_collection.csv" | head -1) > $out/pmc_summary.txt 2>&1
 rm -rf $out/pmc
 step done

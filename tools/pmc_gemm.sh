@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 run() {  # name counters...
   name=$1; shift
   echo "pass $name: $*" >> $out/progress.txt
-  timeout -k 10 150 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $out/$name -- python bench.py --cpu-seconds 0 --steps 3 --warmup 1 --no-profile > $out/$name.log 2>&1 || { echo "pass $name failed" >> $out/progress.txt; return 0; }
+  timeout -k 10 150 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $out/$name -- python bench.py --full --cpu-seconds 0 --steps 3 --warmup 1 --no-profile > $out/$name.log 2>&1 || { echo "pass $name failed" >> $out/progress.txt; return 0; }
   f=$(find $out/$name -name "*counter_collection.csv" | head -1)
   python profiles/summarize_pmc.py "$f" gemm_bf16x3 > $out/pmc_$name.txt 2>&1
   rm -rf $out/$name
