@@ -169,16 +169,28 @@ int xv_check_overflow(xv_handle* h, int reset);
  * batched): copies the two flag words to `host_flags` (2 x int32; pinned host memory makes the copy truly asynchronous)
  * behind everything enqueued on `stream` so far and clears them, in stream order.  Once the stream has reached that
  * point, xv_flags_decode(host_flags) gives 0 = in range, 1 = a value beyond the fp16 range was converted (as above),
- * 2 = every input feature staged since the last clear was below 2^-8 in magnitude: the low halves of the fp16 split
- * are subnormal there and the embeddings lose precision silently -- rescale the features or use XV_PREC_BF16X3.
- * (Hidden activations need no such guard: each layer's split copy is kept at a power-of-two scale derived from its
- * batch-normalisation parameters; csrc/xvec_api.hip, act_exponent.)  xv_check_overflow returns the same codes. */
+ * 2 = an utterance staged since the last clear had every input feature below 2^-8 in magnitude (and not all zero): the
+ * low halves of the fp16 split are subnormal there and its outputs lose precision silently (~2^-11 relative on frame-level
+ * endpoints) -- rescale the features or use XV_PREC_BF16X3.  The test is per utterance (a batch-wide maximum would let one
+ * small utterance among ordinary ones through).
+ * Hidden activations have no flag: each layer's split copy is kept at a power-of-two scale derived from the rms of its
+ * batch-normalisation gamma / beta (csrc/xvec_api.hip, act_exponent), which keeps channels of ordinary magnitude clear of
+ * both ends of the fp16 range; per-channel spread inside a 32-channel block is what XV_PREC_F16F6's block scales cannot
+ * hold, and xv_finalize demotes such layers (xv_layer_two_unit).  xv_check_overflow returns the same codes. */
 int xv_flags_async(xv_handle* h, int32_t* host_flags, void* stream);
 int xv_flags_decode(const int32_t* host_flags);
 
 /* endpoints[...] key -> node id (model/trainer.py:380 `endpoints[params.embedding_node]`).
  * Returns the id (>= 0) or XV_ERR_INVALID for a name the graph does not define. */
 int xv_node_id(const xv_handle* h, const char* endpoint_name);
+
+/* XV_PREC_F16F6: 1 if the layer that produces `endpoint_name` (any of its stage endpoints, e.g. "tdnn3_conv" / "tdnn3_bn" /
+ * "tdnn3_relu"; a ResNet block output names the block's second convolution) runs on the two-unit kernel, 0 if it runs on the
+ * three-unit kernels (other precisions, layers the two-unit kernel does not cover, and layers xv_finalize demoted because the
+ * magnitudes inside one of their 32-channel blocks -- BN-folded scale / shift of the input channels, |w| of a K group -- are too
+ * far apart for the block-scaled fp6 cross terms).  XV_ERR_INVALID for a name that is not a layer endpoint, XV_ERR_STATE before
+ * xv_finalize.  Read-only. */
+int xv_layer_two_unit(const xv_handle* h, const char* endpoint_name);
 
 /* Number of frames of temporal context the node consumes (tdnn: 14 for everything at or past
  * tdnn3; etdnn: 22 at or past tdnn7); an utterance needs more than this many frames. */

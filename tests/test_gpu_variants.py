@@ -370,7 +370,7 @@ def test_split_formats_survive_a_rescaled_layer(precision, layer, shift):
 
 def test_fp16_split_refuses_features_it_cannot_represent():
     """Input features are whatever the caller sends (no normalisation in front of them): features so small that every low
-    half of the fp16 split is subnormal (all below 2^-8) are refused with an error in the fp16 precisions -- as features
+    half of the fp16 split is subnormal (all below 2^-8, in the whole batch or in one utterance of a ragged batch) are refused with an error in the fp16 precisions -- as features
     beyond 65504 are -- and are no problem for bf16x3, which has the full fp32 exponent range."""
     from tf_kaldi_speaker_amd import synth
     params = dict(synth.TDNN_STAT_PARAMS)
@@ -381,6 +381,8 @@ def test_fp16_split_refuses_features_it_cannot_represent():
         tr = _trainer(params, weights, 30, prec, range_fallback=False)
         with pytest.raises(FloatingPointError, match="below 2\\^-8"):
             tr.predict(tiny)
+        with pytest.raises(FloatingPointError, match="below 2\\^-8"):
+            tr.predict_list([feats[0], tiny[1][:15]])                      # ragged: one short utterance below 2^-8 beside a normal one
         ok = tr.predict(feats)                                              # the flag was reset: the next batch is fine
         assert _rel(ok[0], ref_numpy.predict(feats[0], weights, params, 30)) <= TOL
         tr.close()
@@ -391,6 +393,8 @@ def test_fp16_split_refuses_features_it_cannot_represent():
             got = tr.predict(tiny)
         assert _rel(got[1], ref_numpy.predict(tiny[1], weights, params, 30)) <= TOL
         assert np.array_equal(tr.predict(feats), ok)
+        got = tr.predict_list([feats[0], tiny[1][:15]])                    # the ragged batch re-runs too
+        assert _rel(got[1], ref_numpy.predict(tiny[1][:15], weights, params, 30)) <= TOL
         huge = feats.copy()
         huge[1, 7, 3] = 1.0e5
         got = tr.predict_list([huge[0], huge[1]])                          # the pipelined interface: collect() re-runs the batch

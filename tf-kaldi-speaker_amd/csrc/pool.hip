@@ -514,11 +514,49 @@ __global__ void flags_snapshot_kernel(int* __restrict__ dev, int* __restrict__ h
   if (threadIdx.x == 0) {
     for (int i = 1; i < 16; ++i) mx = fmaxf(mx, wmax[i]);
     host[0] = dev[0];
-    host[1] = __float_as_int(fmaxf(mx, __int_as_float(dev[1])));
+    // a small utterance is reported as its own maximum (below 2^-8: the host decodes code 2), else the batch's largest feature
+    host[1] = dev[kUttSmallWord] ? dev[kUttSmallWord] : __float_as_int(fmaxf(mx, __int_as_float(dev[1])));
     dev[0] = 0;
     dev[1] = 0;
+    dev[kUttSmallWord] = 0;
     __threadfence_system();
   }
+}
+
+// The staging kernel's per-wave maxima guard the batch as a whole; an utterance whose features all sit far below the others' would
+// pass that test and run with flushed low halves (~2^-11 relative error on its frame-level outputs).  One workgroup per utterance
+// takes its largest |feature| (the features were just staged: the re-read comes from the caches) and reports one that is non-zero
+// and below 2^-8 with a plain store into the flag word (any such value will do).
+__global__ void feat_utt_guard_kernel(const float* __restrict__ x, int64_t ldx, int cin, const int32_t* __restrict__ offs,
+                                      int* __restrict__ flags) {
+  __shared__ float wmax[16];
+  const int64_t r0 = offs[blockIdx.x];
+  const int n = (int)(offs[blockIdx.x + 1] - r0) * cin;
+  float mx = 0.f;
+  if (ldx == cin) {
+    const float* p = x + r0 * ldx;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) mx = fmaxf(mx, fabsf(p[i]));
+  } else {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const int r = i / cin;
+      mx = fmaxf(mx, fabsf(x[(r0 + r) * ldx + (i - r * cin)]));
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) mx = fmaxf(mx, wmax[i]);
+    if (mx > 0.f && mx < 0.00390625f) flags[kUttSmallWord] = __float_as_int(mx);     // 2^-8
+  }
+}
+
+hipError_t launch_feat_utt_guard(const float* x, int64_t ldx, int cin, const int32_t* offsets_dev, int batch, int* flags,
+                                 hipStream_t s) {
+  if (batch <= 0) return hipSuccess;
+  hipLaunchKernelGGL(feat_utt_guard_kernel, dim3(batch), dim3(1024), 0, s, x, ldx, cin, offsets_dev, flags);
+  return hipGetLastError();
 }
 
 hipError_t launch_flags_snapshot(int* dev, int* host, hipStream_t s) {

@@ -10,9 +10,10 @@ namespace xv {
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_LRELU = 2, ACT_PRELU = 3, ACT_TANH = 4 };
 
 constexpr float kLreluAlpha = 0.2f;       // tf.nn.leaky_relu default (model/tdnn.py:33)
-// fp16 range guard buffer of a handle: kFlagWords ints ([0] overflow flag, [1] bits of a feature maximum carried over), then
+// fp16 range guard buffer of a handle: kFlagWords ints ([0] overflow flag, [1] bits of a feature maximum carried over, [2..3] scratch
+// of xv_flags_async, [kUttSmallWord] bits of the largest |feature| of an utterance that stayed below 2^-8, 0 = none), then
 // kFeatMaxSlots floats: the largest feature magnitude each wave of the feature staging kernel saw since the last read-out
-constexpr int kFlagWords = 4, kFeatMaxSlots = 32768;      // 8192 workgroups x 4 waves
+constexpr int kFlagWords = 8, kUttSmallWord = 4, kFeatMaxSlots = 32768;      // 8192 workgroups x 4 waves
 constexpr float kVarFloor = 1e-12f;       // VAR2STD_EPSILON (model/pooling.py:6)
 
 // One "overlapping-row" GEMM:  Y[rowmap[m], n] = act((sum_k A[m,k] * Wt[n,k]) * scale[n] + shift[n])
@@ -248,6 +249,10 @@ hipError_t launch_copy2d(const float* src, int64_t lds, float* dst, int64_t ldd,
                          hipStream_t s);
 // fp16 range flags (2 ints) -> device-accessible host memory, then cleared; one kernel
 hipError_t launch_flags_snapshot(int* dev, int* host, hipStream_t s);
+// per-utterance lower-range feature guard (fp16 split formats): flag word kUttSmallWord of `flags` gets the largest |feature| of an
+// utterance whose features are not all zero but all below 2^-8
+hipError_t launch_feat_utt_guard(const float* x, int64_t ldx, int cin, const int32_t* offsets_dev, int batch, int* flags,
+                                 hipStream_t s);
 hipError_t launch_att_weights_out(const float* scores, int H, const int32_t* off0, int B, int ctx,
                                   float* out, hipStream_t s);
 

@@ -705,6 +705,68 @@ int act_exponent(const xv_handle* h, const Layer& L) {
   return (int)std::min(20.0, std::max(-20.0, std::floor(4.5 - std::log2(rms))));
 }
 
+// XV_PREC_F16F6: can the two-unit kernel hold this layer?  Its cross terms are fp6 under ONE power-of-two scale per 32 channels along
+// K -- per (frame, block) for the activations, per (block, tap, output column) for the weights -- so a channel much smaller than the
+// largest of its block is quantised against that largest value, and its cross terms fall towards plain fp16 (2^-11).  A trained
+// model may put exactly that into a block (magnitude split between a BN scale and the next kernel's rows).  Estimate, from numbers
+// known here, how much larger the block-scale error is than for channels of equal magnitude:
+//   m_c  = expected magnitude of input channel c = sqrt(s_c^2 + shift_c^2) of the producer's folded BN (1 when unknown: no BN,
+//          a residual sum, a pooling or the network input),
+//   r_a  = sqrt(sum_c M_b(c)^2 W_c^2 / sum_c m_c^2 W_c^2)    M_b(c) = largest m of c's block, W_c^2 = sum over taps, columns of w^2,
+//   r_w  = sqrt(sum_(c,tap,n) m_c^2 Wmax^2 / sum m_c^2 w^2)  Wmax = largest |w| of the (block, tap, n) K group of w,
+// and demote the layer (f16x3 kernels, as for channel counts without a quad of blocks) when hypot(r_a, r_w) > kF6MaxSpread.
+// A heuristic, with assumptions no test breaks: m_c takes the pre-BN output at unit variance (a channel whose real variance differs
+// from moving_variance is misjudged either way) and ignores the activation behind the BN (a mostly dead ReLU channel, shift far
+// below -s, is much smaller than m_c says, so spread of that kind is underestimated).  Calibrated
+// with the CPU emulation (tests/analysis/f16f8_error_model.py, tests/test_f6_error_model.py): ~2.4 on every synthetic model (frame-level
+// error 1.1e-5 .. 1.5e-5 against the exact path), 11 for a compensated per-channel spread of 2^+-2 (2.6e-5), 35 for 2^+-3 (6.5e-5,
+// beyond the 5e-5 the two-unit layers are held to), 110 for 2^+-4 (1.5e-4).
+constexpr double kF6MaxSpread = 16.0;
+
+double f6_block_spread(const xv_handle* h, const Op& op, const Layer& L) {
+  const int fw = L.mode == 1 ? 3 : L.w, fcin = L.mode == 1 ? 3 * L.cin : L.cin, N = L.cout, nb = fcin / 32;
+  std::vector<double> m((size_t)fcin, 1.0);
+  for (const Op& p : h->ops) {
+    if (p.kind != OP_GEMM || p.out != op.in0 || p.in1 > 0) continue;
+    const Layer& P = h->layers[p.layer];
+    if (!P.has_bn || P.cout != L.cin) break;
+    std::vector<double> s, t;
+    bn_fold(h, P.bn_scope, P.cout, s, t);
+    const auto* bias = P.has_bias ? &T(h, P.bias_name).data : nullptr;
+    for (int r = 0; r < fcin; ++r) {
+      const int c = r % L.cin;                       // grid convolution: kernel row kf * cin + c reads channel c
+      const double sh = (bias ? (double)(*bias)[c] * s[c] : 0.0) + t[c];
+      m[r] = std::sqrt(s[c] * s[c] + sh * sh);
+    }
+    break;
+  }
+  const auto& W = T(h, L.kernel_name).data;          // row (tap * fcin + r), column n
+  std::vector<double> w2((size_t)fcin, 0.0);
+  double num_w = 0.0, den = 0.0;
+  for (int j = 0; j < fw; ++j)
+    for (int b = 0; b < nb; ++b)
+      for (int n = 0; n < N; ++n) {
+        double wmax = 0.0, m2 = 0.0;
+        for (int t = 0; t < 32; ++t) {
+          const int r = b * 32 + t;
+          const double wv = W[((size_t)j * fcin + r) * N + n];
+          wmax = std::max(wmax, std::fabs(wv));
+          w2[r] += wv * wv;
+          m2 += m[r] * m[r];
+          den += m[r] * m[r] * wv * wv;
+        }
+        num_w += m2 * wmax * wmax;
+      }
+  double num_a = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    double mb = 0.0;
+    for (int t = 0; t < 32; ++t) mb = std::max(mb, m[b * 32 + t]);
+    for (int t = 0; t < 32; ++t) num_a += mb * mb * w2[b * 32 + t];
+  }
+  if (!(den > 0.0) || !std::isfinite(num_a + num_w)) return 0.0;     // an all-zero layer: nothing to lose
+  return std::hypot(std::sqrt(num_a / den), std::sqrt(num_w / den));
+}
+
 int upload_layer(xv_handle* h, Layer& L) {
   const int K = L.K(), N = L.cout;
   // row of the packed weight matrix that holds kernel row k: identity, or tap * cin_pad + channel for a first layer
@@ -973,6 +1035,8 @@ int xv_finalize(xv_handle* h) {
       L.use_f6 = h->desc.precision == XV_PREC_F16F6 && h->opt_grid_f6 && L.mode == 1 && L.use_split && L.sw == 1 && L.st == 1 &&
                  L.cin % 128 == 0 && L.cout % 128 == 0;      // (3 cin / 32 channel blocks, taken in quads)
     }
+    // a layer whose 32-channel blocks hold magnitudes too far apart for the block-scaled cross terms stays on three units
+    if (L.use_f6 && f6_block_spread(h, op, L) > kF6MaxSpread) L.use_f6 = false;
   }
   if (h->desc.precision == XV_PREC_F16X3 || h->desc.precision == XV_PREC_F16F6) {
     for (const Op& op : h->ops) {      // creation order is topological: a value's exponent is known before its readers
@@ -1051,6 +1115,7 @@ int xv_check_overflow(xv_handle* h, int reset) {
   XV_HIP(h, hipMemcpy(w.data(), h->ovf_flag.p, w.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
   int32_t v[2] = {w[0], w[1]};
   for (int i = 0; i < kFeatMaxSlots; ++i) v[1] = std::max(v[1], w[(size_t)kFlagWords + i]);     // non-negative floats order like ints
+  if (w[kUttSmallWord]) v[1] = w[kUttSmallWord];                 // an utterance below 2^-8 (flags_snapshot_kernel does the same)
   if (reset) XV_HIP(h, hipMemset(h->ovf_flag.p, 0, w.size() * sizeof(int32_t)));
   return xv_flags_decode(v);
 }
@@ -1096,6 +1161,18 @@ int xv_node_context(const xv_handle* h, int node_id) {
   const Op& op = h->ops[h->nodes[node_id].op];
   const Value& v = h->values[op.out];
   return v.frame_level ? v.ctx : h->final_ctx;
+}
+
+int xv_layer_two_unit(const xv_handle* h, const char* endpoint_name) {
+  if (!h || !endpoint_name) return XV_ERR_INVALID;
+  if (!h->finalized) return XV_ERR_STATE;
+  for (const Node& n : h->nodes)
+    if (n.name == endpoint_name) {
+      const Op& op = h->ops[n.op];
+      if (op.kind != OP_GEMM) return XV_ERR_INVALID;
+      return h->layers[op.layer].use_f6 ? 1 : 0;
+    }
+  return XV_ERR_INVALID;
 }
 
 int xv_plan_create(xv_handle* h, const int32_t* frame_offsets, int batch, int node_id, void* stream, xv_plan** out) {
@@ -1790,6 +1867,7 @@ static int run_plan(xv_handle* h, const xv_plan* p, const float* feats, int feat
             // 48 MB of materialised 5-frame rows); the layer is then an ordinary 5-tap convolution over them
             XV_HIP(h, launch_im2col_sb(feats, feat_ld, L.cin, 1, st.rows_in, ws + st.scratch_off, L.cin_pad, f16,
                                        static_cast<int*>(h->ovf_flag.p), s));
+            if (f16) XV_HIP(h, launch_feat_utt_guard(feats, feat_ld, L.cin, off, B, static_cast<int*>(h->ovf_flag.p), s));
             a.Xsb = ws + st.scratch_off;
             a.ldsbx = L.cin_pad;
             a.cin = L.cin_pad;
@@ -1800,6 +1878,7 @@ static int run_plan(xv_handle* h, const xv_plan* p, const float* feats, int feat
             break;
           }
           XV_HIP(h, launch_im2col_sb(feats, feat_ld, L.cin, L.w, st.M, ws + st.scratch_off, L.Kpad, f16, static_cast<int*>(h->ovf_flag.p), s));
+          if (f16) XV_HIP(h, launch_feat_utt_guard(feats, feat_ld, L.cin, off, B, static_cast<int*>(h->ovf_flag.p), s));
           a.Xsb = ws + st.scratch_off;
           a.ldsbx = L.Kpad;
           a.cin = a.K;

@@ -30,7 +30,7 @@ def default_precision(network_type):
     """What Trainer, the command-line drivers and bench.py run when no precision is named: f16f6 for every network -- the fastest
     precision, under the same GPU parity suite as the others (tests/test_gpu_parity.py: every endpoint of the three networks,
     both poolings, ragged batches, the rescaled-layer and feature-range tests), with both ends of the fp16 range guarded (values
-    beyond +-65504 and feature batches below 2^-8 never produce wrong vectors: Trainer and the command-line driver run such a batch again in bf16x3).  Its two-unit
+    beyond +-65504 and utterances whose features all sit below 2^-8 never produce wrong vectors: Trainer and the command-line driver run such a batch again in bf16x3).  Its two-unit
     kernel covers the 5 / 7 / 9-tap convolutions of the (extended) TDNN and the stride-1 3 x 3 convolutions of the ResNet stages of
     128 channels and more; "bf16x3" (full fp32 exponent range, no such refusals) stays one argument away -- and is what a defaulted
     Trainer uses for a model none of whose layers the two-unit kernel applies to (channel counts not multiples of 128)."""
@@ -382,10 +382,21 @@ class Trainer(object):
         _, info = self._plan(np.ascontiguousarray(offsets, dtype=np.int32), node or self.embeddings)
         return {f[0]: getattr(info, f[0]) for f in info._fields_}
 
+    def runs_two_unit(self, endpoint):
+        """True if the layer that produces `endpoint` runs on the two-unit kernel (precision f16f6 only: the 5-, 7- and 9-tap
+        layers over quads of 32-channel blocks, unless the load demoted them to f16x3 for the spread of magnitudes inside a
+        block; xv_layer_two_unit).  KeyError for a name that is not a layer endpoint."""
+        if not self.is_loaded:
+            self._lazy_load()
+        rc = int(self._lib.xv_layer_two_unit(self._h, endpoint.encode()))
+        if rc < 0:
+            raise KeyError("%s is not the endpoint of a layer" % endpoint)
+        return rc == 1
+
     def check_overflow(self):
         """fp16 split precisions only: 1 if a feature or activation went beyond the fp16 range (+-65504) in a forward since
-        the last check, 2 if every feature staged since then was below 2^-8 in magnitude (the low halves of the split are
-        subnormal there), else 0 (xv_check_overflow; synchronous -- call after the results have been fetched)."""
+        the last check, 2 if an utterance staged since then had all its features below 2^-8 in magnitude (the low halves of the
+        split are subnormal there), else 0 (xv_check_overflow; synchronous -- call after the results have been fetched)."""
         if self._precision not in _F16_RANGE or self._h is None:
             return 0
         return _lib.check(self._lib.xv_check_overflow(self._h, 1), self._h)
@@ -405,7 +416,7 @@ class Trainer(object):
             raise FloatingPointError("the %s path converted a value beyond the fp16 range (+-65504): an input feature or an "
                                      "activation is too large; run with precision 'bf16x3' (full fp32 range) or 'f32'" % self._precision)
         if code == 2:
-            raise FloatingPointError("every input feature of the batch is below 2^-8 in magnitude: the %s path would lose precision "
+            raise FloatingPointError("every input feature of an utterance of the batch is below 2^-8 in magnitude: the %s path would lose precision "
                                      "silently (subnormal low halves); rescale the features or run with precision 'bf16x3'" % self._precision)
 
     def decode_flags(self, host_flags):
