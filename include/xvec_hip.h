@@ -256,6 +256,36 @@ int xv_length_normalize(int device, const float* x_dev, int64_t ldx, int64_t row
 int xv_speaker_mean(int device, const float* x_dev, int64_t ldx, int dim, const int32_t* spk_offsets_dev,
                     const int32_t* utt_index_dev, int64_t num_speakers, float* out_dev, int64_t ldo, void* stream);
 
+/* ---- cosine scoring on the GPU (csrc/score.hip): the back-end the reference runs as Kaldi binaries and as a numpy
+ * double loop.  All arithmetic is fp32 with exact products; a score of two prepared (unit) rows of length d is within
+ * (d + 8) * 2^-24 of the exact value.  Rows are device float32; every argument check comes before the first HIP call.
+ * xv_score_prepare = `ivector-subtract-global-mean` | `transform-vec` | `ivector-normalize-length`
+ *   (egs/voxceleb/v1/run.sh:404-407) and the normalisation of misc/utils.py:317, each step optional and in this order:
+ *   y = x - mean (mean_dev [d_in] or NULL); y = T y (transform_dev [d_out, t_cols] or NULL; t_cols == d_in, or d_in + 1 with
+ *   the last column an offset, i.e. the input extended by a constant 1); y / sqrt(sum y^2 + eps) when `normalize`
+ *   (eps 0: Kaldi, a zero row stays zero; eps 1e-12: misc/utils.py).  Without a transform d_out == d_in and out_dev may be
+ *   x_dev; with one, d_in <= 2048 (XV_ERR_UNSUPPORTED beyond) and out_dev is a different buffer.
+ * xv_score_matrix = the score matrix of misc/utils.py:318 (`np.dot(embeddings, np.transpose(embeddings))`), for two sets:
+ *   out[i, j] = a[i] . b[j], a [n, d], b [m, d], out [n, ldo].
+ * xv_score_pairs = `ivector-compute-dot-products` (egs/voxceleb/v1/run.sh:362-365,408): out[k] = a[ia[k]] . b[ib[k]].
+ *   The caller checks 0 <= ia[k] < n, 0 <= ib[k] < m on the host (tf_kaldi_speaker_amd.scoring raises XV_ERR_INVALID); an
+ *   index that slips through is never followed: its score is NaN.  Repeats are bit-identical.
+ * xv_score_histogram = the double loop of misc/utils.py:320-327 without the matrix: every score is counted in
+ *   hist_same[bin] (labels_a[i] == labels_b[j]) or hist_diff[bin], bin = clamp(floor((s + 1) * nbins / 2), 0, nbins - 1),
+ *   nbins a power of two in 256..65536.  `self` (a == b, same labels): only the pairs i < j.  The histograms [nbins] are
+ *   uint64 and are ADDED to (the caller zeroes them); the counts are exact and independent of the order of execution.
+ * 1 <= d <= 2048 in the last three, anything else is XV_ERR_UNSUPPORTED. */
+int xv_score_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* mean_dev,
+                     const float* transform_dev, int64_t ldt, int d_out, int t_cols, int normalize, float eps, float* out_dev,
+                     int64_t ldo, void* stream);
+int xv_score_matrix(int device, const float* a_dev, int64_t lda, int64_t n, const float* b_dev, int64_t ldb, int64_t m, int d,
+                    float* out_dev, int64_t ldo, void* stream);
+int xv_score_pairs(int device, const float* a_dev, int64_t lda, int64_t n, const float* b_dev, int64_t ldb, int64_t m, int d,
+                   const int32_t* ia_dev, const int32_t* ib_dev, int64_t npairs, float* out_dev, void* stream);
+int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, const int32_t* labels_a_dev, const float* b_dev,
+                       int64_t ldb, int64_t m, const int32_t* labels_b_dev, int d, int self, int nbins, uint64_t* hist_same_dev,
+                       uint64_t* hist_diff_dev, void* stream);
+
 /* ---- host-side ark I/O (csrc/ark_io.cpp; no HIP calls, usable without a GPU) ---------------------
  * Batch counterpart of dataset/kaldi_io.py read_mat_ark (:974-994, records per _read_mat_binary
  * :1014-1031 / _read_compressed_mat :1071-1115) and write_vec_flt (:915-946): the extraction driver

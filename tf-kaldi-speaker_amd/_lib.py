@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libxvec_hip.so")
 
 XV_MAX_ATT_LAYERS = 4
 XV_OK = 0
+XV_ERR_INVALID = -1
+XV_ERR_UNSUPPORTED = -2
 XV_ERR_TOO_SHORT = -7
 XV_PREC_F32 = 0
 XV_PREC_BF16X3 = 1
@@ -27,6 +29,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_plan_create", "xv_plan_query", "xv_plan_destroy", "xv_forward", "xv_profile_begin", "xv_profile_end",
            "xv_destroy", "xv_last_error",
            "xv_frontend_cmn_select", "xv_length_normalize", "xv_speaker_mean",
+           "xv_score_prepare", "xv_score_matrix", "xv_score_pairs", "xv_score_histogram",
            "xv_ark_open", "xv_ark_open_scp", "xv_ark_scp_count", "xv_ark_scp_shapes", "xv_ark_next_batch", "xv_ark_pending_shape", "xv_ark_skipped", "xv_ark_set_copy_threads", "xv_ark_error", "xv_ark_close", "xv_ark_format_vectors", "xv_crc32c", "xv_pack_rows"]
 
 
@@ -105,6 +108,10 @@ def load():
     lib.xv_frontend_cmn_select.argtypes = [i32, vp, i32, i32, vp, i32, vp, i64, i32, i32, i32, vp, vp, vp]
     lib.xv_length_normalize.argtypes = [i32, vp, i64, i64, i32, i32, vp, i64, vp]
     lib.xv_speaker_mean.argtypes = [i32, vp, i64, i32, vp, vp, i64, vp, i64, vp]
+    lib.xv_score_prepare.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, i32, i32, i32, C.c_float, vp, i64, vp]
+    lib.xv_score_matrix.argtypes = [i32, vp, i64, i64, vp, i64, i64, i32, vp, i64, vp]
+    lib.xv_score_pairs.argtypes = [i32, vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp]
+    lib.xv_score_histogram.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, vp]
     lib.xv_ark_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
     lib.xv_ark_open_scp.argtypes = [C.c_char_p, C.POINTER(vp)]
     lib.xv_ark_scp_count.argtypes = [vp]

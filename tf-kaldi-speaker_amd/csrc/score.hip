@@ -1,0 +1,407 @@
+// Cosine scoring of x-vectors on the GPU: row preparation, score matrices, trial lists, score histograms.
+//
+// The reference scores in two places, both on the host:
+//   egs/voxceleb/v1/run.sh:362-365   ivector-compute-dot-products over length-normalised x-vectors (plain cosine)
+//   egs/voxceleb/v1/run.sh:404-408   ivector-subtract-global-mean | transform-vec | ivector-normalize-length in front of it
+//   misc/utils.py:307-346            compute_cos_pairwise_eer: embeddings / sqrt(sum x^2 + 1e-12), the full score matrix
+//                                    in numpy and a Python double loop over i < j (hence its down-sampling to 1000 rows)
+// Kaldi is not part of the reference tree; the Kaldi steps restate the published algorithms (**parity unpinned**, as
+// csrc/post.hip), checked against tests/helpers/ref_score.py.
+//
+// All arithmetic is fp32 with exact products and fp32 accumulation, so one error bound ((d + 8) * 2^-24 per score of
+// unit rows) holds for every entry point.
+//
+//  * row_prepare_kernel: one wave per row; y = x - mean, then y / sqrt(sum y^2 + eps).  The sum of squares is taken of
+//    the row scaled by the power of two of its largest element (exact), so rows of any magnitude neither overflow nor flush.
+//  * score_tile_kernel: C = A * B^T over prepared rows with v_mfma_f32_32x32x2_f32, the tile shape and LDS layout of
+//    csrc/gemm_f32.hip (128 x 128 per workgroup, 64 x 64 per wave, K tiles of 32 in [row][32 + 4] floats, register-staged
+//    double buffering), K = d taken whole.  Unlike the layer GEMM nothing is pre-packed: the loaders zero-fill the edges of
+//    n, m and d themselves.  A workgroup walks tiles with a stride of the grid; tiles are ordered in groups of eight
+//    tile rows so that the workgroups in flight share 8 A panels and ~64 B panels.  Epilogues (compile time):
+//      EPI_MATRIX       fp32 [n, m] with a leading dimension
+//      EPI_AFFINE       the same with a vector subtracted from the A rows at load and column d of B added as an offset
+//                       (ivector-subtract-global-mean + transform-vec of the prepare step)
+//      EPI_HIST_LDS     same-label / different-label histograms of the scores, uint32 counts in LDS (ds_add_u32) for the
+//                       whole walk of the workgroup, flushed once with 64-bit vector atomics (2 * nbins * 4 bytes <= 64 KB)
+//      EPI_HIST_GLOBAL  the same with one 64-bit vector atomic per score (bin counts that do not fit in LDS)
+//    Integer adds commute, so the counts are exact and independent of the order of arrival.
+//  * score_pairs_kernel: trial lists.  16 lanes per trial (four trials per wave), 16-byte row loads, four fmaf chains per
+//    lane combined in a fixed order and a DPP butterfly over the 16 lanes: repeats are bit-identical.
+#include <mutex>
+
+#include "xv_kernels.h"
+
+namespace xv {
+
+typedef float sf32x16 __attribute__((ext_vector_type(16)));
+typedef float sf32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int SBM = 128, SBN = 128, SBK = 32;
+constexpr int SLDT = SBK + 4;                 // padded LDS row (floats): conflict-free ds_read_b128, see csrc/gemm_f32.hip
+constexpr int STILE_F = SBM * SLDT;           // floats per operand tile
+constexpr int SGROUP = 8;                     // tile rows per group of the tile order
+constexpr size_t kOperandBytes = (size_t)4 * STILE_F * sizeof(float);
+constexpr int kScoreLdsBins = 8192;           // largest bin count whose two uint32 histograms stay in LDS (64 KB) beside the operand tiles
+constexpr size_t kLabelBytes = (size_t)(SBM + SBN) * sizeof(int32_t);
+
+enum { EPI_MATRIX = 0, EPI_AFFINE = 1, EPI_HIST_LDS = 2, EPI_HIST_GLOBAL = 3 };
+
+__device__ __forceinline__ float dpp_row_sum16(float x) {       // sum over the 16 lanes of a DPP row, in every lane
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));   // row_half_mirror
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));   // row_mirror
+  return x;
+}
+
+// ---------------------------------------------------------------------------------------------- prepare
+__global__ __launch_bounds__(256) void row_prepare_kernel(const float* __restrict__ x, int64_t ldx, int64_t rows, int dim,
+                                                          const float* __restrict__ mean, int normalize, float eps,
+                                                          float* __restrict__ y, int64_t ldy) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float* xr = x + r * ldx;
+  float* yr = y + r * ldy;
+  auto at = [&](int c) { return mean ? xr[c] - mean[c] : xr[c]; };
+  if (!normalize) {
+    for (int c = lane; c < dim; c += 64) yr[c] = at(c);
+    return;
+  }
+  float mx = 0.f;
+  for (int c = lane; c < dim; c += 64) mx = fmaxf(mx, fabsf(at(c)));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (!(mx > 0.f) || !(mx <= 3.4028234e38f)) {     // zero row: stays zero (eps == 0) or is zero anyway; inf / nan rows: copied
+    for (int c = lane; c < dim; c += 64) yr[c] = at(c);
+    return;
+  }
+  const int e = ilogbf(mx);                         // row * 2^-e has its largest element in [1, 2): exact scaling
+  float ss = 0.f;
+  for (int c = lane; c < dim; c += 64) {
+    const float v = ldexpf(at(c), -e);
+    ss = fmaf(v, v, ss);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  // x / sqrt(sum x^2 + eps) = (x 2^-e) / sqrt(ss + eps 2^-2e); where eps 2^-2e is out of range the sum of squares is
+  // far below one ulp of eps and the row is x / sqrt(eps)
+  const float es = ldexpf(ldexpf(eps, -e), -e);
+  if (es <= 3.4028234e38f) {
+    const float inv = 1.0f / sqrtf(ss + es);
+    for (int c = lane; c < dim; c += 64) yr[c] = ldexpf(at(c), -e) * inv;
+  } else {
+    const float inv = 1.0f / sqrtf(eps);
+    for (int c = lane; c < dim; c += 64) yr[c] = at(c) * inv;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- tiles
+struct ScoreArgs {
+  const float* A; int64_t lda; int n;
+  const float* B; int64_t ldb; int m;
+  int d;
+  float* C; int64_t ldc;                 // matrix epilogues
+  const float* a_sub;                    // EPI_AFFINE: subtracted from every A row (or null)
+  int b_offset;                          // EPI_AFFINE: column d of B is added to the output column
+  const int32_t* la; const int32_t* lb;  // histogram epilogues
+  int self, nbins;
+  unsigned long long* hs; unsigned long long* hd;
+  int nMt, nNt;
+};
+
+template <int EPI, bool VEC>
+__global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* As = smem;                    // [2][SBM][SLDT]
+  float* Bs = smem + 2 * STILE_F;      // [2][SBN][SLDT]
+  int32_t* lab = reinterpret_cast<int32_t*>(smem + 4 * STILE_F);          // [SBM + SBN] labels of the tile
+  unsigned* hist = reinterpret_cast<unsigned*>(lab + SBM + SBN);          // EPI_HIST_LDS: [2][nbins]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r32 = lane & 31, h = lane >> 5;
+  const int c4 = tid & 7, lr = tid >> 3;          // staging map: thread -> (row lr + 32*i, float4 column c4)
+  const int nk = (p.d + SBK - 1) / SBK;
+  const float half_bins = 0.5f * (float)p.nbins;
+
+  if (EPI == EPI_HIST_LDS) {
+    for (int i = tid; i < 2 * p.nbins; i += 256) hist[i] = 0u;
+    __syncthreads();
+  }
+
+  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    // groups of SGROUP tile rows, walked column by column
+    const int64_t per_group = (int64_t)SGROUP * p.nNt;
+    const int g = (int)(t / per_group);
+    const int gm = min(SGROUP, p.nMt - g * SGROUP);
+    const int64_t tg = t - g * per_group;
+    const int nt = (int)(tg / gm);
+    const int mt = g * SGROUP + (int)(tg - (int64_t)nt * gm);
+    if ((EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) && p.self && nt < mt) continue;   // strictly below the diagonal (uniform)
+    const int m0 = mt * SBM, n0 = nt * SBN;
+
+    sf32x4 ra[4], rb[4];
+    auto load_rows = [&](const float* base, int64_t ld, int row0, int nrows, int kt, sf32x4 (&r)[4], const float* sub) {
+      const int k = kt * SBK + c4 * 4;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = row0 + lr + 32 * i;
+        sf32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (row < nrows && k < p.d) {
+          const float* src = base + (int64_t)row * ld + k;
+          if (VEC && k + 4 <= p.d) {
+            v = *reinterpret_cast<const sf32x4*>(src);
+            if (EPI == EPI_AFFINE && sub) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] -= sub[k + e];
+            }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (k + e < p.d) v[e] = (EPI == EPI_AFFINE && sub) ? src[e] - sub[k + e] : src[e];
+          }
+        }
+        r[i] = v;
+      }
+    };
+    auto load_tiles = [&](int kt) {
+      load_rows(p.A, p.lda, m0, p.n, kt, ra, p.a_sub);
+      load_rows(p.B, p.ldb, n0, p.m, kt, rb, nullptr);
+    };
+    auto store_tiles = [&](int buf) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = lr + 32 * i;
+        *reinterpret_cast<sf32x4*>(As + buf * STILE_F + row * SLDT + c4 * 4) = ra[i];
+        *reinterpret_cast<sf32x4*>(Bs + buf * STILE_F + row * SLDT + c4 * 4) = rb[i];
+      }
+    };
+
+    sf32x16 acc[2][2];                 // acc[ai][bi]: 32 A rows x 32 B rows
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    if (EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) {
+      const int row = tid < SBM ? m0 + tid : n0 + tid - SBM;
+      const bool ok = tid < SBM ? row < p.n : row < p.m;
+      lab[tid] = ok ? (tid < SBM ? p.la[row] : p.lb[row]) : 0;
+    }
+    load_tiles(0);
+    store_tiles(0);
+    __syncthreads();
+
+    const float* a_base = As + (wm * 64 + r32) * SLDT + 4 * h;
+    const float* b_base = Bs + (wn * 64 + r32) * SLDT + 4 * h;
+    for (int kt = 0; kt < nk; ++kt) {
+      const int cur = kt & 1;
+      if (kt + 1 < nk) load_tiles(kt + 1);
+      const float* ap = a_base + cur * STILE_F;
+      const float* bp = b_base + cur * STILE_F;
+#pragma unroll
+      for (int q = 0; q < SBK / 8; ++q) {
+        // the k index of an MFMA is a summation label only: lane (r, h) feeds k = 8q + 4h + j of both operands
+        const sf32x4 a0 = *reinterpret_cast<const sf32x4*>(ap + q * 8);
+        const sf32x4 a1 = *reinterpret_cast<const sf32x4*>(ap + 32 * SLDT + q * 8);
+        const sf32x4 b0 = *reinterpret_cast<const sf32x4*>(bp + q * 8);
+        const sf32x4 b1 = *reinterpret_cast<const sf32x4*>(bp + 32 * SLDT + q * 8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b0[j], acc[0][0], 0, 0, 0);
+          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b1[j], acc[0][1], 0, 0, 0);
+          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b0[j], acc[1][0], 0, 0, 0);
+          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b1[j], acc[1][1], 0, 0, 0);
+        }
+      }
+      if (kt + 1 < nk) store_tiles(cur ^ 1);
+      __syncthreads();
+    }
+
+    // accumulator layout: element e of lane (r32, h) is D[8 * (e / 4) + 4 * h + e % 4][r32] (A row, B row)
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi) {
+      const int jl = wn * 64 + bi * 32 + r32;
+      const int gj = n0 + jl;
+      if (gj >= p.m) continue;
+      float offs = 0.f;
+      int lbj = 0;
+      if (EPI == EPI_AFFINE) offs = p.b_offset ? p.B[(int64_t)gj * p.ldb + p.d] : 0.f;
+      if (EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) lbj = lab[SBM + jl];
+#pragma unroll
+      for (int ai = 0; ai < 2; ++ai)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int il = wm * 64 + ai * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
+          const int gi = m0 + il;
+          if (gi >= p.n) continue;
+          const float s = acc[ai][bi][e];
+          if (EPI == EPI_MATRIX || EPI == EPI_AFFINE) {
+            p.C[(int64_t)gi * p.ldc + gj] = s + offs;
+          } else {
+            if (p.self && gi >= gj) continue;
+            const float fb = fminf(fmaxf(floorf((s + 1.0f) * half_bins), 0.f), (float)(p.nbins - 1));
+            const int bin = (int)fb;
+            const bool same = lab[il] == lbj;
+            if (EPI == EPI_HIST_LDS)
+              atomicAdd(&hist[(same ? 0 : p.nbins) + bin], 1u);
+            else
+              atomicAdd((same ? p.hs : p.hd) + bin, 1ull);
+          }
+        }
+    }
+    if (EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) __syncthreads();     // the labels are rewritten by the next tile
+  }
+
+  if (EPI == EPI_HIST_LDS) {
+    __syncthreads();
+    for (int i = tid; i < 2 * p.nbins; i += 256) {
+      const unsigned c = hist[i];
+      if (c) atomicAdd(i < p.nbins ? p.hs + i : p.hd + (i - p.nbins), (unsigned long long)c);
+    }
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+template <int EPI, bool VEC>
+hipError_t launch_tiles(const ScoreArgs& a, unsigned grid, size_t smem, hipStream_t s) {
+  static std::mutex mu;            // per-device attribute; any thread may make the first launch on a device
+  static size_t set_for[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    if (set_for[dev & 63] < smem) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(score_tile_kernel<EPI, VEC>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e != hipSuccess) return e;
+      set_for[dev & 63] = smem;
+    }
+  }
+  hipLaunchKernelGGL((score_tile_kernel<EPI, VEC>), dim3(grid), dim3(256), smem, s, a);
+  return hipGetLastError();
+}
+
+template <int EPI>
+hipError_t launch_tiles_v(const ScoreArgs& a, unsigned grid, size_t smem, hipStream_t s) {
+  const bool vec = aligned16(a.A) && aligned16(a.B) && a.lda % 4 == 0 && a.ldb % 4 == 0;
+  return vec ? launch_tiles<EPI, true>(a, grid, smem, s) : launch_tiles<EPI, false>(a, grid, smem, s);
+}
+
+hipError_t compute_units(int* cus) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  return hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+}
+
+// ---------------------------------------------------------------------------------------------- pairs
+template <bool VEC>
+__global__ __launch_bounds__(256) void score_pairs_kernel(const float* __restrict__ a, int64_t lda, int n,
+                                                          const float* __restrict__ b, int64_t ldb, int m, int d,
+                                                          const int32_t* __restrict__ ia, const int32_t* __restrict__ ib,
+                                                          int64_t npairs, float* __restrict__ out) {
+  const int sub = threadIdx.x & 15;
+  const int64_t k = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool have = k < npairs;
+  const int i = have ? ia[k] : 0, j = have ? ib[k] : 0;
+  const bool ok = have && i >= 0 && i < n && j >= 0 && j < m;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  if (ok) {
+    const float* x = a + (int64_t)i * lda;
+    const float* y = b + (int64_t)j * ldb;
+    for (int c = sub * 4; c < d; c += 64) {
+      if (VEC && c + 4 <= d) {
+        const sf32x4 u = *reinterpret_cast<const sf32x4*>(x + c);
+        const sf32x4 v = *reinterpret_cast<const sf32x4*>(y + c);
+        s0 = fmaf(u[0], v[0], s0);
+        s1 = fmaf(u[1], v[1], s1);
+        s2 = fmaf(u[2], v[2], s2);
+        s3 = fmaf(u[3], v[3], s3);
+      } else {
+        if (c < d) s0 = fmaf(x[c], y[c], s0);
+        if (c + 1 < d) s1 = fmaf(x[c + 1], y[c + 1], s1);
+        if (c + 2 < d) s2 = fmaf(x[c + 2], y[c + 2], s2);
+        if (c + 3 < d) s3 = fmaf(x[c + 3], y[c + 3], s3);
+      }
+    }
+  }
+  const float s = dpp_row_sum16((s0 + s1) + (s2 + s3));      // every lane of the wave takes part
+  if (have && sub == 0) out[k] = ok ? s : __builtin_nanf("");  // an index the host let through is marked, never followed
+}
+
+}  // namespace
+
+hipError_t launch_score_prepare_rows(const float* x, int64_t ldx, int64_t rows, int dim, const float* mean, int normalize,
+                                     float eps, float* y, int64_t ldy, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(row_prepare_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, ldx, rows, dim, mean, normalize,
+                     eps, y, ldy);
+  return hipGetLastError();
+}
+
+static void tile_counts(ScoreArgs& p) {
+  p.nMt = (p.n + SBM - 1) / SBM;
+  p.nNt = (p.m + SBN - 1) / SBN;
+}
+
+hipError_t launch_score_matrix(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d,
+                               const float* a_sub, int b_offset, float* out, int64_t ldo, hipStream_t s) {
+  if (n <= 0 || m <= 0) return hipSuccess;
+  ScoreArgs p = {};
+  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = d;
+  p.C = out; p.ldc = ldo; p.a_sub = a_sub; p.b_offset = b_offset;
+  tile_counts(p);
+  int cus = 0;
+  hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+  const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
+  if (a_sub || b_offset) return launch_tiles_v<EPI_AFFINE>(p, grid, kOperandBytes, s);
+  return launch_tiles_v<EPI_MATRIX>(p, grid, kOperandBytes, s);
+}
+
+hipError_t launch_score_histogram(const float* a, int64_t lda, int n, const int32_t* la, const float* b, int64_t ldb, int m,
+                                  const int32_t* lb, int d, int self, int nbins, unsigned long long* hs,
+                                  unsigned long long* hd, hipStream_t s) {
+  if (n <= 0 || m <= 0) return hipSuccess;
+  ScoreArgs p = {};
+  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = d;
+  p.la = la; p.lb = lb; p.self = self; p.nbins = nbins; p.hs = hs; p.hd = hd;
+  tile_counts(p);
+  int cus = 0;
+  hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+  const bool in_lds = nbins <= kScoreLdsBins;
+  const size_t smem = kOperandBytes + kLabelBytes + (in_lds ? (size_t)2 * nbins * sizeof(unsigned) : 0);
+  const int per_cu = smem * 2 <= 160 * 1024 ? 2 : 1;
+  int64_t grid = (int64_t)cus * per_cu;
+  // a workgroup's LDS counters are 32 bits wide: at most 2^16 tiles of 2^14 scores each per workgroup
+  if (in_lds && (ntiles + grid - 1) / grid > 65536) grid = (ntiles + 65535) / 65536;
+  if (grid > ntiles) grid = ntiles;
+  if (in_lds) return launch_tiles_v<EPI_HIST_LDS>(p, (unsigned)grid, smem, s);
+  return launch_tiles_v<EPI_HIST_GLOBAL>(p, (unsigned)grid, smem, s);
+}
+
+hipError_t launch_score_pairs(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d, const int32_t* ia,
+                              const int32_t* ib, int64_t npairs, float* out, hipStream_t s) {
+  if (npairs <= 0) return hipSuccess;
+  const bool vec = aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
+  const dim3 grid((unsigned)((npairs + 15) / 16));
+  if (vec)
+    hipLaunchKernelGGL(score_pairs_kernel<true>, grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out);
+  else
+    hipLaunchKernelGGL(score_pairs_kernel<false>, grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out);
+  return hipGetLastError();
+}
+
+}  // namespace xv

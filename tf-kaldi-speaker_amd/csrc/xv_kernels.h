@@ -211,6 +211,21 @@ hipError_t launch_length_norm(const float* x, int64_t ldx, int64_t rows, int dim
 hipError_t launch_speaker_mean(const float* x, int64_t ldx, int dim, const int32_t* spk_off, const int32_t* utt,
                                int64_t num_spk, float* out, int64_t ldo, hipStream_t s);
 
+// cosine scoring (csrc/score.hip): egs/voxceleb/v1/run.sh:362-365,404-408 and misc/utils.py:307-346
+// y = x - mean (mean may be null), then y / sqrt(sum y^2 + eps) when `normalize`; in place (y == x) is allowed
+hipError_t launch_score_prepare_rows(const float* x, int64_t ldx, int64_t rows, int dim, const float* mean, int normalize,
+                                     float eps, float* y, int64_t ldy, hipStream_t s);
+// out[i, j] = sum_k (a[i, k] - a_sub[k]) * b[j, k] (+ b[j, d] when b_offset); a_sub may be null; 1 <= d <= 2048
+hipError_t launch_score_matrix(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d,
+                               const float* a_sub, int b_offset, float* out, int64_t ldo, hipStream_t s);
+// hs / hd [nbins] += counts of the scores a[i] . b[j] with la[i] == lb[j] / != ; `self`: only i < j
+hipError_t launch_score_histogram(const float* a, int64_t lda, int n, const int32_t* la, const float* b, int64_t ldb, int m,
+                                  const int32_t* lb, int d, int self, int nbins, unsigned long long* hs,
+                                  unsigned long long* hd, hipStream_t s);
+// out[k] = a[ia[k]] . b[ib[k]]; an index out of range writes NaN (the caller checks its indices on the host)
+hipError_t launch_score_pairs(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d, const int32_t* ia,
+                              const int32_t* ib, int64_t npairs, float* out, hipStream_t s);
+
 // attention scores (model/pooling.py:189-194): score[r, h] = scale * sum_d key[r, h*dk_h + d] * q[h, d]
 // (split_key) or sum_d key[r, d] * q[h, d] (no split; dk_h == dk).
 hipError_t launch_att_scores(const float* key, int64_t ldk, int64_t rows, const float* query, int H,

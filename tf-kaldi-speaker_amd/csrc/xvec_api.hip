@@ -2139,6 +2139,88 @@ int xv_speaker_mean(int device, const float* x_dev, int64_t ldx, int dim, const 
   return XV_OK;
 }
 
+int xv_score_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* mean_dev,
+                     const float* transform_dev, int64_t ldt, int d_out, int t_cols, int normalize, float eps, float* out_dev,
+                     int64_t ldo, void* stream) {
+  if (!x_dev || !out_dev) return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: null pointer");
+  if (n < 0 || n > INT32_MAX || d_in < 1 || d_out < 1 || ldx < d_in || ldo < d_out || !(eps >= 0.f))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: bad dimensions");
+  if (transform_dev) {
+    if (t_cols != d_in && t_cols != d_in + 1)
+      return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: a transform for %d-dimensional rows has %d or %d columns, not %d", d_in,
+                  d_in, d_in + 1, t_cols);
+    if (ldt < t_cols) return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: bad dimensions");
+    if (out_dev == x_dev) return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: a transform cannot run in place");
+    if (d_in > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_score_prepare: transforms of more than 2048 columns");
+  } else if (d_out != d_in) {
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: d_out != d_in without a transform");
+  }
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e;
+  if (transform_dev) {
+    e = launch_score_matrix(x_dev, ldx, (int)n, transform_dev, ldt, d_out, d_in, mean_dev, t_cols == d_in + 1, out_dev, ldo, s);
+    if (e == hipSuccess && normalize) e = launch_score_prepare_rows(out_dev, ldo, n, d_out, nullptr, 1, eps, out_dev, ldo, s);
+  } else {
+    e = launch_score_prepare_rows(x_dev, ldx, n, d_in, mean_dev, normalize, eps, out_dev, ldo, s);
+  }
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "score_prepare launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+// shared argument check of the three scoring entry points: prepared rows a [n, d], b [m, d]
+static int score_operands(const char* who, const float* a, int64_t lda, int64_t n, const float* b, int64_t ldb, int64_t m, int d) {
+  if (!a || !b) return fail(nullptr, XV_ERR_INVALID, "%s: null pointer", who);
+  if (d < 1 || d > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= d <= 2048, got %d", who, d);
+  if (n < 0 || m < 0 || n > INT32_MAX || m > INT32_MAX || lda < d || ldb < d) return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", who);
+  return XV_OK;
+}
+
+int xv_score_matrix(int device, const float* a_dev, int64_t lda, int64_t n, const float* b_dev, int64_t ldb, int64_t m, int d,
+                    float* out_dev, int64_t ldo, void* stream) {
+  if (const int rc = score_operands("xv_score_matrix", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
+  if (!out_dev || ldo < m) return fail(nullptr, XV_ERR_INVALID, "xv_score_matrix: bad output");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_score_matrix(a_dev, lda, (int)n, b_dev, ldb, (int)m, d, nullptr, 0, out_dev, ldo,
+                                           static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "score_matrix launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_score_pairs(int device, const float* a_dev, int64_t lda, int64_t n, const float* b_dev, int64_t ldb, int64_t m, int d,
+                   const int32_t* ia_dev, const int32_t* ib_dev, int64_t npairs, float* out_dev, void* stream) {
+  if (const int rc = score_operands("xv_score_pairs", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
+  if (npairs < 0 || npairs > ((int64_t)1 << 34)) return fail(nullptr, XV_ERR_INVALID, "xv_score_pairs: bad pair count");
+  if (npairs > 0 && (!ia_dev || !ib_dev || !out_dev)) return fail(nullptr, XV_ERR_INVALID, "xv_score_pairs: null pointer");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_score_pairs(a_dev, lda, (int)n, b_dev, ldb, (int)m, d, ia_dev, ib_dev, npairs, out_dev,
+                                          static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "score_pairs launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, const int32_t* labels_a_dev, const float* b_dev,
+                       int64_t ldb, int64_t m, const int32_t* labels_b_dev, int d, int self, int nbins, uint64_t* hist_same_dev,
+                       uint64_t* hist_diff_dev, void* stream) {
+  if (const int rc = score_operands("xv_score_histogram", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
+  if (nbins < 256 || nbins > 65536 || (nbins & (nbins - 1)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: nbins is a power of two in 256..65536, got %d", nbins);
+  if (!labels_a_dev || !labels_b_dev || !hist_same_dev || !hist_diff_dev || hist_same_dev == hist_diff_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: null pointer");
+  if (self && (a_dev != b_dev || n != m || lda != ldb || labels_a_dev != labels_b_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: self needs the same rows and labels on both sides");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_score_histogram(a_dev, lda, (int)n, labels_a_dev, b_dev, ldb, (int)m, labels_b_dev, d, self ? 1 : 0, nbins,
+                                              reinterpret_cast<unsigned long long*>(hist_same_dev),
+                                              reinterpret_cast<unsigned long long*>(hist_diff_dev), static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "score_histogram launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 void xv_destroy(xv_handle* h) {
   if (!h) return;
   {

@@ -1,0 +1,270 @@
+"""Cosine scoring of x-vectors on the GPU (csrc/score.hip through the C ABI: xv_score_prepare / xv_score_matrix /
+xv_score_pairs / xv_score_histogram): what the reference does with Kaldi binaries in its cosine back-end
+(egs/voxceleb/v1/run.sh:362-365 plain cosine, :404-408 mean-subtract + transform-vec + length-norm +
+ivector-compute-dot-products) and with a numpy double loop in its model-selection metric (compute_cos_pairwise_eer,
+misc/utils.py:307-346).  PLDA stays with Kaldi.
+
+Everything is fp32 with exact products: a score of two prepared rows of length d is within (d + 8) * 2^-24 of the exact
+value.  Arrays go in and come out as numpy; a float32 torch tensor that already lives on the device is taken as it is,
+and `as_tensor=True` keeps a result there.  No CPU path: without a HIP device every function here except
+eer_from_histograms and read_trials raises RuntimeError."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _need_device():
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("no HIP device visible: scoring has no CPU fallback")
+    return torch
+
+
+def _rows(x, device, what):
+    """[n, d] float32 on cuda:device, contiguous (numpy array or torch tensor)."""
+    torch = _need_device()
+    if isinstance(x, torch.Tensor):
+        t = x.to(device="cuda:%d" % device, dtype=torch.float32)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to("cuda:%d" % device)
+    if t.dim() != 2:
+        raise ValueError("%s: expected a [n, d] array, got shape %s" % (what, tuple(t.shape)))
+    return t.contiguous()
+
+
+def _shape2(x, what):
+    shape = tuple(x.shape)
+    if len(shape) != 2:
+        raise ValueError("%s: expected a [n, d] array, got shape %s" % (what, shape))
+    return shape
+
+
+def check_transform(d_in, transform_shape):
+    """The `transform-vec` rule: a transform for d_in-dimensional rows is [d_out, d_in] or [d_out, d_in + 1] (the last
+    column is an offset: the input is extended by a constant 1).  -> (d_out, t_cols); ValueError otherwise."""
+    if len(transform_shape) != 2 or transform_shape[0] < 1:
+        raise ValueError("transform: expected a [d_out, d_in] or [d_out, d_in + 1] matrix, got shape %s" % (tuple(transform_shape),))
+    d_out, t_cols = int(transform_shape[0]), int(transform_shape[1])
+    if t_cols not in (d_in, d_in + 1):
+        raise ValueError("transform: %d columns for rows of dimension %d (expected %d, or %d with an offset column)"
+                         % (t_cols, d_in, d_in, d_in + 1))
+    return d_out, t_cols
+
+
+def prepare(x, mean=None, transform=None, normalize=True, eps=0.0, device=0, as_tensor=False):
+    """Rows [n, d_in] -> [n, d_out], in this order, each step optional: subtract `mean` [d_in]
+    (`ivector-subtract-global-mean`); apply `transform` [d_out, d_in] or [d_out, d_in + 1] (`transform-vec`); divide by
+    sqrt(sum x^2 + eps) (`ivector-normalize-length`: eps 0, a zero row stays zero; misc/utils.py:317: eps 1e-12)."""
+    n, d_in = _shape2(x, "x")
+    if d_in < 1:
+        raise ValueError("x: rows of dimension 0")
+    d_out, t_cols = d_in, 0
+    if transform is not None:
+        d_out, t_cols = check_transform(d_in, tuple(transform.shape))
+    if mean is not None and tuple(mean.shape) != (d_in,):
+        raise ValueError("mean: shape %s for rows of dimension %d" % (tuple(mean.shape), d_in))
+    if not eps >= 0.0:
+        raise ValueError("eps must be >= 0")
+    torch = _need_device()
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        xd = _rows(x, device, "x")
+        md = None if mean is None else _rows(np.asarray(mean).reshape(1, -1) if not isinstance(mean, torch.Tensor)
+                                             else mean.reshape(1, -1), device, "mean")
+        td = None if transform is None else _rows(transform, device, "transform")
+        out = torch.empty((n, d_out), dtype=torch.float32, device=xd.device)
+        if n:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(lib.xv_score_prepare(device, _p(xd), d_in, n, d_in, None if md is None else _p(md),
+                                            None if td is None else _p(td), t_cols, d_out, t_cols, int(bool(normalize)),
+                                            float(eps), _p(out), d_out, C.c_void_p(stream)))
+        return out if as_tensor else out.cpu().numpy()
+
+
+def cosine_matrix(a, b, device=0, as_tensor=False):
+    """Prepared rows a [n, d], b [m, d] -> [n, m] float32 scores a[i] . b[j] (1 <= d <= 2048)."""
+    (n, d), (m, db) = _shape2(a, "a"), _shape2(b, "b")
+    if d != db:
+        raise ValueError("a and b have different dimensions: %d, %d" % (d, db))
+    torch = _need_device()
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        ad, bd = _rows(a, device, "a"), _rows(b, device, "b")
+        out = torch.empty((n, m), dtype=torch.float32, device=ad.device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        _lib.check(lib.xv_score_matrix(device, _p(ad), d, n, _p(bd), d, m, d, _p(out), max(m, 1), C.c_void_p(stream)))
+        return out if as_tensor else out.cpu().numpy()
+
+
+def cosine_pairs(a, b, ia, ib, device=0, as_tensor=False):
+    """Trial scores a[ia[k]] . b[ib[k]] of prepared rows (`ivector-compute-dot-products`) -> [npairs] float32.
+    An index out of range raises XvError(XV_ERR_INVALID) here, on the host; repeated calls are bit-identical."""
+    (n, d), (m, db) = _shape2(a, "a"), _shape2(b, "b")
+    if d != db:
+        raise ValueError("a and b have different dimensions: %d, %d" % (d, db))
+    ia = np.ascontiguousarray(ia, dtype=np.int64).reshape(-1)
+    ib = np.ascontiguousarray(ib, dtype=np.int64).reshape(-1)
+    if ia.shape != ib.shape:
+        raise ValueError("ia and ib have different lengths")
+    if ia.size and (ia.min() < 0 or ia.max() >= n or ib.min() < 0 or ib.max() >= m):
+        raise _lib.XvError(_lib.XV_ERR_INVALID, "cosine_pairs: a trial index is out of range")
+    torch = _need_device()
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        ad, bd = _rows(a, device, "a"), _rows(b, device, "b")
+        iad = torch.from_numpy(ia.astype(np.int32)).to(ad.device)
+        ibd = torch.from_numpy(ib.astype(np.int32)).to(ad.device)
+        out = torch.empty((ia.size,), dtype=torch.float32, device=ad.device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        _lib.check(lib.xv_score_pairs(device, _p(ad), d, n, _p(bd), d, m, d, _p(iad), _p(ibd), ia.size, _p(out),
+                                      C.c_void_p(stream)))
+        return out if as_tensor else out.cpu().numpy()
+
+
+def _check_nbins(nbins):
+    nbins = int(nbins)
+    if nbins < 256 or nbins > 65536 or nbins & (nbins - 1):
+        raise ValueError("nbins must be a power of two in 256..65536, got %d" % nbins)
+    return nbins
+
+
+def score_histograms(a, labels_a, b=None, labels_b=None, nbins=65536, device=0):
+    """Histograms of the scores of prepared rows, never materialising the score matrix -> (h_same, h_diff), two uint64
+    arrays [nbins]; bin = clamp(floor((s + 1) * nbins / 2), 0, nbins - 1).  With b None: all pairs i < j of a (labels
+    compared within a); otherwise all pairs (i, j) of a x b.  Labels are any array np.unique can sort."""
+    nbins = _check_nbins(nbins)
+    n, d = _shape2(a, "a")
+    self_mode = b is None
+    if self_mode and labels_b is not None:
+        raise ValueError("labels_b without b")
+    la = np.asarray(labels_a).reshape(-1)
+    if la.shape[0] != n:
+        raise ValueError("labels_a: %d labels for %d rows" % (la.shape[0], n))
+    if self_mode:
+        m = n
+        ids = np.unique(la, return_inverse=True)[1].astype(np.int32)
+        ida = idb = ids
+    else:
+        m, db = _shape2(b, "b")
+        if d != db:
+            raise ValueError("a and b have different dimensions: %d, %d" % (d, db))
+        lb = np.asarray(labels_b).reshape(-1)
+        if lb.shape[0] != m:
+            raise ValueError("labels_b: %d labels for %d rows" % (lb.shape[0], m))
+        ids = np.unique(np.concatenate([la, lb]), return_inverse=True)[1].astype(np.int32)
+        ida, idb = ids[:n], ids[n:]
+    torch = _need_device()
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        ad = _rows(a, device, "a")
+        lad = torch.from_numpy(np.ascontiguousarray(ida)).to(ad.device)
+        bd, lbd = (ad, lad) if self_mode else (_rows(b, device, "b"), torch.from_numpy(np.ascontiguousarray(idb)).to(ad.device))
+        hist = torch.zeros((2, nbins), dtype=torch.int64, device=ad.device)      # uint64 counts (torch has no uint64 arithmetic)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        _lib.check(lib.xv_score_histogram(device, _p(ad), d, n, _p(lad), _p(bd), d, m, _p(lbd), d, int(self_mode), nbins,
+                                          C.c_void_p(hist.data_ptr()), C.c_void_p(hist.data_ptr() + 8 * nbins),
+                                          C.c_void_p(stream)))
+        h = hist.cpu().numpy().view(np.uint64)
+    return h[0].copy(), h[1].copy()
+
+
+def eer_from_histograms(h_same, h_diff):
+    """Equal error rate of two score histograms over [-1, 1] (bin k = [e_k, e_k+1), e_k = -1 + 2k / nbins) -> (eer, threshold).
+
+    At a bin edge k (0..nbins) the false-reject rate is FRR(k) = sum(h_same[:k]) / sum(h_same) (same-label mass below the
+    edge) and the false-accept rate is FAR(k) = sum(h_diff[k:]) / sum(h_diff) (different-label mass at or above it).
+    FRR - FAR runs from -1 at k = 0 to +1 at k = nbins without decreasing; the crossing bin is the first k with
+    FRR(k+1) >= FAR(k+1).  Inside it both rates are taken as linear; with g = FRR - FAR and t = -g(k) / (g(k+1) - g(k))
+    the result is eer = FRR(k) + t (FRR(k+1) - FRR(k)) (= the interpolated FAR) at threshold e_k + t (e_k+1 - e_k).
+    Pure numpy in float64 over exact integer counts: deterministic."""
+    hs = np.asarray(h_same).astype(np.uint64).reshape(-1)
+    hd = np.asarray(h_diff).astype(np.uint64).reshape(-1)
+    if hs.shape != hd.shape or hs.size < 1:
+        raise ValueError("histograms of different or zero length")
+    nbins = hs.size
+    cs = np.concatenate([[0], np.cumsum(hs, dtype=np.uint64)])
+    cd = np.concatenate([[0], np.cumsum(hd, dtype=np.uint64)])
+    ns, nd = int(cs[-1]), int(cd[-1])
+    if ns == 0 or nd == 0:
+        raise ValueError("EER needs at least one same-label and one different-label score (%d, %d)" % (ns, nd))
+    frr = cs.astype(np.float64) / ns
+    far = (nd - cd.astype(np.float64)) / nd
+    g = frr - far
+    k = int(np.argmax(g[1:] >= 0.0))
+    t = -g[k] / (g[k + 1] - g[k])
+    w = 2.0 / nbins
+    return float(frr[k] + t * (frr[k + 1] - frr[k])), float(-1.0 + w * (k + t))
+
+
+def select_rows(n, max_num_embeddings):
+    """Row numbers compute_cos_pairwise_eer keeps (misc/utils.py:319-323): all of them, or every (n // max)-th."""
+    if max_num_embeddings is None or n <= max_num_embeddings:
+        return np.arange(n)
+    if max_num_embeddings < 1:
+        raise ValueError("max_num_embeddings must be positive")
+    return np.arange(0, n, n // max_num_embeddings)
+
+
+def pairwise_eer(embeddings, labels, max_num_embeddings=None, nbins=65536, device=0):
+    """compute_cos_pairwise_eer (misc/utils.py:307-346) on the GPU -> (eer, threshold).
+
+    Rows are divided by sqrt(sum x^2 + 1e-12) and every pair i < j is scored; the scores are counted in two histograms of
+    `nbins` bins (score_histograms) and the EER is read from them (eer_from_histograms), so it is exact up to the bin width
+    2 / nbins instead of up to the reference's interp1d / brentq.  There is no need to down-sample; with
+    `max_num_embeddings` set and exceeded the reference's selection range(0, n, n // max_num_embeddings) is applied.
+    Unlike the reference this does not write a `test.txt` into the working directory and does not normalise the
+    caller's `embeddings` in place."""
+    nbins = _check_nbins(nbins)
+    n, _ = _shape2(embeddings, "embeddings")
+    labels = np.asarray(labels).reshape(-1)
+    if labels.shape[0] != n:
+        raise ValueError("labels: %d labels for %d rows" % (labels.shape[0], n))
+    keep = select_rows(n, max_num_embeddings)
+    if len(keep) != n:
+        embeddings, labels = embeddings[keep], labels[keep]
+    x = prepare(embeddings, normalize=True, eps=1e-12, device=device, as_tensor=True)
+    h_same, h_diff = score_histograms(x, labels, nbins=nbins, device=device)
+    return eer_from_histograms(h_same, h_diff)
+
+
+def read_trials(path):
+    """Trial list: lines `key1 key2 [target|nontarget]` -> (keys1, keys2, targets); targets is a bool list, or None when
+    no line has a third column.  Blank lines are skipped; anything else raises ValueError with the line number."""
+    k1, k2, tg = [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            if len(p) not in (2, 3) or (len(p) == 3 and p[2] not in ("target", "nontarget")):
+                raise ValueError("%s:%d: expected `key1 key2 [target|nontarget]`, got %r" % (path, no, line.rstrip("\n")))
+            if tg and (len(p) == 3) != (tg[-1] is not None):
+                raise ValueError("%s:%d: trials with and without a label in one list" % (path, no))
+            k1.append(p[0])
+            k2.append(p[1])
+            tg.append(p[2] == "target" if len(p) == 3 else None)
+    if not tg or tg[0] is None:
+        return k1, k2, None
+    return k1, k2, tg
+
+
+def exact_eer(scores, targets):
+    """EER of a finite trial list, exactly, from the sorted scores (host, float64): with FRR(x) = #{target < x} / #target
+    and FAR(x) = #{nontarget >= x} / #nontarget, the minimum over every threshold x (each distinct score, and one above
+    the largest) of max(FRR(x), FAR(x)).  FRR - FAR does not decrease in x, so this is the value at the crossing."""
+    s = np.asarray(scores, dtype=np.float64)
+    t = np.asarray(targets, dtype=bool)
+    nt, nn = int(t.sum()), int((~t).sum())
+    if nt == 0 or nn == 0:
+        raise ValueError("EER needs target and nontarget trials (%d, %d)" % (nt, nn))
+    xs = np.unique(s)
+    tgt, non = np.sort(s[t]), np.sort(s[~t])
+    frr = np.concatenate([np.searchsorted(tgt, xs, side="left"), [nt]]) / float(nt)
+    far = np.concatenate([nn - np.searchsorted(non, xs, side="left"), [0]]) / float(nn)
+    return float(np.min(np.maximum(frr, far)))

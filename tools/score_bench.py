@@ -1,0 +1,159 @@
+"""Timing of the cosine scoring kernels (csrc/score.hip) on one MI355X, 512-dimensional vectors:
+
+  pairs      0.5 M trials over 145 k rows (xv_score_pairs)            beside torch gather + row-wise dot product
+  matrix     8192 x 8192 scores (xv_score_matrix)                     beside torch.matmul in fp32
+  self-hist  all pairs i < j of n = 16 384, 65 536, 145 000 rows      beside torch.matmul (+ torch.histc on the masked
+             (xv_score_histogram; 65 536 bins = one 64-bit global      result at n = 16 384; matmul alone at 65 536, 17 GB;
+             atomic per score, 8192 bins = counts in LDS)              nothing at 145 000: the matrix would be 84 GB)
+  numpy      the reference-shaped host loop (misc/utils.py:318-327) at n = 1000
+
+Device times are hipEvent times around repeated calls of one entry point (warmed up, at least --seconds of work each); the
+host-side setup of scoring.py (uploads, label coding) is outside them.  Rates: useful FLOP = 2 d per score (the self
+histogram computes n (n - 1) / 2 scores, plus the lower halves of the diagonal tiles, which are not counted); `of_peak` is
+that rate over the 155 TFLOP/s measured fp32-matrix peak.  Prints one JSON line; profiles/scoring.md keeps the numbers."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PEAK_F32_MATRIX = 155e12
+
+
+def timed(torch, fn, seconds, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    iters, total = 0, 0.0
+    while total < seconds * 1e3 and iters < 200:
+        n = max(1, min(50, iters))          # growing batches between two events
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        total += e0.elapsed_time(e1)
+        iters += n
+    return total / iters * 1e-3, iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=0.5, help="least device time per measurement")
+    ap.add_argument("--sizes", type=str, default="16384,65536,145000", help="self-histogram row counts")
+    ap.add_argument("--dim", type=int, default=512)
+    args = ap.parse_args()
+    import torch
+    import __graft_entry__ as g
+    g.build()
+    from tf_kaldi_speaker_amd import _lib, scoring
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench needs a GPU")
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    d = args.dim
+    P = lambda t: C.c_void_p(t.data_ptr())           # noqa: E731
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    out = {"device": torch.cuda.get_device_name(0), "dim": d, "peak_f32_matrix_tflops": PEAK_F32_MATRIX / 1e12}
+
+    def rows(n, speakers):
+        """n prepared rows: speaker centroid + noise, like a validation set -> (rows, int32 labels)."""
+        lab = torch.randint(0, speakers, (n,), device=dev, generator=gen, dtype=torch.int32)
+        cent = torch.randn((speakers, d), device=dev, generator=gen)
+        x = cent[lab.long()] + 2.0 * torch.randn((n, d), device=dev, generator=gen)
+        return scoring.prepare(x, eps=1e-12, as_tensor=True), lab
+
+    # ---- pairs
+    n, k = 145000, 500000
+    x, _ = rows(n, 1251)
+    ia = torch.randint(0, n, (k,), device=dev, generator=gen, dtype=torch.int32)
+    ib = torch.randint(0, n, (k,), device=dev, generator=gen, dtype=torch.int32)
+    sc = torch.empty((k,), device=dev)
+    t, it = timed(torch, lambda: _lib.check(lib.xv_score_pairs(0, P(x), d, n, P(x), d, n, d, P(ia), P(ib), k, P(sc), stream)), args.seconds)
+    ial, ibl = ia.long(), ib.long()
+    tt, _ = timed(torch, lambda: (x[ial] * x[ibl]).sum(1), args.seconds)
+    ref = (x[ial].double() * x[ibl].double()).sum(1)
+    out["pairs"] = {"rows": n, "trials": k, "ms": t * 1e3, "iters": it, "gbytes_per_s": k * 2 * d * 4 / t / 1e9,
+                    "torch_gather_dot_ms": tt * 1e3, "max_abs_err_vs_f64": float((sc.double() - ref).abs().max())}
+    del sc, ref
+
+    # ---- matrix
+    n = 8192
+    a, b = x[:n], x[n:2 * n]
+    m = torch.empty((n, n), device=dev)
+    t, it = timed(torch, lambda: _lib.check(lib.xv_score_matrix(0, P(a), d, n, P(b), d, n, d, P(m), n, stream)), args.seconds)
+    tt, _ = timed(torch, lambda: torch.matmul(a, b.t()), args.seconds)
+    err = float((m - torch.matmul(a.double(), b.double().t()).float()).abs().max())
+    out["matrix"] = {"n": n, "m": n, "ms": t * 1e3, "iters": it, "tflops": 2.0 * n * n * d / t / 1e12,
+                     "of_peak": 2.0 * n * n * d / t / PEAK_F32_MATRIX, "torch_matmul_ms": tt * 1e3,
+                     "torch_matmul_tflops": 2.0 * n * n * d / tt / 1e12, "max_abs_err_vs_f64": err}
+    del m, x
+
+    # ---- self histograms
+    out["self_histogram"] = []
+    for n in [int(s) for s in args.sizes.split(",") if s]:
+        x, lab = rows(n, max(2, n // 116))          # ~116 utterances per speaker (VoxCeleb1-like)
+        pairs = n * (n - 1) // 2
+        row = {"n": n, "pairs": pairs}
+        for nbins, name in ((65536, "global_atomics_65536"), (8192, "lds_8192")):
+            h = torch.zeros((2, nbins), dtype=torch.int64, device=dev)
+
+            def call():
+                _lib.check(lib.xv_score_histogram(0, P(x), d, n, P(lab), P(x), d, n, P(lab), d, 1, nbins, C.c_void_p(h.data_ptr()),
+                                                  C.c_void_p(h.data_ptr() + 8 * nbins), stream))
+            t, it = timed(torch, call, args.seconds, warmup=1)
+            assert int(h.sum().item()) == pairs * (it + 1), "histogram totals"
+            eer, thr = scoring.eer_from_histograms(*h.cpu().numpy().view(np.uint64))
+            row[name] = {"ms": t * 1e3, "iters": it, "tflops": 2.0 * pairs * d / t / 1e12,
+                         "of_peak": 2.0 * pairs * d / t / PEAK_F32_MATRIX, "gscores_per_s": pairs / t / 1e9, "eer": eer}
+        if n <= 65536:
+            tt, _ = timed(torch, lambda: torch.matmul(x, x.t()), args.seconds, warmup=1)
+            row["torch_matmul_full_ms"] = tt * 1e3
+        if n <= 16384:
+            same = lab[:, None] == lab[None, :]
+            upper = torch.ones((n, n), dtype=torch.bool, device=dev).triu(1)
+            ms, md = same & upper, (~same) & upper
+
+            def standin():
+                s = torch.matmul(x, x.t())
+                return torch.histc(s[ms], 65536, -1.0, 1.0), torch.histc(s[md], 65536, -1.0, 1.0)
+            tt, _ = timed(torch, standin, args.seconds, warmup=1)
+            row["torch_matmul_histc_ms"] = tt * 1e3
+            del same, upper, ms, md
+        out["self_histogram"].append(row)
+        del x, lab
+        torch.cuda.empty_cache()
+
+    # ---- the reference-shaped host loop at its own size limit
+    n = 1000
+    rng = np.random.default_rng(0)
+    e = rng.standard_normal((n, d)).astype(np.float32)
+    labels = rng.integers(0, 40, n)
+    t0 = time.perf_counter()
+    e = e / np.sqrt(np.sum(e ** 2, axis=1, keepdims=True) + 1e-12)
+    mat = np.dot(e, e.T)
+    scores, keys, idx = np.zeros(n * (n - 1) // 2), np.zeros(n * (n - 1) // 2), 0
+    for i in range(n - 1):
+        for j in range(i + 1, n):
+            scores[idx] = mat[i, j]
+            keys[idx] = 1 if labels[i] == labels[j] else 0
+            idx += 1
+    t_host = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    scoring.pairwise_eer(e, labels)
+    t_gpu = time.perf_counter() - t0
+    out["n1000"] = {"numpy_double_loop_ms": t_host * 1e3, "pairwise_eer_end_to_end_ms": t_gpu * 1e3}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
