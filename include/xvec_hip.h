@@ -286,6 +286,42 @@ int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, c
                        int64_t ldb, int64_t m, const int32_t* labels_b_dev, int d, int self, int nbins, uint64_t* hist_same_dev,
                        uint64_t* hist_diff_dev, void* stream);
 
+/* ---- PLDA scoring on the GPU (csrc/score.hip): scoring with a trained Kaldi `Plda` (mean, transform, psi), the last line of
+ * every recipe of the reference (`ivector-plda-scoring`, egs/voxceleb/v1/run.sh:410-426, egs/sre/v1/run.sh:415-491).  Kaldi is
+ * absent from the reference tree: these restate plda.cc as published (**parity unpinned**).  Training stays with Kaldi.
+ * With c = n psi / (n psi + 1) and v = 1 + psi / (n psi + 1) the log likelihood ratio of plda.cc is
+ *   s(i, j) = sum_d A_id t_jd + sum_d W_id t_jd^2 + rho_i,  A = e c / v,  W = (1 / (1 + psi) - 1 / v) / 2,
+ *   rho = sum_d [log(1 + psi) - log v] / 2 - sum_d e^2 c^2 / v / 2
+ * (tf_kaldi_speaker_amd.plda builds the per-n tables in float64).  All products are exact fp32 with fp32 accumulation, as in the
+ * cosine entry points; rho / tau are accumulated in double and rounded once.
+ * xv_plda_prepare = `Plda::TransformIvector` (plda.cc) of n rows, and the packed operands of the scoring calls:
+ *   u = T [x; 1] (transform_dev [d, d_in + 1], the last column holding -transform * mean; NULL: x is u already, d_in == d);
+ *   y = u sqrt(d / sum_d u_d^2 inv_d) (norm 1: --normalize-length=true), u sqrt(d) / ||u|| (norm 2:
+ *   --simple-length-normalization=true) or u (norm 0); a zero row stays zero.  tables_dev [num_tables, 4, d] doubles holds per
+ *   distinct n the vectors inv, p, q, w and logdet_dev [num_tables] (or NULL: 0) a constant; table_index_dev [n] picks the
+ *   table of a row (NULL: table 0).  Outputs, each optional: rows_dev [n, ldr] = y; packed_dev [n, ldp] = y p in columns
+ *   0..d-1 and, with pack_second, w (side 0, enrolment) or y^2 (side 1, test) in columns d..2d-1; bias_dev [n] =
+ *   logdet + sum_d q_d y_d^2.  rows_dev == x_dev is allowed without a transform.
+ * xv_plda_matrix = `Plda::LogLikelihoodRatio` over two sets: out[i, j] = a[i] . b[j] + rho[i] + tau[j], a [n, k], b [m, k] packed
+ *   rows (k = d, or 2 d for an enrolment set of mixed n), tau_dev NULL = 0.
+ * xv_plda_pairs = `ivector-plda-scoring` over a trial list: out[t] = a[ia[t]] . b[ib[t]] + rho[ia[t]] + tau[ib[t]]; indices as in
+ *   xv_score_pairs (checked by the caller, never followed out of range: NaN); repeats are bit-identical.
+ * xv_plda_histogram = xv_score_histogram over the PLDA scores of a x b and a caller-given range:
+ *   bin = clamp(floor((s - lo) * nbins / (hi - lo)), 0, nbins - 1), so the end bins also hold what falls outside [lo, hi).
+ * 1 <= k <= 2048 in the last three, 1 <= d, d_in <= 2048 in the first; anything else is XV_ERR_UNSUPPORTED. */
+int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
+                    int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
+                    int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,
+                    float* bias_dev, void* stream);
+int xv_plda_matrix(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const float* b_dev, int64_t ldb,
+                   int64_t m, const float* tau_dev, int k, float* out_dev, int64_t ldo, void* stream);
+int xv_plda_pairs(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const float* b_dev, int64_t ldb,
+                  int64_t m, const float* tau_dev, int k, const int32_t* ia_dev, const int32_t* ib_dev, int64_t npairs,
+                  float* out_dev, void* stream);
+int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const int32_t* labels_a_dev,
+                      const float* b_dev, int64_t ldb, int64_t m, const float* tau_dev, const int32_t* labels_b_dev, int k, double lo,
+                      double hi, int nbins, uint64_t* hist_same_dev, uint64_t* hist_diff_dev, void* stream);
+
 /* ---- host-side ark I/O (csrc/ark_io.cpp; no HIP calls, usable without a GPU) ---------------------
  * Batch counterpart of dataset/kaldi_io.py read_mat_ark (:974-994, records per _read_mat_binary
  * :1014-1031 / _read_compressed_mat :1071-1115) and write_vec_flt (:915-946): the extraction driver

@@ -1,0 +1,400 @@
+"""PLDA scoring on the GPU (csrc/score.hip) through the C ABI via tf_kaldi_speaker_amd.plda, against the float64 oracle
+tests/helpers/ref_plda.py (Kaldi's plda.cc form, not the expansion the GPU evaluates).
+
+The bar of one score.  The GPU evaluates s = sum_k a_ik b_jk + rho_i + tau_j over packed fp32 rows (K = D, or 2 D for an
+enrolment set of mixed n).  With u = 2^-24, the device's own prepared rows (TransformIvector outputs e_i, t_j) read back and
+taken as exact, and the oracle evaluating plda.cc in float64 from them:
+
+    |s_gpu - s_ref| <= (K + 8) u sum_k |a_ik b_jk|  +  4 u (|rho_i| + |tau_j| + |s_ref|)
+
+ * the product is a k-ordered fp32 fma chain of length K (MFMA) or shorter chains joined by a tree (trial lists): at most
+   K u sum|a b| to first order;
+ * the packed operands are roundings of float64 values: a = fl(e c / v) (one rounding, the table is float64 on the device),
+   and with mixed n also fl(W) and fl(t^2): at most 2 u sum|a b| more, inside the 8;
+ * rho and tau are accumulated in double and rounded once: u |rho|, u |tau|;
+ * the two final adds (s + rho) + tau: u |acc + rho| + u |s| <= u (2 |s| + 2 |rho| + |tau|) with acc = s - rho - tau.
+Together 3 u |rho| + 2 u |tau| + 2 u |s| <= 4 u (|rho| + |tau| + |s_ref|).  Derived, not measured; every test prints what
+it measured beside it."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import ref_plda  # noqa: E402
+import ref_score  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+U = 2.0 ** -24
+
+
+@pytest.fixture(scope="module")
+def plda():
+    import __graft_entry__ as g
+    g.build()
+    from tf_kaldi_speaker_amd import plda as p
+    return p
+
+
+def _set(rng, model, speakers, per, scaled=True, noise=1.0):
+    """Rows drawn from the model (ref_plda.draw), each times 2^-6..2^6 when `scaled`, one zero row -> (float32 rows, labels)."""
+    x, labels = ref_plda.draw(rng, model.mean, model.transform, model.psi, speakers, per, noise)
+    if scaled:
+        x = (x - model.mean) * np.exp2(rng.integers(-6, 7, (x.shape[0], 1))) + model.mean
+    x = x.astype(np.float32)
+    return x, labels
+
+
+def _counts(rng, kind, n):
+    return {"n1": None, "n5": np.full(n, 5), "mixed": rng.integers(1, 31, n)}[kind]
+
+
+def _bar(e, t, psi=None):
+    """The bar above for every pair of an (enroll, test) pair of PldaRows, from the device's packed operands."""
+    k = e.k
+    a = np.abs(e.packed.cpu().numpy().astype(np.float64)[:, :k])
+    b = np.abs(t.packed.cpu().numpy().astype(np.float64)[:, :k])
+    rho = np.abs(e.bias.cpu().numpy().astype(np.float64))
+    tau = np.zeros(len(t)) if e.uniform_n is None else np.abs(t.tau(e.uniform_n).cpu().numpy().astype(np.float64))
+    return k, (k + 8) * U * (a @ b.T), 4 * U * (rho[:, None] + tau[None, :])
+
+
+def _oracle(model, e, t):
+    n = np.ones(len(e)) if e.num_utts is None else e.num_utts
+    return ref_plda.llr(model.psi, e.rows.cpu().numpy(), n, t.rows.cpu().numpy())
+
+
+@pytest.mark.parametrize("kind", ["n1", "n5", "mixed"])
+@pytest.mark.parametrize("d,spk_e,spk_t", [(3, 5, 7), (150, 37, 43), (200, 131, 67), (512, 50, 77)])
+def test_scores_of_prepared_rows(plda, d, spk_e, spk_t, kind):
+    """Matrix and trial list against plda.cc in float64 from the device's prepared rows; the bar of the module docstring."""
+    rng = np.random.default_rng(1000 + d)
+    model = plda.Plda(np.zeros(d), *ref_plda.random_model(rng, d)[1:])      # mean 0: a zero row is exactly zero behind the transform
+    xe, _ = _set(rng, model, spk_e, 3)
+    xt, _ = _set(rng, model, spk_t, 3)
+    n, m = xe.shape[0], xt.shape[0]                  # 15 x 21, 111 x 129, 393 x 201, 150 x 231: no multiple of the tile
+    ze, zt = n // 2, m // 3
+    xe[ze], xt[zt] = 0.0, 0.0
+    counts = _counts(rng, kind, n)
+    e = plda.prepare_enroll(model, xe, num_utts=counts)
+    t = plda.prepare_test(model, xt)
+    assert (e.uniform_n is None) == (kind == "mixed") and e.k == (2 * d if kind == "mixed" else d)
+    k, dot_bar, bias_bar = _bar(e, t)
+    want = _oracle(model, e, t)
+    bar = dot_bar + bias_bar + 4 * U * np.abs(want)
+    got = plda.llr_matrix(e, t)
+    assert got.shape == (n, m) and got.dtype == np.float32 and np.all(np.isfinite(got))
+    err = np.abs(got - want)
+    print("matrix D %d %s (K %d): scores %.1f..%.1f, max |error| %.3e, max error / bar %.3f, bar %.2e..%.2e"
+          % (d, kind, k, want.min(), want.max(), err.max(), np.max(err / bar), bar.min(), bar.max()))
+    assert np.all(err <= bar)
+    ia, ib = rng.integers(0, n, 3000), rng.integers(0, m, 3000)
+    ia[:n], ib[:n] = np.arange(n), zt                # the zero test row against every enrolment row
+    ia[n:n + m], ib[n:n + m] = ze, np.arange(m)      # the zero enrolment row against every test row
+    ia[-100:], ib[-100:] = ia[-200:-100], ib[-200:-100]
+    pairs = plda.llr_pairs(e, t, ia, ib)
+    perr = np.abs(pairs - want[ia, ib])
+    print("pairs: max error / bar %.3f, against the matrix / 2 bars %.3f" % (np.max(perr / bar[ia, ib]),
+                                                                               np.max(np.abs(pairs - got[ia, ib]) / (2 * bar[ia, ib]))))
+    assert np.all(np.isfinite(pairs)) and np.all(perr <= bar[ia, ib])
+    assert np.all(np.abs(pairs - got[ia, ib]) <= 2 * bar[ia, ib])
+    assert np.array_equal(pairs[-100:], pairs[-200:-100])
+    assert plda.llr_pairs(e, t, ia, ib).tobytes() == pairs.tobytes()
+    # the zero rows: prepared as zeros, scored finite and within the bar (checked above with every other pair)
+    assert np.all(e.rows.cpu().numpy()[ze] == 0.0) and np.all(t.rows.cpu().numpy()[zt] == 0.0)
+    from tf_kaldi_speaker_amd import _lib
+    with pytest.raises(_lib.XvError) as ex:
+        plda.llr_pairs(e, t, [0, n], [0, 0])
+    assert ex.value.code == _lib.XV_ERR_INVALID
+    with pytest.raises(_lib.XvError):
+        plda.llr_pairs(e, t, [0, 1], [-1, 0])
+
+
+def _f32_prepare(model, x, n, normalize_length, simple):
+    """TransformIvector in plain float32 numpy, the chain the GPU runs: [transform | -transform mean] applied to [x; 1]."""
+    t = model.transform.astype(np.float32)
+    off = (-(model.transform @ model.mean)).astype(np.float32)
+    u = x.astype(np.float32) @ t.T + off[None, :]
+    if not normalize_length:
+        return u
+    inv = np.ones_like(u) if simple else (1.0 / (model.psi[None, :] + 1.0 / np.asarray(n, np.float64).reshape(-1, 1))).astype(np.float32)
+    ss = np.sum(u * u * inv, axis=1, dtype=np.float32)
+    return u * np.where(ss > 0, np.sqrt(np.float32(u.shape[1]) / np.where(ss > 0, ss, np.float32(1))), np.float32(0))[:, None]
+
+
+@pytest.mark.parametrize("case", ["plda_norm", "plda_norm_num_utts", "simple", "simple_num_utts", "none"])
+def test_prepare(plda, case):
+    """TransformIvector.  The matrix-vector product cancels, so no closed bound: the rule of test_gpu_scoring.test_prepare,
+    bar = max(ref_score.delta(D) x the norm of the output row, 4 x the error of the same chain in float32 numpy), per set.
+    rho and tau against float64 sums of the device's rows within 4 u sum|terms|."""
+    rng = np.random.default_rng(77)
+    d = 200
+    model = plda.Plda(*ref_plda.random_model(rng, d))
+    normalize, simple = case != "none", case.startswith("simple")
+    xe, _ = _set(rng, model, 111, 3, scaled=normalize)
+    n = xe.shape[0]
+    counts = rng.integers(1, 31, n) if case.endswith("num_utts") else None
+    nn = np.ones(n) if counts is None else counts
+    e = plda.prepare_enroll(model, xe, num_utts=counts, normalize_length=normalize, simple_length_norm=simple)
+    t = plda.prepare_test(model, xe, normalize_length=normalize, simple_length_norm=simple)
+    for side, rows, cnt in (("enroll", e.rows.cpu().numpy(), nn), ("test", t.rows.cpu().numpy(), np.ones(n))):
+        want = ref_plda.transform_ivector(model.mean, model.transform, model.psi, xe, cnt, normalize, simple)
+        f32 = _f32_prepare(model, xe, cnt, normalize, simple)
+        f32_err = np.max(np.abs(f32 - want))
+        scale = np.linalg.norm(want, axis=1)
+        err = np.abs(rows - want)
+        bar = np.maximum(ref_score.delta(d) * scale, 4 * f32_err)
+        print("prepare %s %s: GPU max |error| %.3e, float32 numpy %.3e, delta x scale %.3e..%.3e"
+              % (case, side, err.max(), f32_err, ref_score.delta(d) * scale[scale > 0].min(), ref_score.delta(d) * scale.max()))
+        assert rows.dtype == np.float32 and np.all(np.isfinite(rows))
+        assert np.all(err.max(axis=1) <= bar)
+    # rho, tau and the packed operands from the device's own rows
+    er, tr = e.rows.cpu().numpy().astype(np.float64), t.rows.cpu().numpy().astype(np.float64)
+    psi = model.psi
+    c = nn[:, None] * psi / (nn[:, None] * psi + 1.0)
+    v = 1.0 + psi / (nn[:, None] * psi + 1.0)
+    logs = 0.5 * (np.log1p(psi)[None, :] - np.log(v))
+    quad = -0.5 * er * er * c * c / v
+    rho = e.bias.cpu().numpy()
+    rho_err = np.abs(rho - (logs.sum(1) + quad.sum(1)))
+    rho_bar = 4 * U * (np.abs(logs).sum(1) + np.abs(quad).sum(1))
+    print("rho: max error / bar %.3f" % np.max(rho_err / rho_bar))
+    assert np.all(rho_err <= rho_bar)
+    a = e.packed.cpu().numpy()[:, :d]
+    assert np.all(np.abs(a - er * c / v) <= U * np.abs(er * c / v) * 1.0001)
+    tp = t.packed.cpu().numpy()
+    assert np.array_equal(tp[:, :d], t.rows.cpu().numpy())
+    assert np.all(np.abs(tp[:, d:2 * d] - tr * tr) <= U * tr * tr * 1.0001)
+    if counts is None:
+        w = 0.5 * (1.0 / (1.0 + psi) - 1.0 / v[0])
+        tau = t.tau(1).cpu().numpy()
+        terms = tr * tr * w[None, :]
+        tau_err, tau_bar = np.abs(tau - terms.sum(1)), 4 * U * np.abs(terms).sum(1)
+        print("tau: max error / bar %.3f" % np.max(tau_err / np.maximum(tau_bar, 1e-300)))
+        assert np.all(tau_err <= tau_bar)
+    else:
+        w = 0.5 * (1.0 / (1.0 + psi)[None, :] - 1.0 / v)
+        assert np.all(np.abs(e.packed.cpu().numpy()[:, d:2 * d] - w) <= U * np.abs(w) * 1.0001)
+
+
+def test_prepare_extreme_rows(plda):
+    """Rows x 2^+-100 neither overflow nor flush: the weighted sum of squares is taken in double."""
+    rng = np.random.default_rng(78)
+    d = 150
+    model = plda.Plda(np.zeros(d), *ref_plda.random_model(rng, d)[1:])       # mean 0: the scaled row is the scaled deviation
+    x, _ = _set(rng, model, 6, 1, scaled=False)
+    x[2] = 0.0
+    x[0] *= np.float32(2.0 ** 100)
+    x[1] *= np.float32(2.0 ** -100)
+    x[3] *= np.float32(2.0 ** 90)
+    for simple in (False, True):
+        e = plda.prepare_enroll(model, x, num_utts=[1, 3, 1, 7, 2, 30], simple_length_norm=simple)
+        t = plda.prepare_test(model, x, simple_length_norm=simple)
+        got = e.rows.cpu().numpy()
+        want = ref_plda.transform_ivector(model.mean, model.transform, model.psi, x, [1, 3, 1, 7, 2, 30], True, simple)
+        f32_err = np.max(np.abs(_f32_prepare(model, x[[4, 5]], [2, 30], True, simple) - want[[4, 5]]))
+        bar = np.maximum(ref_score.delta(d) * np.linalg.norm(want, axis=1), 4 * f32_err)
+        print("extreme rows (simple %s): max |error| %.3e, bar %.3e" % (simple, np.max(np.abs(got - want)), bar.min()))
+        assert np.all(np.isfinite(got)) and np.all(np.isfinite(t.rows.cpu().numpy()))
+        assert np.all(np.max(np.abs(got - want), axis=1) <= bar)
+        assert np.all(got[2] == 0.0) and np.all(t.rows.cpu().numpy()[2] == 0.0)          # a zero row stays zero
+        assert np.all(np.isfinite(plda.llr_matrix(e, t)))
+
+
+def _front(rng, d_in, d):
+    mean = (0.25 * rng.standard_normal(d_in)).astype(np.float32)
+    lda = (rng.standard_normal((d, d_in)) / np.sqrt(d_in)).astype(np.float32)
+    return mean, lda
+
+
+def _end_to_end_oracle(model, mean, lda, xe, xt, counts, ia, ib):
+    fe, ft = ref_score.prepare(xe, mean, lda), ref_score.prepare(xt, mean, lda)
+    n = np.ones(xe.shape[0]) if counts is None else counts
+    e = ref_plda.transform_ivector(model.mean, model.transform, model.psi, fe, n)
+    t = ref_plda.transform_ivector(model.mean, model.transform, model.psi, ft, 1)
+    return ref_plda.llr_pairs(model.psi, e, n, t, ia, ib)
+
+
+def _end_to_end_f32(model, mean, lda, xe, xt, counts, ia, ib):
+    """The whole chain in plain float32 numpy (front, TransformIvector), scored by the oracle from those rows."""
+    def front(x):
+        y = (x.astype(np.float32) - mean[None, :]) @ lda.T
+        return y / np.sqrt(np.sum(y * y, axis=1, dtype=np.float32))[:, None]
+    n = np.ones(xe.shape[0]) if counts is None else counts
+    e = _f32_prepare(model, front(xe), n, True, False)
+    t = _f32_prepare(model, front(xt), np.ones(xt.shape[0]), True, False)
+    return ref_plda.llr_pairs(model.psi, e, n, t, ia, ib)
+
+
+@pytest.mark.parametrize("kind", ["n1", "mixed"])
+def test_end_to_end(plda, kind):
+    """Raw x-vectors [*, 512] through scoring.prepare (mean, LDA to 200, length norm) -> prepare_enroll / prepare_test ->
+    llr_pairs against ref_plda from the same raw inputs.  bar = max(the derived bar of the scores, 4 x the error of the
+    float32 numpy chain), per trial for the first and over the set for the second."""
+    from tf_kaldi_speaker_amd import scoring
+    rng = np.random.default_rng(55)
+    d_in, d = 512, 200
+    mean, lda = _front(rng, d_in, d)
+    # a model that fits length-normalised LDA outputs: rows of norm 1, so a transform of scale sqrt(d)
+    pm, pt, psi = ref_plda.random_model(rng, d)
+    model = plda.Plda(0.02 * pm, pt * np.sqrt(d), psi)
+    xe = (rng.standard_normal((157, d_in)) * np.exp2(rng.integers(-6, 7, (157, 1)))).astype(np.float32)
+    xt = (rng.standard_normal((211, d_in)) * np.exp2(rng.integers(-6, 7, (211, 1)))).astype(np.float32)
+    counts = _counts(rng, kind, 157)
+    ia, ib = rng.integers(0, 157, 4000), rng.integers(0, 211, 4000)
+    front = dict(mean=mean, transform=lda)
+    e = plda.prepare_enroll(model, scoring.prepare(xe, as_tensor=True, **front), num_utts=counts)
+    t = plda.prepare_test(model, scoring.prepare(xt, as_tensor=True, **front))
+    got = plda.llr_pairs(e, t, ia, ib)
+    want = _end_to_end_oracle(model, mean, lda, xe, xt, counts, ia, ib)
+    f32_err = np.max(np.abs(_end_to_end_f32(model, mean, lda, xe, xt, counts, ia, ib) - want))
+    _, dot_bar, bias_bar = _bar(e, t)
+    derived = (dot_bar + bias_bar)[ia, ib] + 4 * U * np.abs(want)
+    err = np.abs(got - want)
+    print("end to end %s: scores %.1f..%.1f, max |error| %.3e, float32 numpy chain %.3e, derived bar %.2e..%.2e"
+          % (kind, want.min(), want.max(), err.max(), f32_err, derived.min(), derived.max()))
+    assert np.all(err <= np.maximum(derived, 4 * f32_err))
+
+
+def _check_bracket(h, oracle_sorted, lo, hi, nbins, delta, what):
+    """tests/test_gpu_scoring._check_bracket over [lo, hi): C(k) = the cumulative count below edge k.  Edge 0 and edge nbins
+    are open ends (the end bins also hold what falls outside): C(0) = 0, C(nbins) = all."""
+    edges = lo + (hi - lo) * np.arange(nbins + 1) / nbins
+    c = np.concatenate([[0], np.cumsum(h.astype(np.int64))])
+    below = np.searchsorted(oracle_sorted, edges - delta, side="left")
+    above = np.searchsorted(oracle_sorted, edges + delta, side="left")
+    below[0] = above[0] = 0
+    below[-1] = above[-1] = oracle_sorted.size
+    exact = np.searchsorted(oracle_sorted, edges, side="left")
+    print("%s, %d bins: %d scores in a neighbouring bin at the worst inner edge" % (what, nbins, np.max(np.abs(c - exact)[1:-1])))
+    assert np.all(below <= c) and np.all(c <= above), what
+
+
+@pytest.mark.parametrize("kind", ["n1", "mixed"])
+@pytest.mark.parametrize("nbins", [8192, 65536])
+def test_histograms(plda, kind, nbins):
+    from tf_kaldi_speaker_amd import scoring
+    rng = np.random.default_rng(91)
+    d = 200
+    model = plda.Plda(*ref_plda.random_model(rng, d))
+    # 60 speakers x 12 utterances, within-speaker noise 8 (oracle EER 0.15 / 0.27 on the CPU); 5 of each enrol, 7 test;
+    # shuffled, so that same-label pairs lie all over the matrix
+    x, labels = _set(rng, model, 60, 12, noise=8.0)
+    perm = rng.permutation(x.shape[0])
+    first = (np.arange(x.shape[0]) % 12) < 5
+    ie, it = perm[first[perm]], perm[~first[perm]]
+    xe, le, xt, lt = x[ie], labels[ie], x[it], labels[it]
+    counts = _counts(rng, kind, xe.shape[0])
+    e, t = plda.prepare_enroll(model, xe, num_utts=counts), plda.prepare_test(model, xt)
+    want = _oracle(model, e, t)
+    _, dot_bar, bias_bar = _bar(e, t)
+    bar_max = float(np.max(dot_bar + bias_bar + 4 * U * np.abs(want)))
+    eq = le[:, None] == lt[None, :]
+    same, diff = want[eq], want[~eq]
+    exact = ref_score.exact_eer(same, diff)
+    lo, hi = float(np.quantile(want, 0.02)), float(np.quantile(want, 0.995))      # some scores fall outside on both sides
+    print("scores %.1f..%.1f, range [%.2f, %.2f), bar_max %.3e, oracle exact EER %.6f" % (want.min(), want.max(), lo, hi, bar_max, exact))
+    assert 0.02 <= exact <= 0.4
+    assert np.sum(want < lo) > 0 and np.sum(want >= hi) > 0
+    hs, hd = plda.llr_histograms(e, le, t, lt, lo=lo, hi=hi, nbins=nbins)
+    assert hs.dtype == np.uint64 and hs.shape == (nbins,) and hd.shape == (nbins,)
+    assert int(hs.sum()) == int(eq.sum()) and int(hd.sum()) == eq.size - int(eq.sum())
+    _check_bracket(hs, np.sort(same), lo, hi, nbins, bar_max, "same-label")
+    _check_bracket(hd, np.sort(diff), lo, hi, nbins, bar_max, "different-label")
+    hs2, hd2 = plda.llr_histograms(e, le, t, lt, lo=lo, hi=hi, nbins=nbins)
+    assert np.array_equal(hs, hs2) and np.array_equal(hd, hd2)
+    # EER from the histograms: the bracket of tests/test_gpu_scoring._check_eer with the bin width of this range
+    eer, thr = scoring.eer_from_histograms(hs, hd, lo, hi)
+    rates = ref_score.StepRates(same, diff)
+    w = (hi - lo) / nbins
+    low = min(rates.frr(thr - w - bar_max), rates.far(thr + w + bar_max))
+    high = max(rates.frr(thr + w + bar_max), rates.far(thr - w - bar_max))
+    print("EER from %d bins: %.6f at %.4f, |eer - exact| %.2e" % (nbins, eer, thr, abs(eer - exact)))
+    assert lo < thr < hi
+    assert low <= eer <= high, (low, eer, high)
+
+
+def test_command_line(plda, repo_root, tmp_path):
+    from tf_kaldi_speaker_amd import kaldi_io, native_ark, scoring
+    rng = np.random.default_rng(8)
+    d_in, d = 512, 200
+    mean, lda = _front(rng, d_in, d)
+    lda_off = np.concatenate([lda, (np.float32(2.0 ** -8) * rng.standard_normal((d, 1))).astype(np.float32)], axis=1)
+    pm, ptm, psi = ref_plda.random_model(rng, d)
+    model = plda.Plda(0.02 * pm, ptm * np.sqrt(d), psi)
+    plda.write_plda(str(tmp_path / "plda"), model)
+    ne, nt = 120, 300
+    ekeys, tkeys = ["spk%03d" % i for i in range(ne)], ["utt%04d" % i for i in range(nt)]
+    cent = rng.standard_normal((ne, d_in))
+    xe = (cent + 0.3 * rng.standard_normal((ne, d_in))).astype(np.float32)
+    owner = rng.integers(0, ne, nt)
+    xt = ((cent[owner] + 1.5 * rng.standard_normal((nt, d_in))) * np.exp2(rng.integers(-6, 7, (nt, 1)))).astype(np.float32)
+    for name, keys, x in (("enroll", ekeys, xe), ("test", tkeys, xt)):
+        w = native_ark.VectorWriter("ark,scp:%s,%s" % (tmp_path / (name + ".ark"), tmp_path / (name + ".scp")))
+        w.write(keys, x)
+        w.close()
+    counts = rng.integers(1, 31, ne)
+    (tmp_path / "num_utts.ark").write_text("".join("%s %d\n" % (k, c) for k, c in list(zip(ekeys, counts))[:-3]))
+    counts[-3:] = 1                                  # three keys without an entry count as 1
+    t2 = rng.integers(0, nt, 2000)
+    t1 = rng.integers(0, ne, 2000)
+    t1[::4] = owner[t2[::4]]
+    lines = [[ekeys[i], tkeys[j], "target" if owner[j] == i else "nontarget"] for i, j in zip(t1, t2)]
+    missing = (3, 500, 777, 1200, 10, 1500, 1999)
+    for pos in missing[:4]:
+        lines[pos][0] = "missing%d" % pos
+    for pos in missing[4:]:
+        lines[pos][1] = "nobody%d" % pos
+    (tmp_path / "trials").write_text("".join(" ".join(p) + "\n" for p in lines))
+    kaldi_io.write_vec_flt(str(tmp_path / "mean.vec"), mean)
+    kaldi_io.write_mat(str(tmp_path / "transform.mat"), lda_off)
+    env = dict(os.environ, PYTHONPATH=repo_root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    base = [sys.executable, "-m", "tf_kaldi_speaker_amd.score_plda", "--gpu", "0"]
+    kept = [p for k, p in enumerate(lines) if k not in missing]
+    erow, trow = {k: i for i, k in enumerate(ekeys)}, {k: i for i, k in enumerate(tkeys)}
+    ia, ib = np.array([erow[p[0]] for p in kept]), np.array([trow[p[1]] for p in kept])
+
+    r = subprocess.run(base + ["--num-utts", "ark:num_utts.ark", "--smoothing", "0.0", "--mean", "mean.vec", "--transform", "transform.mat",
+                               "--eer", "--min-dcf", "0.01", "--min-dcf", "0.001", "plda", "scp:enroll.scp", "ark:test.ark", "trials",
+                               "scores.plda"], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = [ln.split() for ln in (tmp_path / "scores.plda").read_text().splitlines()]
+    assert len(got) == 1993
+    assert [g[:2] for g in got] == [p[:2] for p in kept]
+    assert "skipped 7 of 2000" in r.stderr
+    assert "3 of 120 enrolment keys have no --num-utts entry" in r.stderr
+    scores = np.array([float(g[2]) for g in got])
+    want = _end_to_end_oracle(model, mean, lda_off, xe, xt, counts, ia, ib)
+
+    def front32(x):
+        y = (x.astype(np.float32) - mean[None, :]) @ lda_off[:, :-1].T + lda_off[:, -1][None, :]
+        return y / np.sqrt(np.sum(y * y, axis=1, dtype=np.float32))[:, None]
+    f32 = ref_plda.llr_pairs(model.psi, _f32_prepare(model, front32(xe), counts, True, False), counts,
+                             _f32_prepare(model, front32(xt), np.ones(nt), True, False), ia, ib)
+    f32_err = np.max(np.abs(f32 - want))
+    front = dict(mean=mean, transform=lda_off)
+    e = plda.prepare_enroll(model, scoring.prepare(xe, as_tensor=True, **front), num_utts=counts)
+    t = plda.prepare_test(model, scoring.prepare(xt, as_tensor=True, **front))
+    _, dot_bar, bias_bar = _bar(e, t)
+    derived = (dot_bar + bias_bar)[ia, ib] + 4 * U * np.abs(want)
+    err = np.abs(scores - want)
+    print("command line: scores %.1f..%.1f, max |error| %.3e, float32 numpy chain %.3e, derived bar up to %.2e"
+          % (want.min(), want.max(), err.max(), f32_err, derived.max()))
+    # + the %g rounding: half a unit of the sixth significant digit of the printed score
+    half_digit = 0.5 * 10.0 ** (np.floor(np.log10(np.maximum(np.abs(scores), 1e-300))) - 5)
+    assert np.all(err <= np.maximum(derived, 4 * f32_err) + half_digit)
+    tgt = np.array([p[2] == "target" for p in kept])
+    out = r.stdout.strip().splitlines()
+    print("the tool printed %r" % out)
+    assert out[0] == "EER: %.4g%%" % (100.0 * ref_score.exact_eer(scores[tgt], scores[~tgt]))
+    assert out[1] == "minDCF(p-target=0.01): %.4f" % scoring.min_dcf(scores, tgt, 0.01)[0]
+    assert out[2] == "minDCF(p-target=0.001): %.4f" % scoring.min_dcf(scores, tgt, 0.001)[0]
+    assert abs(scoring.min_dcf(scores, tgt, 0.01)[0] - ref_plda.min_dcf(scores, tgt, 0.01)) < 1e-12
+
+    # nothing matches: non-zero exit status
+    (tmp_path / "none").write_text("x y target\nz w nontarget\n")
+    r = subprocess.run(base + ["plda", "scp:enroll.scp", "scp:test.scp", "none", "none.plda"], env=env, cwd=str(tmp_path),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0

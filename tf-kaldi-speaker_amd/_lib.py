@@ -30,6 +30,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_destroy", "xv_last_error",
            "xv_frontend_cmn_select", "xv_length_normalize", "xv_speaker_mean",
            "xv_score_prepare", "xv_score_matrix", "xv_score_pairs", "xv_score_histogram",
+           "xv_plda_prepare", "xv_plda_matrix", "xv_plda_pairs", "xv_plda_histogram",
            "xv_ark_open", "xv_ark_open_scp", "xv_ark_scp_count", "xv_ark_scp_shapes", "xv_ark_next_batch", "xv_ark_pending_shape", "xv_ark_skipped", "xv_ark_set_copy_threads", "xv_ark_error", "xv_ark_close", "xv_ark_format_vectors", "xv_crc32c", "xv_pack_rows"]
 
 
@@ -112,6 +113,10 @@ def load():
     lib.xv_score_matrix.argtypes = [i32, vp, i64, i64, vp, i64, i64, i32, vp, i64, vp]
     lib.xv_score_pairs.argtypes = [i32, vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp]
     lib.xv_score_histogram.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, vp]
+    lib.xv_plda_prepare.argtypes = [i32, vp, i64, i64, i32, vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp]
+    lib.xv_plda_matrix.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, i64, vp]
+    lib.xv_plda_pairs.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, vp, i64, vp, vp]
+    lib.xv_plda_histogram.argtypes = [i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, vp]
     lib.xv_ark_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
     lib.xv_ark_open_scp.argtypes = [C.c_char_p, C.POINTER(vp)]
     lib.xv_ark_scp_count.argtypes = [vp]

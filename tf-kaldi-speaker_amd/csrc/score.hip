@@ -1,4 +1,4 @@
-// Cosine scoring of x-vectors on the GPU: row preparation, score matrices, trial lists, score histograms.
+// Cosine and PLDA scoring of x-vectors on the GPU: row preparation, score matrices, trial lists, score histograms.
 //
 // The reference scores in two places, both on the host:
 //   egs/voxceleb/v1/run.sh:362-365   ivector-compute-dot-products over length-normalised x-vectors (plain cosine)
@@ -10,6 +10,12 @@
 //
 // All arithmetic is fp32 with exact products and fp32 accumulation, so one error bound ((d + 8) * 2^-24 per score of
 // unit rows) holds for every entry point.
+//
+// PLDA scoring with a trained Kaldi `Plda` (`ivector-plda-scoring`, the last line of every recipe: egs/voxceleb/v1/run.sh:410-426)
+// runs on the same kernels: the log likelihood ratio of plda.cc expands to  s(i, j) = sum_d A_id t_jd + sum_d W_id t_jd^2 + rho_i
+// (tf-kaldi-speaker_amd/plda.py has the algebra), i.e. a product of packed rows plus a row term and a column term added in the
+// epilogue.  plda_rows_kernel normalises the transformed rows and packs the operands; rho / tau are accumulated in double and
+// rounded once.  Training (ivector-compute-lda / -plda, ivector-adapt-plda) stays with Kaldi.  **Parity unpinned** as well.
 //
 //  * row_prepare_kernel: one wave per row; y = x - mean, then y / sqrt(sum y^2 + eps).  The sum of squares is taken of
 //    the row scaled by the power of two of its largest element (exact), so rows of any magnitude neither overflow nor flush.
@@ -24,9 +30,19 @@
 //      EPI_HIST_LDS     same-label / different-label histograms of the scores, uint32 counts in LDS (ds_add_u32) for the
 //                       whole walk of the workgroup, flushed once with 64-bit vector atomics (2 * nbins * 4 bytes <= 64 KB)
 //      EPI_HIST_GLOBAL  the same with one 64-bit vector atomic per score (bin counts that do not fit in LDS)
+//      EPI_PLDA         EPI_MATRIX with row_bias[i] + col_bias[j] added before the store (the biases of the tile sit in LDS)
+//      EPI_PLDA_HIST_LDS / EPI_PLDA_HIST_GLOBAL   the two histogram epilogues over the biased score and a caller-given range
+//                       [lo, hi): bin = clamp(floor((s - lo) * nbins / (hi - lo)), 0, nbins - 1), evaluated in double so that the
+//                       bin edges are exact
 //    Integer adds commute, so the counts are exact and independent of the order of arrival.
 //  * score_pairs_kernel: trial lists.  16 lanes per trial (four trials per wave), 16-byte row loads, four fmaf chains per
 //    lane combined in a fixed order and a DPP butterfly over the 16 lanes: repeats are bit-identical.
+//    The PLDA form adds row_bias[ia[k]] + col_bias[ib[k]].
+//  * plda_rows_kernel: one wave per row, after the affine product of the prepare step (u = transform (x - mean)):
+//    y = u * sqrt(D / sum_d u_d^2 inv_d) (Kaldi's TransformIvector; inv = 1 / (psi + 1 / n), or 1 for the simple form), the sum
+//    in double so that rows of any fp32 magnitude neither overflow nor flush and a zero row stays zero; then the packed operand
+//    y_d p_d (and the second half, W_d on the enrolment side or y_d^2 on the test side, for sets of mixed n) and the bias
+//    logdet + sum_d q_d y_d^2.  The per-n vectors inv, p, q, w come from the host in float64, one table per distinct n.
 #include <mutex>
 
 #include "xv_kernels.h"
@@ -46,7 +62,13 @@ constexpr size_t kOperandBytes = (size_t)4 * STILE_F * sizeof(float);
 constexpr int kScoreLdsBins = 8192;           // largest bin count whose two uint32 histograms stay in LDS (64 KB) beside the operand tiles
 constexpr size_t kLabelBytes = (size_t)(SBM + SBN) * sizeof(int32_t);
 
-enum { EPI_MATRIX = 0, EPI_AFFINE = 1, EPI_HIST_LDS = 2, EPI_HIST_GLOBAL = 3 };
+constexpr size_t kBiasBytes = (size_t)(SBM + SBN) * sizeof(float);
+
+enum { EPI_MATRIX = 0, EPI_AFFINE = 1, EPI_HIST_LDS = 2, EPI_HIST_GLOBAL = 3, EPI_PLDA = 4, EPI_PLDA_HIST_LDS = 5, EPI_PLDA_HIST_GLOBAL = 6 };
+
+constexpr bool epi_hist(int e) { return e == EPI_HIST_LDS || e == EPI_HIST_GLOBAL || e == EPI_PLDA_HIST_LDS || e == EPI_PLDA_HIST_GLOBAL; }
+constexpr bool epi_hist_lds(int e) { return e == EPI_HIST_LDS || e == EPI_PLDA_HIST_LDS; }
+constexpr bool epi_plda(int e) { return e == EPI_PLDA || e == EPI_PLDA_HIST_LDS || e == EPI_PLDA_HIST_GLOBAL; }
 
 __device__ __forceinline__ float dpp_row_sum16(float x) {       // sum over the 16 lanes of a DPP row, in every lane
   x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
@@ -110,6 +132,8 @@ struct ScoreArgs {
   int self, nbins;
   unsigned long long* hs; unsigned long long* hd;
   int nMt, nNt;
+  const float* row_bias; const float* col_bias;   // PLDA epilogues: rho [n], tau [m] (tau may be null: 0)
+  double lo, bin_scale;                           // PLDA histograms: bin = floor((s - lo) * bin_scale)
 };
 
 template <int EPI, bool VEC>
@@ -119,6 +143,9 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
   float* Bs = smem + 2 * STILE_F;      // [2][SBN][SLDT]
   int32_t* lab = reinterpret_cast<int32_t*>(smem + 4 * STILE_F);          // [SBM + SBN] labels of the tile
   unsigned* hist = reinterpret_cast<unsigned*>(lab + SBM + SBN);          // EPI_HIST_LDS: [2][nbins]
+  // PLDA: [SBM + SBN] biases of the tile, behind whatever the epilogue keeps in front of them
+  float* bias = EPI == EPI_PLDA ? smem + 4 * STILE_F
+                                : reinterpret_cast<float*>(hist + (EPI == EPI_PLDA_HIST_LDS ? 2 * p.nbins : 0));
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -128,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
   const int nk = (p.d + SBK - 1) / SBK;
   const float half_bins = 0.5f * (float)p.nbins;
 
-  if (EPI == EPI_HIST_LDS) {
+  if (epi_hist_lds(EPI)) {
     for (int i = tid; i < 2 * p.nbins; i += 256) hist[i] = 0u;
     __syncthreads();
   }
@@ -142,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
     const int64_t tg = t - g * per_group;
     const int nt = (int)(tg / gm);
     const int mt = g * SGROUP + (int)(tg - (int64_t)nt * gm);
-    if ((EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) && p.self && nt < mt) continue;   // strictly below the diagonal (uniform)
+    if (epi_hist(EPI) && p.self && nt < mt) continue;   // strictly below the diagonal (uniform)
     const int m0 = mt * SBM, n0 = nt * SBN;
 
     sf32x4 ra[4], rb[4];
@@ -190,10 +217,18 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    if (EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) {
+    if (epi_hist(EPI) && !epi_plda(EPI)) {
       const int row = tid < SBM ? m0 + tid : n0 + tid - SBM;
       const bool ok = tid < SBM ? row < p.n : row < p.m;
       lab[tid] = ok ? (tid < SBM ? p.la[row] : p.lb[row]) : 0;
+    }
+    if (epi_plda(EPI)) {
+      const bool rowside = __builtin_amdgcn_readfirstlane(tid) < SBM;     // waves 0-1: rows, waves 2-3: columns; the bases stay scalar
+      const float* src = rowside ? p.row_bias : p.col_bias;
+      const int row = rowside ? m0 + tid : n0 + tid - SBM;
+      const bool ok = row < (rowside ? p.n : p.m);
+      bias[tid] = src && ok ? src[row] : 0.f;
+      if (epi_hist(EPI)) lab[tid] = ok ? (rowside ? p.la : p.lb)[row] : 0;
     }
     load_tiles(0);
     store_tiles(0);
@@ -234,7 +269,9 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
       float offs = 0.f;
       int lbj = 0;
       if (EPI == EPI_AFFINE) offs = p.b_offset ? p.B[(int64_t)gj * p.ldb + p.d] : 0.f;
-      if (EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) lbj = lab[SBM + jl];
+      if (epi_hist(EPI)) lbj = lab[SBM + jl];
+      float cb = 0.f;
+      if (epi_plda(EPI)) cb = bias[SBM + jl];
 #pragma unroll
       for (int ai = 0; ai < 2; ++ai)
 #pragma unroll
@@ -242,25 +279,34 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
           const int il = wm * 64 + ai * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
           const int gi = m0 + il;
           if (gi >= p.n) continue;
-          const float s = acc[ai][bi][e];
+          float s = acc[ai][bi][e];
+          if (epi_plda(EPI)) s = (s + bias[il]) + cb;
           if (EPI == EPI_MATRIX || EPI == EPI_AFFINE) {
             p.C[(int64_t)gi * p.ldc + gj] = s + offs;
+          } else if (EPI == EPI_PLDA) {
+            p.C[(int64_t)gi * p.ldc + gj] = s;
           } else {
             if (p.self && gi >= gj) continue;
-            const float fb = fminf(fmaxf(floorf((s + 1.0f) * half_bins), 0.f), (float)(p.nbins - 1));
-            const int bin = (int)fb;
+            int bin;
+            if (epi_plda(EPI)) {      // truncation is floor where it is used; a NaN score lands in bin 0
+              const double fb = ((double)s - p.lo) * p.bin_scale;
+              bin = fb >= (double)p.nbins ? p.nbins - 1 : (fb >= 1.0 ? (int)fb : 0);
+            } else {
+              const float fb = fminf(fmaxf(floorf((s + 1.0f) * half_bins), 0.f), (float)(p.nbins - 1));
+              bin = (int)fb;
+            }
             const bool same = lab[il] == lbj;
-            if (EPI == EPI_HIST_LDS)
+            if (epi_hist_lds(EPI))
               atomicAdd(&hist[(same ? 0 : p.nbins) + bin], 1u);
             else
               atomicAdd((same ? p.hs : p.hd) + bin, 1ull);
           }
         }
     }
-    if (EPI == EPI_HIST_LDS || EPI == EPI_HIST_GLOBAL) __syncthreads();     // the labels are rewritten by the next tile
+    if (epi_hist(EPI) || epi_plda(EPI)) __syncthreads();     // the labels / biases are rewritten by the next tile
   }
 
-  if (EPI == EPI_HIST_LDS) {
+  if (epi_hist_lds(EPI)) {
     __syncthreads();
     for (int i = tid; i < 2 * p.nbins; i += 256) {
       const unsigned c = hist[i];
@@ -304,11 +350,12 @@ hipError_t compute_units(int* cus) {
 }
 
 // ---------------------------------------------------------------------------------------------- pairs
-template <bool VEC>
+template <bool VEC, bool PLDA>
 __global__ __launch_bounds__(256) void score_pairs_kernel(const float* __restrict__ a, int64_t lda, int n,
                                                           const float* __restrict__ b, int64_t ldb, int m, int d,
                                                           const int32_t* __restrict__ ia, const int32_t* __restrict__ ib,
-                                                          int64_t npairs, float* __restrict__ out) {
+                                                          int64_t npairs, float* __restrict__ out,
+                                                          const float* __restrict__ row_bias, const float* __restrict__ col_bias) {
   const int sub = threadIdx.x & 15;
   const int64_t k = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   const bool have = k < npairs;
@@ -334,8 +381,58 @@ __global__ __launch_bounds__(256) void score_pairs_kernel(const float* __restric
       }
     }
   }
-  const float s = dpp_row_sum16((s0 + s1) + (s2 + s3));      // every lane of the wave takes part
+  float s = dpp_row_sum16((s0 + s1) + (s2 + s3));            // every lane of the wave takes part
+  if (PLDA && ok) s = (s + row_bias[i]) + (col_bias ? col_bias[j] : 0.f);
   if (have && sub == 0) out[k] = ok ? s : __builtin_nanf("");  // an index the host let through is marked, never followed
+}
+
+// ---------------------------------------------------------------------------------------------- PLDA rows
+constexpr int PT_INV = 0, PT_P = 1, PT_Q = 2, PT_W = 3;      // components of a per-n table [4][d] (doubles)
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// norm: 0 none, 1 Kaldi's psi-weighted length normalisation (inv table), 2 simple (sqrt(d) / ||u||).
+// side: 0 enrolment (second half of the packed row = W), 1 test (second half = y^2).  Any output may be null; rows == u is allowed.
+__global__ __launch_bounds__(256) void plda_rows_kernel(const float* u, int64_t ldu, int64_t nrows, int d, int norm,
+                                                        int side, int pack_second, const double* __restrict__ tables,
+                                                        const double* __restrict__ logdet, const int32_t* __restrict__ table_index,
+                                                        int num_tables, float* rows, int64_t ldr, float* __restrict__ packed,
+                                                        int64_t ldp, float* __restrict__ bias) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= nrows) return;
+  int k = table_index ? table_index[r] : 0;
+  if (k < 0 || k >= num_tables) k = 0;              // the host checks; never followed out of the tables
+  const double* tab = tables + (int64_t)k * 4 * d;
+  const float* ur = u + r * ldu;
+  double scale = 1.0;
+  if (norm) {
+    double ss = 0.0;
+    for (int c = lane; c < d; c += 64) {
+      const double v = (double)ur[c];
+      ss = fma(v * v, norm == 1 ? tab[PT_INV * d + c] : 1.0, ss);
+    }
+    ss = wave_sum(ss);
+    // a zero row stays zero; a row with inf / nan is passed through
+    scale = ss > 0.0 ? (ss <= 1.7976931348623157e308 ? sqrt((double)d / ss) : 1.0) : (ss == 0.0 ? 0.0 : 1.0);
+  }
+  double acc = 0.0;
+  for (int c = lane; c < d; c += 64) {
+    const float y = (float)((double)ur[c] * scale);
+    const double y2 = (double)y * (double)y;
+    acc = fma(tab[PT_Q * d + c], y2, acc);
+    if (rows) rows[r * ldr + c] = y;
+    if (packed) {
+      packed[r * ldp + c] = (float)((double)y * tab[PT_P * d + c]);
+      if (pack_second) packed[r * ldp + d + c] = side == 0 ? (float)tab[PT_W * d + c] : (float)y2;
+    }
+  }
+  acc = wave_sum(acc);
+  if (bias && lane == 0) bias[r] = (float)((logdet ? logdet[k] : 0.0) + acc);
 }
 
 }  // namespace
@@ -397,10 +494,72 @@ hipError_t launch_score_pairs(const float* a, int64_t lda, int n, const float* b
   if (npairs <= 0) return hipSuccess;
   const bool vec = aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
   const dim3 grid((unsigned)((npairs + 15) / 16));
+  const float* none = nullptr;
   if (vec)
-    hipLaunchKernelGGL(score_pairs_kernel<true>, grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out);
+    hipLaunchKernelGGL((score_pairs_kernel<true, false>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out, none, none);
   else
-    hipLaunchKernelGGL(score_pairs_kernel<false>, grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out);
+    hipLaunchKernelGGL((score_pairs_kernel<false, false>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out, none, none);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- PLDA launches
+hipError_t launch_plda_rows(const float* u, int64_t ldu, int64_t rows, int d, int norm, int side, int pack_second,
+                            const double* tables, const double* logdet, const int32_t* table_index, int num_tables,
+                            float* rows_out, int64_t ldr, float* packed, int64_t ldp, float* bias, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(plda_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, u, ldu, rows, d, norm, side, pack_second,
+                     tables, logdet, table_index, num_tables, rows_out, ldr, packed, ldp, bias);
+  return hipGetLastError();
+}
+
+hipError_t launch_plda_matrix(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
+                              const float* col_bias, int k, float* out, int64_t ldo, hipStream_t s) {
+  if (n <= 0 || m <= 0) return hipSuccess;
+  ScoreArgs p = {};
+  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
+  p.C = out; p.ldc = ldo; p.row_bias = row_bias; p.col_bias = col_bias;
+  tile_counts(p);
+  int cus = 0;
+  hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+  const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
+  return launch_tiles_v<EPI_PLDA>(p, grid, kOperandBytes + kBiasBytes, s);
+}
+
+hipError_t launch_plda_histogram(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
+                                 int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, double lo, double hi,
+                                 int nbins, unsigned long long* hs, unsigned long long* hd, hipStream_t s) {
+  if (n <= 0 || m <= 0) return hipSuccess;
+  ScoreArgs p = {};
+  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
+  p.la = la; p.lb = lb; p.self = 0; p.nbins = nbins; p.hs = hs; p.hd = hd;
+  p.row_bias = row_bias; p.col_bias = col_bias; p.lo = lo; p.bin_scale = (double)nbins / (hi - lo);
+  tile_counts(p);
+  int cus = 0;
+  hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+  const bool in_lds = nbins <= kScoreLdsBins;
+  const size_t smem = kOperandBytes + kLabelBytes + kBiasBytes + (in_lds ? (size_t)2 * nbins * sizeof(unsigned) : 0);
+  const int per_cu = smem * 2 <= 160 * 1024 ? 2 : 1;
+  int64_t grid = (int64_t)cus * per_cu;
+  if (in_lds && (ntiles + grid - 1) / grid > 65536) grid = (ntiles + 65535) / 65536;      // 32-bit LDS counters, as above
+  if (grid > ntiles) grid = ntiles;
+  if (in_lds) return launch_tiles_v<EPI_PLDA_HIST_LDS>(p, (unsigned)grid, smem, s);
+  return launch_tiles_v<EPI_PLDA_HIST_GLOBAL>(p, (unsigned)grid, smem, s);
+}
+
+hipError_t launch_plda_pairs(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
+                             const float* col_bias, int k, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
+                             hipStream_t s) {
+  if (npairs <= 0) return hipSuccess;
+  const bool vec = aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
+  const dim3 grid((unsigned)((npairs + 15) / 16));
+  if (vec)
+    hipLaunchKernelGGL((score_pairs_kernel<true, true>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, k, ia, ib, npairs, out, row_bias, col_bias);
+  else
+    hipLaunchKernelGGL((score_pairs_kernel<false, true>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, k, ia, ib, npairs, out, row_bias, col_bias);
   return hipGetLastError();
 }
 

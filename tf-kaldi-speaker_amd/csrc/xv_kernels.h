@@ -226,6 +226,21 @@ hipError_t launch_score_histogram(const float* a, int64_t lda, int n, const int3
 hipError_t launch_score_pairs(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d, const int32_t* ia,
                               const int32_t* ib, int64_t npairs, float* out, hipStream_t s);
 
+// PLDA scoring (csrc/score.hip; Kaldi's ivector-plda-scoring, egs/voxceleb/v1/run.sh:410-426): the row kernel behind the
+// affine product (normalisation, packed operands, bias), and the PLDA forms of the three scoring launches, which add
+// row_bias[i] + col_bias[j] (col_bias may be null) to the product of the packed rows; k = d or 2 d, 1 <= k <= 2048
+hipError_t launch_plda_rows(const float* u, int64_t ldu, int64_t rows, int d, int norm, int side, int pack_second,
+                            const double* tables, const double* logdet, const int32_t* table_index, int num_tables,
+                            float* rows_out, int64_t ldr, float* packed, int64_t ldp, float* bias, hipStream_t s);
+hipError_t launch_plda_matrix(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
+                              const float* col_bias, int k, float* out, int64_t ldo, hipStream_t s);
+hipError_t launch_plda_histogram(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
+                                 int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, double lo, double hi,
+                                 int nbins, unsigned long long* hs, unsigned long long* hd, hipStream_t s);
+hipError_t launch_plda_pairs(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
+                             const float* col_bias, int k, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
+                             hipStream_t s);
+
 // attention scores (model/pooling.py:189-194): score[r, h] = scale * sum_d key[r, h*dk_h + d] * q[h, d]
 // (split_key) or sum_d key[r, d] * q[h, d] (no split; dk_h == dk).
 hipError_t launch_att_scores(const float* key, int64_t ldk, int64_t rows, const float* query, int H,

@@ -2221,6 +2221,96 @@ int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, c
   return XV_OK;
 }
 
+int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
+                    int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
+                    int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,
+                    float* bias_dev, void* stream) {
+  if (!x_dev || !tables_dev) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: null pointer");
+  if (d < 1 || d > 2048 || d_in < 1 || d_in > 2048)
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_plda_prepare: 1 <= d, d_in <= 2048, got %d, %d", d, d_in);
+  if (n < 0 || n > INT32_MAX || ldx < d_in || num_tables < 1 || norm < 0 || norm > 2 || side < 0 || side > 1)
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: bad dimensions");
+  if (rows_dev && ldr < d) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: bad dimensions");
+  if (packed_dev && (ldp < (pack_second ? 2 * (int64_t)d : d) || packed_dev == x_dev || packed_dev == rows_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: packed rows of dimension %d need a buffer of their own with ldp >= %d", d,
+                pack_second ? 2 * d : d);
+  if (transform_dev) {
+    if (ldt < d_in + 1) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: the transform is [d, d_in + 1] (last column: offset)");
+    if (!rows_dev || rows_dev == x_dev) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: a transform needs rows_dev, not in place");
+  } else if (d_in != d) {
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: d_in != d without a transform");
+  }
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipSuccess;
+  const float* u = x_dev;
+  int64_t ldu = ldx;
+  if (transform_dev) {
+    e = launch_score_matrix(x_dev, ldx, (int)n, transform_dev, ldt, d, d_in, nullptr, 1, rows_dev, ldr, s);
+    u = rows_dev;
+    ldu = ldr;
+  }
+  if (e == hipSuccess)
+    e = launch_plda_rows(u, ldu, n, d, norm, side, pack_second ? 1 : 0, tables_dev, logdet_dev, table_index_dev, num_tables, rows_dev,
+                         ldr, packed_dev, ldp, bias_dev, s);
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "plda_prepare launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+// shared argument check of the three PLDA scoring entry points: packed rows a [n, k], b [m, k], rho [n], tau [m] or null
+static int plda_operands(const char* who, const float* a, int64_t lda, int64_t n, const float* rho, const float* b, int64_t ldb,
+                         int64_t m, int k) {
+  if (const int rc = score_operands(who, a, lda, n, b, ldb, m, k)) return rc;
+  if (!rho) return fail(nullptr, XV_ERR_INVALID, "%s: null pointer", who);
+  return XV_OK;
+}
+
+int xv_plda_matrix(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const float* b_dev, int64_t ldb,
+                   int64_t m, const float* tau_dev, int k, float* out_dev, int64_t ldo, void* stream) {
+  if (const int rc = plda_operands("xv_plda_matrix", a_dev, lda, n, rho_dev, b_dev, ldb, m, k)) return rc;
+  if (!out_dev || ldo < m) return fail(nullptr, XV_ERR_INVALID, "xv_plda_matrix: bad output");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_plda_matrix(a_dev, lda, (int)n, rho_dev, b_dev, ldb, (int)m, tau_dev, k, out_dev, ldo,
+                                          static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "plda_matrix launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_plda_pairs(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const float* b_dev, int64_t ldb,
+                  int64_t m, const float* tau_dev, int k, const int32_t* ia_dev, const int32_t* ib_dev, int64_t npairs,
+                  float* out_dev, void* stream) {
+  if (const int rc = plda_operands("xv_plda_pairs", a_dev, lda, n, rho_dev, b_dev, ldb, m, k)) return rc;
+  if (npairs < 0 || npairs > ((int64_t)1 << 34)) return fail(nullptr, XV_ERR_INVALID, "xv_plda_pairs: bad pair count");
+  if (npairs > 0 && (!ia_dev || !ib_dev || !out_dev)) return fail(nullptr, XV_ERR_INVALID, "xv_plda_pairs: null pointer");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_plda_pairs(a_dev, lda, (int)n, rho_dev, b_dev, ldb, (int)m, tau_dev, k, ia_dev, ib_dev, npairs, out_dev,
+                                         static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "plda_pairs launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const int32_t* labels_a_dev,
+                      const float* b_dev, int64_t ldb, int64_t m, const float* tau_dev, const int32_t* labels_b_dev, int k, double lo,
+                      double hi, int nbins, uint64_t* hist_same_dev, uint64_t* hist_diff_dev, void* stream) {
+  if (const int rc = plda_operands("xv_plda_histogram", a_dev, lda, n, rho_dev, b_dev, ldb, m, k)) return rc;
+  if (nbins < 256 || nbins > 65536 || (nbins & (nbins - 1)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: nbins is a power of two in 256..65536, got %d", nbins);
+  if (!(lo < hi) || !(hi - lo <= 1.7976931348623157e308))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: the range [lo, hi) is empty or not finite");
+  if (!labels_a_dev || !labels_b_dev || !hist_same_dev || !hist_diff_dev || hist_same_dev == hist_diff_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: null pointer");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_plda_histogram(a_dev, lda, (int)n, rho_dev, labels_a_dev, b_dev, ldb, (int)m, tau_dev, labels_b_dev, k, lo,
+                                             hi, nbins, reinterpret_cast<unsigned long long*>(hist_same_dev),
+                                             reinterpret_cast<unsigned long long*>(hist_diff_dev), static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "plda_histogram launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 void xv_destroy(xv_handle* h) {
   if (!h) return;
   {

@@ -243,6 +243,33 @@ def write_vec_flt(file_or_fd, v, key=''):
             fd.close()
 
 
+def vec_payload(v):
+    """Bytes of a binary Kaldi vector from its type tag on ('FV ' | 'DV ', \4 <i32 dim>, payload): what follows the
+    '\0B' flag of a stand-alone vector and what an object file (e.g. a `Plda`) holds between its tokens."""
+    v = np.asarray(v)
+    if v.ndim != 1 or v.dtype not in (np.float32, np.float64):
+        raise UnsupportedDataType("vector of shape %s, type '%s'" % (v.shape, v.dtype))
+    tag = b'FV ' if v.dtype == np.float32 else b'DV '
+    return tag + b'\x04' + struct.pack('<i', v.shape[0]) + np.ascontiguousarray(v).astype(v.dtype.newbyteorder('<'), copy=False).tobytes()
+
+
+def mat_payload(m):
+    """Bytes of a binary Kaldi matrix from its type tag on ('FM ' | 'DM ', \4 <i32 rows> \4 <i32 cols>, row-major payload)."""
+    m = np.asarray(m)
+    if m.ndim != 2 or m.dtype not in (np.float32, np.float64):
+        raise UnsupportedDataType("matrix of shape %s, type '%s'" % (m.shape, m.dtype))
+    tag = b'FM ' if m.dtype == np.float32 else b'DM '
+    return (tag + b'\x04' + struct.pack('<i', m.shape[0]) + b'\x04' + struct.pack('<i', m.shape[1])
+            + np.ascontiguousarray(m).astype(m.dtype.newbyteorder('<'), copy=False).tobytes())
+
+
+def expect_token(s, token):
+    """Consume `token` and the space behind it from a _Stream (Kaldi's ExpectToken in binary mode); BadInputFormat otherwise."""
+    got = s.read_token()
+    if got != token.encode("latin1"):
+        raise BadInputFormat("expected token %s, got %r" % (token, got[:40].decode("latin1")))
+
+
 # ----------------------------------------------------------------------------- matrices
 _U16 = 1.52590218966964e-05      # 1/65535, the constant the reference uses (:1083)
 

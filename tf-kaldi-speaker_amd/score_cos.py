@@ -10,7 +10,7 @@ are `key1 key2 score` in trial order, as ivector-compute-dot-products writes the
 its table is skipped and counted (reported on stderr); the exit status is non-zero only if no trial was scored.  That is
 Kaldi's behaviour as published; Kaldi is absent from the reference tree, so this is **parity unpinned**.  `--eer` needs
 the third column and prints `EER: x%`, the exact EER of the scores as written (from the sorted scores, on the host,
-what `compute-eer` would be given).  PLDA scoring stays with Kaldi."""
+what `compute-eer` would be given).  PLDA scoring is score_plda.py, which shares the helpers below."""
 import argparse
 import sys
 
@@ -41,6 +41,28 @@ def _table(rspecifier, mean, transform, normalize, device):
     return {k: i for i, k in enumerate(keys)}, rows
 
 
+def select_trials(tool, keys1, keys2, row1, row2):
+    """Numbers of the trials whose keys are both in their tables (the others are skipped and counted on stderr), or None
+    when there is none."""
+    kept = [t for t in range(len(keys1)) if keys1[t] in row1 and keys2[t] in row2]
+    skipped = len(keys1) - len(kept)
+    if skipped:
+        sys.stderr.write("%s: skipped %d of %d trials (key not in its table)\n" % (tool, skipped, len(keys1)))
+    if not kept:
+        sys.stderr.write("%s: no trial was scored\n" % tool)
+        return None
+    return kept
+
+
+def write_scores(tool, path, keys1, keys2, kept, scores):
+    """Lines `key1 key2 score` (%g) in trial order to `path` ('-': stdout) -> the scores as printed."""
+    text = ["%g" % s for s in scores]
+    with (sys.stdout if path == "-" else open(path, "w")) as f:
+        f.write("".join("%s %s %s\n" % (keys1[t], keys2[t], s) for t, s in zip(kept, text)))
+    sys.stderr.write("%s: scored %d trials\n" % (tool, len(kept)))
+    return [float(s) for s in text]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="score_cos", description=__doc__.split("\n\n")[0])
     ap.add_argument("-g", "--gpu", type=int, default=0, help="HIP device")
@@ -63,22 +85,15 @@ def main(argv=None):
     row1, x1 = _table(args.rspecifier1, mean, transform, args.normalize, args.gpu)
     row2, x2 = (row1, x1) if args.rspecifier2 == args.rspecifier1 else _table(args.rspecifier2, mean, transform,
                                                                              args.normalize, args.gpu)
-    kept = [t for t in range(len(keys1)) if keys1[t] in row1 and keys2[t] in row2]
-    skipped = len(keys1) - len(kept)
-    if skipped:
-        sys.stderr.write("score_cos: skipped %d of %d trials (key not in its table)\n" % (skipped, len(keys1)))
-    if not kept:
-        sys.stderr.write("score_cos: no trial was scored\n")
+    kept = select_trials("score_cos", keys1, keys2, row1, row2)
+    if kept is None:
         return 1
     ia = np.fromiter((row1[keys1[t]] for t in kept), dtype=np.int64, count=len(kept))
     ib = np.fromiter((row2[keys2[t]] for t in kept), dtype=np.int64, count=len(kept))
     scores = scoring.cosine_pairs(x1, x2, ia, ib, device=args.gpu)
-    text = ["%g" % s for s in scores]
-    with (sys.stdout if args.scores_out == "-" else open(args.scores_out, "w")) as f:
-        f.write("".join("%s %s %s\n" % (keys1[t], keys2[t], s) for t, s in zip(kept, text)))
-    sys.stderr.write("score_cos: scored %d trials\n" % len(kept))
+    printed = write_scores("score_cos", args.scores_out, keys1, keys2, kept, scores)
     if args.eer:
-        eer = scoring.exact_eer([float(s) for s in text], [targets[t] for t in kept])
+        eer = scoring.exact_eer(printed, [targets[t] for t in kept])
         print("EER: %.4g%%" % (100.0 * eer))
     return 0
 

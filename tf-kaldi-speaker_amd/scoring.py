@@ -2,12 +2,13 @@
 xv_score_pairs / xv_score_histogram): what the reference does with Kaldi binaries in its cosine back-end
 (egs/voxceleb/v1/run.sh:362-365 plain cosine, :404-408 mean-subtract + transform-vec + length-norm +
 ivector-compute-dot-products) and with a numpy double loop in its model-selection metric (compute_cos_pairwise_eer,
-misc/utils.py:307-346).  PLDA stays with Kaldi.
+misc/utils.py:307-346).  PLDA scoring with a trained model is in plda.py, on the same kernels; PLDA / LDA training stays
+with Kaldi.
 
 Everything is fp32 with exact products: a score of two prepared rows of length d is within (d + 8) * 2^-24 of the exact
 value.  Arrays go in and come out as numpy; a float32 torch tensor that already lives on the device is taken as it is,
 and `as_tensor=True` keeps a result there.  No CPU path: without a HIP device every function here except
-eer_from_histograms and read_trials raises RuntimeError."""
+eer_from_histograms, exact_eer, min_dcf and read_trials raises RuntimeError."""
 import ctypes as C
 
 import numpy as np
@@ -174,8 +175,9 @@ def score_histograms(a, labels_a, b=None, labels_b=None, nbins=65536, device=0):
     return h[0].copy(), h[1].copy()
 
 
-def eer_from_histograms(h_same, h_diff):
-    """Equal error rate of two score histograms over [-1, 1] (bin k = [e_k, e_k+1), e_k = -1 + 2k / nbins) -> (eer, threshold).
+def eer_from_histograms(h_same, h_diff, lo=-1.0, hi=1.0):
+    """Equal error rate of two score histograms over [lo, hi), by default the cosine range [-1, 1] (bin k = [e_k, e_k+1),
+    e_k = lo + (hi - lo) k / nbins; the end bins of plda.llr_histograms also hold what falls outside) -> (eer, threshold).
 
     At a bin edge k (0..nbins) the false-reject rate is FRR(k) = sum(h_same[:k]) / sum(h_same) (same-label mass below the
     edge) and the false-accept rate is FAR(k) = sum(h_diff[k:]) / sum(h_diff) (different-label mass at or above it).
@@ -198,8 +200,11 @@ def eer_from_histograms(h_same, h_diff):
     g = frr - far
     k = int(np.argmax(g[1:] >= 0.0))
     t = -g[k] / (g[k + 1] - g[k])
-    w = 2.0 / nbins
-    return float(frr[k] + t * (frr[k + 1] - frr[k])), float(-1.0 + w * (k + t))
+    lo, hi = float(lo), float(hi)
+    if not lo < hi:
+        raise ValueError("empty score range [%r, %r)" % (lo, hi))
+    w = (hi - lo) / nbins
+    return float(frr[k] + t * (frr[k + 1] - frr[k])), float(lo + w * (k + t))
 
 
 def select_rows(n, max_num_embeddings):
@@ -268,3 +273,29 @@ def exact_eer(scores, targets):
     frr = np.concatenate([np.searchsorted(tgt, xs, side="left"), [nt]]) / float(nt)
     far = np.concatenate([nn - np.searchsorted(non, xs, side="left"), [0]]) / float(nn)
     return float(np.min(np.maximum(frr, far)))
+
+
+def min_dcf(scores, targets, p_target=0.01, c_miss=1.0, c_fa=1.0):
+    """Minimum normalised detection cost of a finite trial list (host, float64), the statement of Kaldi's
+    sid/compute_min_dcf.py (egs/voxceleb/v1/run.sh:418-421: --p-target 0.01 and 0.001) -> (minDCF, threshold).
+
+    With P_miss(x) = #{target < x} / #target and P_fa(x) = #{nontarget >= x} / #nontarget (the rates of exact_eer), the
+    minimum over every threshold x (each distinct score, and one above the largest: reported as +inf) of
+    c_miss P_miss(x) p_target + c_fa P_fa(x) (1 - p_target), divided by min(c_miss p_target, c_fa (1 - p_target)), the cost
+    of the better of the two constant decisions.  Of equal minima the lowest threshold is returned."""
+    s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    t = np.asarray(targets, dtype=bool).reshape(-1)
+    if s.shape != t.shape:
+        raise ValueError("scores and targets have different lengths")
+    if not (0.0 < p_target < 1.0) or not c_miss > 0.0 or not c_fa > 0.0:
+        raise ValueError("min_dcf needs 0 < p_target < 1 and positive costs, got %r, %r, %r" % (p_target, c_miss, c_fa))
+    nt, nn = int(t.sum()), int((~t).sum())
+    if nt == 0 or nn == 0:
+        raise ValueError("minDCF needs target and nontarget trials (%d, %d)" % (nt, nn))
+    xs = np.unique(s)
+    tgt, non = np.sort(s[t]), np.sort(s[~t])
+    p_miss = np.concatenate([np.searchsorted(tgt, xs, side="left"), [nt]]) / float(nt)
+    p_fa = np.concatenate([nn - np.searchsorted(non, xs, side="left"), [0]]) / float(nn)
+    cost = c_miss * p_miss * p_target + c_fa * p_fa * (1.0 - p_target)
+    k = int(np.argmin(cost))
+    return float(cost[k] / min(c_miss * p_target, c_fa * (1.0 - p_target))), float(xs[k]) if k < xs.size else float("inf")

@@ -7,6 +7,9 @@
              atomic per score, 8192 bins = counts in LDS)              nothing at 145 000: the matrix would be 84 GB)
   numpy      the reference-shaped host loop (misc/utils.py:318-327) at n = 1000
 
+  --plda     instead of the above: the PLDA entry points (xv_plda_matrix / _pairs / _histogram / _prepare) beside the cosine
+             entry point of the same (n, m, K), D = 200 and 512, enrolment sets of uniform and of mixed num_utts
+
 Device times are hipEvent times around repeated calls of one entry point (warmed up, at least --seconds of work each); the
 host-side setup of scoring.py (uploads, label coding) is outside them.  Rates: useful FLOP = 2 d per score (the self
 histogram computes n (n - 1) / 2 scores, plus the lower halves of the diagonal tiles, which are not counted); `of_peak` is
@@ -43,11 +46,77 @@ def timed(torch, fn, seconds, warmup=2):
     return total / iters * 1e-3, iters
 
 
+def plda_leg(args, torch, lib, _lib, scoring):
+    """xv_plda_* beside the cosine twin of the same (n, m, K), in one process, the two alternating case by case."""
+    from tf_kaldi_speaker_amd import plda
+    dev = torch.device("cuda:0")
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    P = lambda t: C.c_void_p(t.data_ptr())           # noqa: E731
+    rng = np.random.default_rng(3)
+    n, m, k_pairs, nbins = args.plda_rows, args.plda_rows, 500000, 8192
+    out = {"device": torch.cuda.get_device_name(0), "n": n, "m": m, "trials": k_pairs, "nbins": nbins, "cases": []}
+    for d in (200, 512):
+        q, _ = np.linalg.qr(rng.standard_normal((d, d)))
+        psi = np.sort(np.exp(rng.uniform(np.log(1e-3), np.log(1e2), d)))[::-1].copy()
+        model = plda.Plda(0.1 * rng.standard_normal(d), q, psi)
+        spk = rng.integers(0, max(2, n // 116), n + m)
+        cent = rng.standard_normal((max(2, n // 116), d)) * np.sqrt(psi)[None, :]
+        x = (cent[spk] + rng.standard_normal((n + m, d))).astype(np.float32) @ q.astype(np.float32) + model.mean.astype(np.float32)
+        xd = torch.from_numpy(x).to(dev)
+        lab = torch.from_numpy(spk.astype(np.int32)).to(dev)
+        ia = torch.from_numpy(rng.integers(0, n, k_pairs).astype(np.int32)).to(dev)
+        ib = torch.from_numpy(rng.integers(0, m, k_pairs).astype(np.int32)).to(dev)
+        for kind in ("uniform", "mixed"):
+            counts = None if kind == "uniform" else rng.integers(1, 31, n)
+            e = plda.prepare_enroll(model, xd[:n], num_utts=counts)
+            t = plda.prepare_test(model, xd[n:])
+            k = e.k
+            tau = t.tau(e.uniform_n) if e.uniform_n is not None else None
+            ptau = None if tau is None else P(tau)
+            lda, ldb = e.packed.shape[1], t.packed.shape[1]
+            # the cosine twin: prepared (unit) rows of length K with the same leading dimensions
+            ca = scoring.prepare(torch.randn((n, lda), device=dev)[:, :k].contiguous(), as_tensor=True)
+            cb = scoring.prepare(torch.randn((m, ldb), device=dev)[:, :k].contiguous(), as_tensor=True)
+            mat = torch.empty((n, m), device=dev)
+            sc = torch.empty((k_pairs,), device=dev)
+            h = torch.zeros((2, nbins), dtype=torch.int64, device=dev)
+            hs, hd = C.c_void_p(h.data_ptr()), C.c_void_p(h.data_ptr() + 8 * nbins)
+            s_all = plda.llr_matrix(e, t, as_tensor=True)
+            lo, hi = float(s_all.min()), float(s_all.max()) + 1.0
+            del s_all
+            row = {"d": d, "num_utts": kind, "k": k}
+            calls = {
+                "matrix": (lambda: lib.xv_plda_matrix(0, P(e.packed), lda, n, P(e.bias), P(t.packed), ldb, m, ptau, k, P(mat), m, stream),
+                           lambda: lib.xv_score_matrix(0, P(ca), k, n, P(cb), k, m, k, P(mat), m, stream)),
+                "pairs": (lambda: lib.xv_plda_pairs(0, P(e.packed), lda, n, P(e.bias), P(t.packed), ldb, m, ptau, k, P(ia), P(ib), k_pairs, P(sc), stream),
+                          lambda: lib.xv_score_pairs(0, P(ca), k, n, P(cb), k, m, k, P(ia), P(ib), k_pairs, P(sc), stream)),
+                "histogram": (lambda: lib.xv_plda_histogram(0, P(e.packed), lda, n, P(e.bias), P(lab[:n]), P(t.packed), ldb, m, ptau, P(lab[n:]), k,
+                                                            lo, hi, nbins, hs, hd, stream),
+                              lambda: lib.xv_score_histogram(0, P(ca), k, n, P(lab[:n]), P(cb), k, m, P(lab[n:]), k, 0, nbins, hs, hd, stream)),
+            }
+            for name, (f_plda, f_cos) in calls.items():
+                tp, it = timed(torch, lambda: _lib.check(f_plda()), args.seconds)
+                tc, _ = timed(torch, lambda: _lib.check(f_cos()), args.seconds)
+                tp2, _ = timed(torch, lambda: _lib.check(f_plda()), args.seconds)       # once more: the spread of one box
+                row[name] = {"plda_ms": tp * 1e3, "plda_again_ms": tp2 * 1e3, "cosine_ms": tc * 1e3, "ratio": min(tp, tp2) / tc, "iters": it}
+            # prepare: affine product + row kernel, beside xv_score_prepare with the same [d, d + 1] transform and length norm
+            aff = plda._affine(model, 0, torch)
+            tp, _ = timed(torch, lambda: plda.prepare_test(model, xd[n:]), args.seconds)
+            tc, _ = timed(torch, lambda: scoring.prepare(xd[n:], transform=aff, as_tensor=True), args.seconds)
+            row["prepare_python"] = {"plda_ms": tp * 1e3, "cosine_ms": tc * 1e3, "ratio": tp / tc, "rows": m}
+            out["cases"].append(row)
+            del e, t, ca, cb, mat, sc, h
+            torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=0.5, help="least device time per measurement")
     ap.add_argument("--sizes", type=str, default="16384,65536,145000", help="self-histogram row counts")
     ap.add_argument("--dim", type=int, default=512)
+    ap.add_argument("--plda", action="store_true", help="time the PLDA entry points beside their cosine twins instead")
+    ap.add_argument("--plda-rows", type=int, default=8192, help="rows on either side of the PLDA leg")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as g
@@ -56,6 +125,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("score_bench needs a GPU")
     lib = _lib.load()
+    if args.plda:
+        return plda_leg(args, torch, lib, _lib, scoring)
     dev = torch.device("cuda:0")
     stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
     d = args.dim
