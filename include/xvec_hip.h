@@ -288,7 +288,7 @@ int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, c
 
 /* ---- PLDA scoring on the GPU (csrc/score.hip): scoring with a trained Kaldi `Plda` (mean, transform, psi), the last line of
  * every recipe of the reference (`ivector-plda-scoring`, egs/voxceleb/v1/run.sh:410-426, egs/sre/v1/run.sh:415-491).  Kaldi is
- * absent from the reference tree: these restate plda.cc as published (**parity unpinned**).  Training stays with Kaldi.
+ * absent from the reference tree: these restate plda.cc as published (**parity unpinned**).  Training is the next block (csrc/backend.hip).
  * With c = n psi / (n psi + 1) and v = 1 + psi / (n psi + 1) the log likelihood ratio of plda.cc is
  *   s(i, j) = sum_d A_id t_jd + sum_d W_id t_jd^2 + rho_i,  A = e c / v,  W = (1 / (1 + psi) - 1 / v) / 2,
  *   rho = sum_d [log(1 + psi) - log v] / 2 - sum_d e^2 c^2 / v / 2
@@ -321,6 +321,30 @@ int xv_plda_pairs(int device, const float* a_dev, int64_t lda, int64_t n, const 
 int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const int32_t* labels_a_dev,
                       const float* b_dev, int64_t ldb, int64_t m, const float* tau_dev, const int32_t* labels_b_dev, int k, double lo,
                       double hi, int nbins, uint64_t* hist_same_dev, uint64_t* hist_diff_dev, void* stream);
+
+/* ---- back-end training statistics on the GPU (csrc/backend.hip): the sums behind `ivector-mean`, `ivector-compute-lda` and
+ * `ivector-compute-plda` (egs/voxceleb/v1/run.sh:384-400, egs/sre/v1/run.sh:399-411); the d x d linear algebra behind them is
+ * host float64 (tf_kaldi_speaker_amd.backend).  Kaldi is absent from the reference tree: **parity unpinned**.
+ * xv_gram_f64 = G = sum_r w_r (x_r - c)(x_r - c)^T: x_dev [n, ldx] float32, c_dev [d] double or NULL (0), w_dev [n] double or
+ *   NULL (1), g_dev [d, d] double, both triangles written, G == G^T bitwise.  x - c is evaluated in double (one rounding), w is
+ *   applied to one operand, products and sums are double (v_mfma_f64_16x16x4_f64): with y = x - c in double,
+ *   |G - sum_r w_r y_ri y_rj| <= (n + 16) 2^-53 sum_r |w_r y_ri y_rj|.  No floating-point atomics: repeated calls are
+ *   bit-identical.  n = 0 writes zeros.  1 <= d <= 2048 (XV_ERR_UNSUPPORTED otherwise); ws_dev is a scratch buffer of at least
+ *   xv_gram_f64_workspace(n, d) bytes (XV_ERR_WORKSPACE when ws_bytes is less; the size depends on (n, d) alone and may be 0,
+ *   then ws_dev may be NULL).  Every argument check comes before the first HIP call.
+ * xv_gram_f64_rows64 = the same over double rows (the class means of xv_class_mean_f64: the between-class scatter).
+ * xv_class_mean_f64 = per-class means in double, the index convention of xv_speaker_mean: class s owns the rows
+ *   utt_index[spk_offsets[s] .. spk_offsets[s+1]) of x_dev [n, ldx]; out[s] = (their sum in double, in that order) / count,
+ *   minus c_dev [dim] when it is not NULL; a class without rows gets zeros; a row number outside [0, n) is never followed
+ *   (the class gets NaN; the caller checks its indices on the host). */
+int64_t xv_gram_f64_workspace(int64_t n, int d);
+int xv_gram_f64(int device, const float* x_dev, int64_t ldx, int64_t n, int d, const double* c_dev, const double* w_dev,
+                double* g_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+int xv_gram_f64_rows64(int device, const double* x_dev, int64_t ldx, int64_t n, int d, const double* c_dev, const double* w_dev,
+                       double* g_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+int xv_class_mean_f64(int device, const float* x_dev, int64_t ldx, int64_t n, int dim, const int32_t* spk_offsets_dev,
+                      const int32_t* utt_index_dev, int64_t num_classes, const double* c_dev, double* out_dev, int64_t ldo,
+                      void* stream);
 
 /* ---- host-side ark I/O (csrc/ark_io.cpp; no HIP calls, usable without a GPU) ---------------------
  * Batch counterpart of dataset/kaldi_io.py read_mat_ark (:974-994, records per _read_mat_binary

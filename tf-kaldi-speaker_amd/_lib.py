@@ -16,6 +16,7 @@ XV_MAX_ATT_LAYERS = 4
 XV_OK = 0
 XV_ERR_INVALID = -1
 XV_ERR_UNSUPPORTED = -2
+XV_ERR_WORKSPACE = -6
 XV_ERR_TOO_SHORT = -7
 XV_PREC_F32 = 0
 XV_PREC_BF16X3 = 1
@@ -31,6 +32,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_frontend_cmn_select", "xv_length_normalize", "xv_speaker_mean",
            "xv_score_prepare", "xv_score_matrix", "xv_score_pairs", "xv_score_histogram",
            "xv_plda_prepare", "xv_plda_matrix", "xv_plda_pairs", "xv_plda_histogram",
+           "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
            "xv_ark_open", "xv_ark_open_scp", "xv_ark_scp_count", "xv_ark_scp_shapes", "xv_ark_next_batch", "xv_ark_pending_shape", "xv_ark_skipped", "xv_ark_set_copy_threads", "xv_ark_error", "xv_ark_close", "xv_ark_format_vectors", "xv_crc32c", "xv_pack_rows"]
 
 
@@ -117,6 +119,11 @@ def load():
     lib.xv_plda_matrix.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, i64, vp]
     lib.xv_plda_pairs.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, vp, i64, vp, vp]
     lib.xv_plda_histogram.argtypes = [i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, vp]
+    lib.xv_gram_f64_workspace.argtypes = [i64, i32]
+    lib.xv_gram_f64_workspace.restype = i64
+    lib.xv_gram_f64.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
+    lib.xv_gram_f64_rows64.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
+    lib.xv_class_mean_f64.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, vp, vp, i64, vp]
     lib.xv_ark_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
     lib.xv_ark_open_scp.argtypes = [C.c_char_p, C.POINTER(vp)]
     lib.xv_ark_scp_count.argtypes = [vp]
@@ -139,7 +146,7 @@ def load():
     lib.xv_crc32c.restype = C.c_uint32
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
-                     "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows"):
+                     "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

@@ -15,7 +15,7 @@
 // runs on the same kernels: the log likelihood ratio of plda.cc expands to  s(i, j) = sum_d A_id t_jd + sum_d W_id t_jd^2 + rho_i
 // (tf-kaldi-speaker_amd/plda.py has the algebra), i.e. a product of packed rows plus a row term and a column term added in the
 // epilogue.  plda_rows_kernel normalises the transformed rows and packs the operands; rho / tau are accumulated in double and
-// rounded once.  Training (ivector-compute-lda / -plda, ivector-adapt-plda) stays with Kaldi.  **Parity unpinned** as well.
+// rounded once.  Training (ivector-compute-lda / -plda) is csrc/backend.hip; ivector-adapt-plda stays with Kaldi.  **Parity unpinned** as well.
 //
 //  * row_prepare_kernel: one wave per row; y = x - mean, then y / sqrt(sum y^2 + eps).  The sum of squares is taken of
 //    the row scaled by the power of two of its largest element (exact), so rows of any magnitude neither overflow nor flush.

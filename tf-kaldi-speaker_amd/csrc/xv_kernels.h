@@ -241,6 +241,17 @@ hipError_t launch_plda_pairs(const float* a, int64_t lda, int n, const float* ro
                              const float* col_bias, int k, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
                              hipStream_t s);
 
+// back-end training statistics (csrc/backend.hip): G = sum_r w_r (x_r - c)(x_r - c)^T in double (c, w may be null), both
+// triangles of g [d, d]; ws holds gram_f64_workspace_bytes(n, d) bytes; rows fp32, or double in the _rows64 form
+int64_t gram_f64_workspace_bytes(int64_t n, int d);
+hipError_t launch_gram_f64(const float* x, int64_t ldx, int64_t n, int d, const double* c, const double* w, double* g,
+                           double* ws, hipStream_t s);
+hipError_t launch_gram_f64_rows64(const double* x, int64_t ldx, int64_t n, int d, const double* c, const double* w, double* g,
+                                  double* ws, hipStream_t s);
+// out[s] = mean of the rows index[off[s] .. off[s + 1]) of x [n, dim] in double, list order (- c when given); empty class: 0
+hipError_t launch_class_mean_f64(const float* x, int64_t ldx, int64_t n, int dim, const int32_t* off, const int32_t* index,
+                                 int64_t num_classes, const double* c, double* out, int64_t ldo, hipStream_t s);
+
 // attention scores (model/pooling.py:189-194): score[r, h] = scale * sum_d key[r, h*dk_h + d] * q[h, d]
 // (split_key) or sum_d key[r, d] * q[h, d] (no split; dk_h == dk).
 hipError_t launch_att_scores(const float* key, int64_t ldk, int64_t rows, const float* query, int H,

@@ -2139,6 +2139,58 @@ int xv_speaker_mean(int device, const float* x_dev, int64_t ldx, int dim, const 
   return XV_OK;
 }
 
+// shared argument check of the two Gram entry points
+static int gram_operands(const char* who, const void* x, int64_t ldx, int64_t n, int d, const double* g, const void* ws,
+                         int64_t ws_bytes) {
+  if (d < 1 || d > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= d <= 2048, got %d", who, d);
+  if (n < 0 || ldx < d || !g || (n > 0 && !x)) return fail(nullptr, XV_ERR_INVALID, "%s: bad arguments", who);
+  const int64_t need = gram_f64_workspace_bytes(n, d);
+  if (ws_bytes < need || (need > 0 && !ws))
+    return fail(nullptr, XV_ERR_WORKSPACE, "%s: workspace %lld bytes < %lld", who, (long long)ws_bytes, (long long)need);
+  return XV_OK;
+}
+
+int64_t xv_gram_f64_workspace(int64_t n, int d) {
+  if (d < 1 || d > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_gram_f64_workspace: 1 <= d <= 2048, got %d", d);
+  if (n < 0) return fail(nullptr, XV_ERR_INVALID, "xv_gram_f64_workspace: n < 0");
+  return gram_f64_workspace_bytes(n, d);
+}
+
+int xv_gram_f64(int device, const float* x_dev, int64_t ldx, int64_t n, int d, const double* c_dev, const double* w_dev,
+                double* g_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = gram_operands("xv_gram_f64", x_dev, ldx, n, d, g_dev, ws_dev, ws_bytes)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_gram_f64(x_dev, ldx, n, d, c_dev, w_dev, g_dev, static_cast<double*>(ws_dev),
+                                       static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "gram_f64 launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_gram_f64_rows64(int device, const double* x_dev, int64_t ldx, int64_t n, int d, const double* c_dev, const double* w_dev,
+                       double* g_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = gram_operands("xv_gram_f64_rows64", x_dev, ldx, n, d, g_dev, ws_dev, ws_bytes)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_gram_f64_rows64(x_dev, ldx, n, d, c_dev, w_dev, g_dev, static_cast<double*>(ws_dev),
+                                              static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "gram_f64_rows64 launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_class_mean_f64(int device, const float* x_dev, int64_t ldx, int64_t n, int dim, const int32_t* spk_offsets_dev,
+                      const int32_t* utt_index_dev, int64_t num_classes, const double* c_dev, double* out_dev, int64_t ldo,
+                      void* stream) {
+  if (!x_dev || !out_dev || !spk_offsets_dev || !utt_index_dev) return fail(nullptr, XV_ERR_INVALID, "xv_class_mean_f64: null pointer");
+  if (num_classes < 0 || n < 0 || dim < 1 || ldx < dim || ldo < dim) return fail(nullptr, XV_ERR_INVALID, "xv_class_mean_f64: bad dimensions");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_class_mean_f64(x_dev, ldx, n, dim, spk_offsets_dev, utt_index_dev, num_classes, c_dev, out_dev, ldo,
+                                             static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "class_mean_f64 launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 int xv_score_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* mean_dev,
                      const float* transform_dev, int64_t ldt, int d_out, int t_cols, int normalize, float eps, float* out_dev,
                      int64_t ldo, void* stream) {

@@ -2,7 +2,7 @@
 xv_plda_pairs / xv_plda_histogram): the last line of every recipe of the reference, `ivector-plda-scoring
 --normalize-length=true [--num-utts=ark:num_utts.ark] "ivector-copy-plda --smoothing=0.0 plda - |" enroll test trials scores`
 (egs/voxceleb/v1/run.sh:410-426, egs/voxceleb/v2|v3/run.sh:188-190, egs/sre/v1/run.sh:415-491, egs/fisher/v1/eval_plda.sh).
-Training (`ivector-compute-lda`, `ivector-compute-plda`, `ivector-adapt-plda`) stays with Kaldi.  Kaldi is absent from the
+Training (`ivector-compute-lda`, `ivector-compute-plda`) is in backend.py; `ivector-adapt-plda` stays with Kaldi.  Kaldi is absent from the
 reference tree: model file, TransformIvector and LogLikelihoodRatio restate plda.cc as published (**parity unpinned**),
 checked against tests/helpers/ref_plda.py.
 

@@ -19,7 +19,7 @@ the speaker means (an enrolment key without an entry counts as 1; how many is re
 score` in trial order.  A trial whose key is missing is skipped and counted on stderr; the exit status is non-zero only if
 no trial was scored.  --eer and --min-dcf need the third column and print `EER: x%` and `minDCF(p-target=P): x` of the
 scores as written (sid/compute_min_dcf.py; exact, from the sorted scores, on the host).  Kaldi is absent from the reference
-tree: **parity unpinned**.  Training the model (ivector-compute-lda / -plda, ivector-adapt-plda) stays with Kaldi."""
+tree: **parity unpinned**.  Training the model (ivector-compute-lda / -plda) is compute_lda.py / compute_plda.py; ivector-adapt-plda stays with Kaldi."""
 import argparse
 import sys
 

@@ -2,8 +2,8 @@
 xv_score_pairs / xv_score_histogram): what the reference does with Kaldi binaries in its cosine back-end
 (egs/voxceleb/v1/run.sh:362-365 plain cosine, :404-408 mean-subtract + transform-vec + length-norm +
 ivector-compute-dot-products) and with a numpy double loop in its model-selection metric (compute_cos_pairwise_eer,
-misc/utils.py:307-346).  PLDA scoring with a trained model is in plda.py, on the same kernels; PLDA / LDA training stays
-with Kaldi.
+misc/utils.py:307-346).  PLDA scoring with a trained model is in plda.py, on the same kernels; PLDA / LDA training is in
+backend.py.
 
 Everything is fp32 with exact products: a score of two prepared rows of length d is within (d + 8) * 2^-24 of the exact
 value.  Arrays go in and come out as numpy; a float32 torch tensor that already lives on the device is taken as it is,
