@@ -242,6 +242,52 @@ int xv_frontend_cmn_select(int device, const float* feats_dev, int ld, int dim, 
                            int batch, const int32_t* src_rows_dev, int64_t out_rows, int cmn_window, int center,
                            int min_window, double* scratch_dev, float* out_dev, void* stream);
 
+/* ---- MFCC features and energy VAD on the GPU (csrc/mfcc.hip): the first step of the reference recipe
+ * (egs/voxceleb/v1/run.sh:57-65), steps/make_mfcc.sh and sid/compute_vad_decision.sh.  The algorithm is Kaldi's as published
+ * and is written out in the header of csrc/mfcc.hip; **parity unpinned**.  Field names and defaults are the options of Kaldi's
+ * compute-mfcc-feats; a field set to a value this library cannot honour is refused by xv_mfcc_create with a message
+ * (xv_last_error(NULL)): dither != 0 (Kaldi's default 1.0 is random noise; here features are deterministic), htk_compat,
+ * round_to_power_of_two = 0, a padded frame length other than 256 or 512 samples, num_mel_bins > 64, frame shift > frame length. */
+enum { XV_WINDOW_POVEY = 0, XV_WINDOW_HAMMING = 1, XV_WINDOW_HANNING = 2, XV_WINDOW_RECTANGULAR = 3 };
+typedef struct {
+  int32_t struct_size;             /* sizeof(xv_mfcc_opts)                         */
+  float sample_frequency;          /* --sample-frequency          16000            */
+  float frame_length_ms;           /* --frame-length              25               */
+  float frame_shift_ms;            /* --frame-shift               10               */
+  float preemphasis_coefficient;   /* --preemphasis-coefficient   0.97             */
+  int32_t remove_dc_offset;        /* --remove-dc-offset          1                */
+  int32_t window_type;             /* --window-type               XV_WINDOW_POVEY  */
+  int32_t round_to_power_of_two;   /* --round-to-power-of-two     1                */
+  int32_t snip_edges;              /* --snip-edges                1                */
+  float dither;                    /* --dither                    0 (Kaldi: 1.0)   */
+  int32_t num_mel_bins;            /* --num-mel-bins              23               */
+  float low_freq;                  /* --low-freq                  20               */
+  float high_freq;                 /* --high-freq                 0 (<= 0: Nyquist + value) */
+  int32_t num_ceps;                /* --num-ceps                  13               */
+  float cepstral_lifter;           /* --cepstral-lifter           22               */
+  int32_t use_energy;              /* --use-energy                1                */
+  float energy_floor;              /* --energy-floor              0                */
+  int32_t raw_energy;              /* --raw-energy                1                */
+  int32_t htk_compat;              /* --htk-compat                0 (1 is refused) */
+} xv_mfcc_opts;
+typedef struct xv_mfcc xv_mfcc;
+/* xv_mfcc_create / xv_mfcc_destroy: the tables of one option set (window, FFT twiddles, mel bank, DCT x lifter; built in double,
+ *   rounded once to fp32) on `device`.  Option checks come before the first HIP call.
+ * xv_mfcc_num_frames: frames compute-mfcc-feats yields for an utterance of num_samples samples (< 0: XV_ERR_INVALID).
+ * xv_mfcc_compute = `compute-mfcc-feats`: wave_dev holds the int16 samples of `batch` utterances back to back, utterance b at
+ *   [sample_offsets_dev[b], sample_offsets_dev[b + 1]); frame_offsets_dev [batch + 1] are the prefix sums of xv_mfcc_num_frames.
+ *   Writes the num_ceps features of frame t of utterance b to feats_dev[(frame_offsets[b] + t) * ld .. ], ld >= num_ceps; other
+ *   columns are left alone.  fp32, no atomics: repeated runs are bit-identical.
+ * xv_vad_energy = `compute-vad-decision`: column 0 of feats_dev is the log energy; writes one float (0 or 1) per frame to
+ *   vad_dev[frame_offsets[b] + t].  The mean is accumulated in double in a fixed order. */
+int xv_mfcc_create(const xv_mfcc_opts* opts, int device, xv_mfcc** out);
+void xv_mfcc_destroy(xv_mfcc* m);
+int64_t xv_mfcc_num_frames(const xv_mfcc* m, int64_t num_samples);
+int xv_mfcc_compute(xv_mfcc* m, const int16_t* wave_dev, const int64_t* sample_offsets_dev, const int32_t* frame_offsets_dev,
+                    int batch, float* feats_dev, int64_t ld, void* stream);
+int xv_vad_energy(int device, const float* feats_dev, int64_t ld, const int32_t* frame_offsets_dev, int batch, float threshold,
+                  float mean_scale, int context, float proportion, float* vad_dev, void* stream);
+
 /* ---- post-step on the GPU (csrc/post.hip): what the reference runs as Kaldi binaries behind extract.py
  * (egs/voxceleb/v1/nnet/run_extract_embeddings.sh:80-103).
  * xv_length_normalize = `ivector-normalize-length [--scaleup=false]` (:86,88,101): out[r] = x[r] / ratio,

@@ -29,7 +29,8 @@ XV_ACT_RELU, XV_ACT_LRELU, XV_ACT_PRELU = 0, 1, 2
 EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_option", "xv_check_overflow", "xv_flags_async", "xv_flags_decode", "xv_node_id", "xv_node_context", "xv_layer_two_unit",
            "xv_plan_create", "xv_plan_query", "xv_plan_destroy", "xv_forward", "xv_profile_begin", "xv_profile_end",
            "xv_destroy", "xv_last_error",
-           "xv_frontend_cmn_select", "xv_length_normalize", "xv_speaker_mean",
+           "xv_frontend_cmn_select", "xv_mfcc_create", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_mfcc_compute", "xv_vad_energy",
+           "xv_length_normalize", "xv_speaker_mean",
            "xv_score_prepare", "xv_score_matrix", "xv_score_pairs", "xv_score_histogram",
            "xv_plda_prepare", "xv_plda_matrix", "xv_plda_pairs", "xv_plda_histogram",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
@@ -51,6 +52,17 @@ class ModelDesc(C.Structure):
         ("att_apply_nonlinear", C.c_int32), ("att_use_scale", C.c_int32), ("att_num_heads", C.c_int32),
         ("att_split_value", C.c_int32), ("att_split_key", C.c_int32), ("precision", C.c_int32),
         ("resnet_blocks", C.c_int32 * 4), ("resnet_maxpooling", C.c_int32), ("resnet_time_stride", C.c_int32),
+    ]
+
+
+class MfccOpts(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("sample_frequency", C.c_float), ("frame_length_ms", C.c_float),
+        ("frame_shift_ms", C.c_float), ("preemphasis_coefficient", C.c_float), ("remove_dc_offset", C.c_int32),
+        ("window_type", C.c_int32), ("round_to_power_of_two", C.c_int32), ("snip_edges", C.c_int32), ("dither", C.c_float),
+        ("num_mel_bins", C.c_int32), ("low_freq", C.c_float), ("high_freq", C.c_float), ("num_ceps", C.c_int32),
+        ("cepstral_lifter", C.c_float), ("use_energy", C.c_int32), ("energy_floor", C.c_float), ("raw_energy", C.c_int32),
+        ("htk_compat", C.c_int32),
     ]
 
 
@@ -109,6 +121,13 @@ def load():
     lib.xv_destroy.argtypes = [vp]
     lib.xv_destroy.restype = None
     lib.xv_frontend_cmn_select.argtypes = [i32, vp, i32, i32, vp, i32, vp, i64, i32, i32, i32, vp, vp, vp]
+    lib.xv_mfcc_create.argtypes = [C.POINTER(MfccOpts), i32, C.POINTER(vp)]
+    lib.xv_mfcc_destroy.argtypes = [vp]
+    lib.xv_mfcc_destroy.restype = None
+    lib.xv_mfcc_num_frames.argtypes = [vp, i64]
+    lib.xv_mfcc_num_frames.restype = i64
+    lib.xv_mfcc_compute.argtypes = [vp, vp, vp, vp, i32, vp, i64, vp]
+    lib.xv_vad_energy.argtypes = [i32, vp, i64, vp, i32, C.c_float, C.c_float, i32, C.c_float, vp, vp]
     lib.xv_length_normalize.argtypes = [i32, vp, i64, i64, i32, i32, vp, i64, vp]
     lib.xv_speaker_mean.argtypes = [i32, vp, i64, i32, vp, vp, i64, vp, i64, vp]
     lib.xv_score_prepare.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, i32, i32, i32, C.c_float, vp, i64, vp]
@@ -146,7 +165,8 @@ def load():
     lib.xv_crc32c.restype = C.c_uint32
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
-                     "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace"):
+                     "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
+                     "xv_mfcc_destroy", "xv_mfcc_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

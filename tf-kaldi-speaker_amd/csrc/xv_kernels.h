@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
+#include "../../include/xvec_hip.h"
+
 namespace xv {
 
 // Epilogue activation applied after  v = acc * scale[n] + shift[n].
@@ -204,6 +208,18 @@ hipError_t launch_grid_unpad_n(const float* grid, const int32_t* off0, int B, in
 hipError_t launch_cmn_select(const float* x, int64_t ld, int dim, const int32_t* off, int B, double* prefix,
                              const int32_t* src, int64_t out_rows, int window, int center, int min_window, float* out,
                              hipStream_t s);
+
+// MFCC + energy VAD (csrc/mfcc.hip; the opaque xv_mfcc of include/xvec_hip.h holds the tables).  mfcc_create validates the
+// options (reason in *err) before any HIP call.
+int mfcc_create(const xv_mfcc_opts* opts, int device, xv_mfcc** out, std::string* err);
+void mfcc_destroy(xv_mfcc* m);
+int mfcc_num_frames(const xv_mfcc* m, int64_t num_samples, int64_t* out);
+int mfcc_device(const xv_mfcc* m);
+int mfcc_num_ceps(const xv_mfcc* m);
+hipError_t launch_mfcc(xv_mfcc* m, const int16_t* wave, const int64_t* sample_off, const int32_t* frame_off, int B, float* out,
+                       int64_t ld, hipStream_t s);
+hipError_t launch_vad_energy(const float* feats, int64_t ld, const int32_t* frame_off, int B, float threshold, float mean_scale,
+                             int context, float proportion, float* vad, hipStream_t s);
 
 // post-step (csrc/post.hip): ivector-normalize-length / ivector-mean of run_extract_embeddings.sh:80-103
 hipError_t launch_length_norm(const float* x, int64_t ldx, int64_t rows, int dim, int scaleup, float* y, int64_t ldy,

@@ -2116,6 +2116,49 @@ int xv_frontend_cmn_select(int device, const float* feats_dev, int ld, int dim, 
   return XV_OK;
 }
 
+int xv_mfcc_create(const xv_mfcc_opts* opts, int device, xv_mfcc** out) {
+  if (!opts || !out) return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_create: null pointer");
+  *out = nullptr;
+  std::string err;
+  const int rc = mfcc_create(opts, device, out, &err);
+  if (rc != XV_OK) return fail(nullptr, rc, "xv_mfcc_create: %s", err.c_str());
+  return XV_OK;
+}
+
+void xv_mfcc_destroy(xv_mfcc* m) { mfcc_destroy(m); }
+
+int64_t xv_mfcc_num_frames(const xv_mfcc* m, int64_t num_samples) {
+  int64_t t = 0;
+  if (!m || mfcc_num_frames(m, num_samples, &t) != 0) return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_num_frames: bad argument");
+  return t;
+}
+
+int xv_mfcc_compute(xv_mfcc* m, const int16_t* wave_dev, const int64_t* sample_offsets_dev, const int32_t* frame_offsets_dev,
+                    int batch, float* feats_dev, int64_t ld, void* stream) {
+  if (!m || !wave_dev || !sample_offsets_dev || !frame_offsets_dev || !feats_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_compute: null pointer");
+  if (batch < 1 || ld < mfcc_num_ceps(m)) return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_compute: bad dimensions (batch >= 1, ld >= num_ceps)");
+  DeviceGuard g(mfcc_device(m));
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", mfcc_device(m));
+  const hipError_t e = launch_mfcc(m, wave_dev, sample_offsets_dev, frame_offsets_dev, batch, feats_dev, ld,
+                                   static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "mfcc launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_vad_energy(int device, const float* feats_dev, int64_t ld, const int32_t* frame_offsets_dev, int batch, float threshold,
+                  float mean_scale, int context, float proportion, float* vad_dev, void* stream) {
+  if (!feats_dev || !frame_offsets_dev || !vad_dev) return fail(nullptr, XV_ERR_INVALID, "xv_vad_energy: null pointer");
+  if (batch < 1 || ld < 1 || context < 0 || !(proportion >= 0.f && proportion <= 1.f))
+    return fail(nullptr, XV_ERR_INVALID, "xv_vad_energy: bad arguments (batch >= 1, ld >= 1, context >= 0, 0 <= proportion <= 1)");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_vad_energy(feats_dev, ld, frame_offsets_dev, batch, threshold, mean_scale, context, proportion,
+                                         vad_dev, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "vad launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 int xv_length_normalize(int device, const float* x_dev, int64_t ldx, int64_t rows, int dim, int scaleup, float* out_dev,
                         int64_t ldo, void* stream) {
   if (!x_dev || !out_dev) return fail(nullptr, XV_ERR_INVALID, "xv_length_normalize: null pointer");

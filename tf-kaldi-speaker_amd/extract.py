@@ -56,6 +56,14 @@ def build_parser():
     parser.add_argument("--vad-rspecifier", type=str, default="",
                         help="Kaldi vector ark of per-frame VAD decisions, same key order as the features; voiced frames "
                              "are selected on the GPU (extension; replaces `select-voiced-frames`).")
+    parser.add_argument("--wav-input", action="store_true",
+                        help="The rspecifier is `scp:wav.scp`: MFCC features (--mfcc-config) and the energy VAD (--vad-config) are "
+                             "computed on the GPU and handed to the --cmn-window front-end and the network without a feature file "
+                             "(extension; replaces steps/make_mfcc.sh + sid/compute_vad_decision.sh of run.sh:57-65).")
+    parser.add_argument("--mfcc-config", type=str, default="", help="Kaldi conf/mfcc.conf for --wav-input.")
+    parser.add_argument("--vad-config", type=str, default="", help="Kaldi conf/vad.conf for --wav-input (default: Kaldi's defaults).")
+    parser.add_argument("--channel", type=int, default=-1, help="Channel of the wav files for --wav-input (-1: they must be mono).")
+    parser.add_argument("--batch-samples", type=int, default=32 << 20, help="Samples packed into one device batch with --wav-input.")
     parser.add_argument("model_dir", type=str, help="The model directory.")
     parser.add_argument("rspecifier", type=str, help="Kaldi feature rspecifier (or ark file).")
     parser.add_argument("wspecifier", type=str, help="Kaldi output wspecifier (or ark file).")
@@ -421,6 +429,53 @@ def run_native(trainer, rspecifier, writer, min_chunk_size, chunk_size, normaliz
     return done, skipped
 
 
+def run_wav(trainer, rspecifier, writer, mopts, vopts, min_chunk_size, chunk_size, normalize, batch_frames, cmn_window=0,
+            channel=-1, batch_samples=32 << 20):
+    """--wav-input: wav.scp -> MFCC -> energy VAD -> sliding CMN + voiced-frame selection -> network, one device batch of about
+    batch_samples samples at a time; the features never leave the device.  Utterances without frames, and those left with fewer
+    than min_chunk_size voiced frames, are skipped as on the feature-file route."""
+    import torch
+    from .frontend import cmn_select_packed
+    from .mfcc import Mfcc, read_wav_scp, vad_packed, wav_batches
+    dev_index = trainer._device_index
+    devname = "cuda:%d" % dev_index
+    mfcc = Mfcc(mopts, dev_index)
+    done = skipped = 0
+
+    def on_error(key, e):
+        nonlocal skipped
+        skipped += 1
+        log.warning("[WARNING] %s: %s" % (key, e))
+
+    for keys, samples, soff in wav_batches(read_wav_scp(rspecifier), mopts, batch_samples, channel, on_error):
+        with torch.cuda.device(dev_index):
+            raw, foff = mfcc.compute(torch.from_numpy(samples).to(devname), soff)
+            vad = vad_packed(raw, foff, vopts).cpu().numpy()
+            vads = [vad[foff[i]:foff[i + 1]] for i in range(len(keys))]
+            dev, offsets, kept = cmn_select_packed(raw, foff, vads, cmn_window=cmn_window, min_frames=min_chunk_size)
+        skipped += len(keys) - len(kept)
+        keys = [keys[i] for i in kept]
+        if not keys:
+            continue
+        if np.diff(offsets).max() > chunk_size:         # rare: chunk / weight / average on host views
+            feats = dev.cpu().numpy()
+            items = [(k, feats[offsets[i]:offsets[i + 1]]) for i, k in enumerate(keys)]
+            out = []
+            extract_stream(trainer.predict_list, iter(items), lambda k, v: out.append((k, v)), min_chunk_size, chunk_size,
+                           normalize, batch_frames, prefetch=0)
+            writer.write([k for k, _ in out], np.stack([v for _, v in out]))
+            done += len(out)
+            continue
+        with torch.cuda.device(dev_index):
+            emb = trainer.checked_or_rerun(trainer.predict_packed(dev, offsets).cpu().numpy(), dev, offsets)
+        if normalize:
+            emb = emb / np.sqrt(np.sum(np.square(emb), axis=1, keepdims=True))
+        writer.write(keys, emb)
+        done += len(keys)
+    mfcc.close()
+    return done, skipped
+
+
 def _writer_idle(wq, werr):
     """Block until the writer thread has consumed everything queued so far (queue.join semantics via task counts)."""
     wq.join()
@@ -443,7 +498,23 @@ def main(argv=None):
         dim = int(f.readline().strip())
 
     spec = args.rspecifier.strip()
-    if spec.rsplit(".", 1)[-1] == "scp" and not (args.scp_input and spec.startswith(("scp:", "scp,"))):   # extract.py:59-61
+    mopts = vopts = None
+    if args.wav_input:
+        from .mfcc import MfccOptions, VadOptions
+        if not spec.startswith("scp:"):
+            sys.exit("--wav-input: the rspecifier must be scp:wav.scp")
+        if not args.mfcc_config or args.vad_rspecifier:
+            sys.exit("--wav-input needs --mfcc-config and computes its own VAD (no --vad-rspecifier)")
+        try:
+            mopts = MfccOptions.from_config(args.mfcc_config)
+            vopts = VadOptions.from_config(args.vad_config) if args.vad_config else VadOptions()
+        except ValueError as e:
+            sys.exit("--wav-input: %s" % e)
+        if mopts.num_ceps < dim:
+            sys.exit("--wav-input: the model expects %d features, %s gives %d" % (dim, args.mfcc_config, mopts.num_ceps))
+    elif args.mfcc_config or args.vad_config:
+        sys.exit("--mfcc-config / --vad-config go with --wav-input")
+    elif spec.rsplit(".", 1)[-1] == "scp" and not (args.scp_input and spec.startswith(("scp:", "scp,"))):   # extract.py:59-61
         sys.exit("The rspecifier must be ark or input pipe")
 
     from .trainer import Trainer
@@ -466,7 +537,10 @@ def main(argv=None):
     if trainer.model is not None and os.path.isfile(os.path.join(trainer.model, "checkpoint")):
         trainer.load()                      # the reference restores lazily inside the first predict (trainer.py:891-895)
     t_loop = time.perf_counter()
-    if native:
+    if args.wav_input:
+        done, skipped = run_wav(trainer, args.rspecifier, writer, mopts, vopts, args.min_chunk_size, args.chunk_size,
+                                args.normalize, args.batch_frames, args.cmn_window, args.channel, args.batch_samples)
+    elif native:
         done, skipped = run_native(trainer, args.rspecifier, writer, args.min_chunk_size, args.chunk_size,
                                    args.normalize, args.batch_frames, args.cmn_window, args.vad_rspecifier)
     else:
