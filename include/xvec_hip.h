@@ -368,6 +368,34 @@ int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, co
                       const float* b_dev, int64_t ldb, int64_t m, const float* tau_dev, const int32_t* labels_b_dev, int k, double lo,
                       double hi, int nbins, uint64_t* hist_same_dev, uint64_t* hist_diff_dev, void* stream);
 
+/* ---- classifier-head validation loss on the GPU (csrc/loss.hip): what Trainer.valid evaluates per batch
+ * (model/trainer.py:756-884), loss_i = logsumexp_c(z_ic) - z_i,label as tf.losses.sparse_softmax_cross_entropy takes it, without
+ * ever writing the [n, C] logits.  Products are exact fp32 with fp32 accumulation (the tile arithmetic of the scoring calls);
+ * the error bound is derived in the header of csrc/loss.hip.  No floating-point atomics: repeats are bit-identical and a
+ * row's result does not depend on its position in the batch.  1 <= embed_dim <= 2048 (XV_ERR_UNSUPPORTED otherwise).
+ * xv_loss_prepare_classes = `softmax/output/kernel` [embed_dim, num_classes] -> class rows [num_classes, ldc]: the transpose
+ *   for XV_LOSS_SOFTMAX (tf.layers.dense, model/loss.py:30-34), with `normalize` the columns divided by
+ *   sqrt(max(sum w^2, 1e-12)) (tf.nn.l2_normalize(w, dim=0), model/loss.py:133,242,328).  Once per checkpoint.
+ * xv_loss_workspace = bytes of scratch xv_loss_classifier needs for n rows and num_classes classes: 256 + 16 n ceil(C / 128),
+ *   against the 4 n C bytes of the logit matrix.
+ * xv_loss_classifier = the four heads: XV_LOSS_SOFTMAX z = x W + b (bias_dev [num_classes] or NULL; model/loss.py:9-48);
+ *   XV_LOSS_ASOFTMAX (model/loss.py:80-198; margin = m, one of 1, 2, 4, anything else XV_ERR_UNSUPPORTED as the reference
+ *   raises; m = 1 is the plain cross-entropy on x W^), XV_LOSS_AMSOFTMAX (model/loss.py:201-286: phi = cos t - margin),
+ *   XV_LOSS_ARCSOFTMAX (model/loss.py:289-384: phi = cos(t + margin) while cos t > cos(pi - margin), else
+ *   -cos(t + margin) - 2); the target logit becomes (1 - fa) z + fa ||x|| phi with fa = 1 / (1 + lambda) from the host.
+ *   Fills, per row, loss_dev, target_dev (the target logit after the margin), lse_dev and top1_dev (the class of the
+ *   largest logit BEFORE the margin, the lowest index of equal ones: the argmax of model/trainer.py:1097).
+ *   A label outside [0, num_classes) is never followed: the call waits for its first kernel, returns XV_ERR_INVALID and
+ *   launches nothing else (this one wait makes the call unfit for hipGraph capture).  Everything after it is stream-ordered. */
+enum { XV_LOSS_SOFTMAX = 0, XV_LOSS_ASOFTMAX = 1, XV_LOSS_AMSOFTMAX = 2, XV_LOSS_ARCSOFTMAX = 3 };
+int xv_loss_prepare_classes(int device, const float* kernel_dev, int64_t ldk, int embed_dim, int64_t num_classes, int normalize,
+                            float* classes_dev, int64_t ldc, void* stream);
+int64_t xv_loss_workspace(int64_t n, int64_t num_classes);
+int xv_loss_classifier(int device, const float* x_dev, int64_t ldx, int64_t n, int embed_dim, const int32_t* labels_dev,
+                       const float* classes_dev, int64_t ldc, int64_t num_classes, const float* bias_dev, int head, double margin,
+                       double fa, float* loss_dev, float* target_dev, float* lse_dev, int32_t* top1_dev, void* ws_dev,
+                       int64_t ws_bytes, void* stream);
+
 /* ---- back-end training statistics on the GPU (csrc/backend.hip): the sums behind `ivector-mean`, `ivector-compute-lda` and
  * `ivector-compute-plda` (egs/voxceleb/v1/run.sh:384-400, egs/sre/v1/run.sh:399-411); the d x d linear algebra behind them is
  * host float64 (tf_kaldi_speaker_amd.backend).  Kaldi is absent from the reference tree: **parity unpinned**.

@@ -257,6 +257,21 @@ hipError_t launch_plda_pairs(const float* a, int64_t lda, int n, const float* ro
                              const float* col_bias, int k, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
                              hipStream_t s);
 
+// classifier-head validation loss (csrc/loss.hip): model/loss.py:9-48,80-384 without the logit matrix
+// kernel [E, ldk] -> class rows [C, ldr], columns normalised (tf.nn.l2_normalize) when `normalize`
+hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,
+                               hipStream_t s);
+int64_t loss_workspace_bytes(int64_t n, int64_t C);
+// target[i] = the target logit after the margin (double arithmetic, rounded once); the first word of ws is zeroed and then
+// set when a label lies outside [0, C) (that row gets NaN and is never followed)
+hipError_t launch_loss_rows(const float* x, int64_t ldx, int64_t n, int E, const int32_t* labels, const float* rows, int64_t ldr,
+                            int64_t C, const float* bias, int head, int m, double margin, double fa, float* target, void* ws,
+                            hipStream_t s);
+// tile kernel + merge: loss, lse, top1 [n] from x, the class rows and target; ws as sized by loss_workspace_bytes
+hipError_t launch_loss_tiles(const float* x, int64_t ldx, int n, int E, const int32_t* labels, const float* rows, int64_t ldr, int C,
+                             const float* bias, const float* target, float* loss, float* lse, int32_t* top1, void* ws,
+                             hipStream_t s);
+
 // back-end training statistics (csrc/backend.hip): G = sum_r w_r (x_r - c)(x_r - c)^T in double (c, w may be null), both
 // triangles of g [d, d]; ws holds gram_f64_workspace_bytes(n, d) bytes; rows fp32, or double in the _rows64 form
 int64_t gram_f64_workspace_bytes(int64_t n, int d);

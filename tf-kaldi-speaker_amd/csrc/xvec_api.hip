@@ -2316,6 +2316,63 @@ int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, c
   return XV_OK;
 }
 
+// model/loss.py:133,242,328 (tf.nn.l2_normalize(w, dim=0)) and the transpose tf.layers.dense implies (:30-34)
+int xv_loss_prepare_classes(int device, const float* kernel_dev, int64_t ldk, int embed_dim, int64_t num_classes, int normalize,
+                            float* classes_dev, int64_t ldc, void* stream) {
+  if (!kernel_dev || !classes_dev) return fail(nullptr, XV_ERR_INVALID, "xv_loss_prepare_classes: null pointer");
+  if (embed_dim < 1 || embed_dim > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_prepare_classes: 1 <= embed_dim <= 2048, got %d", embed_dim);
+  if (num_classes < 0 || num_classes > INT32_MAX || ldk < num_classes || ldc < embed_dim)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_prepare_classes: bad dimensions");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_loss_classes(kernel_dev, ldk, embed_dim, num_classes, normalize ? 1 : 0, classes_dev, ldc,
+                                           static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "loss_classes launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int64_t xv_loss_workspace(int64_t n, int64_t num_classes) { return loss_workspace_bytes(n, num_classes); }
+
+// model/loss.py:9-48 (softmax), :80-198 (asoftmax), :201-286 (additive margin), :289-384 (additive angular margin), each
+// followed by tf.losses.sparse_softmax_cross_entropy; top1 = the argmax of model/trainer.py:1097
+int xv_loss_classifier(int device, const float* x_dev, int64_t ldx, int64_t n, int embed_dim, const int32_t* labels_dev,
+                       const float* classes_dev, int64_t ldc, int64_t num_classes, const float* bias_dev, int head, double margin,
+                       double fa, float* loss_dev, float* target_dev, float* lse_dev, int32_t* top1_dev, void* ws_dev,
+                       int64_t ws_bytes, void* stream) {
+  if (!x_dev || !labels_dev || !classes_dev || !loss_dev || !target_dev || !lse_dev || !top1_dev || !ws_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: null pointer");
+  if (embed_dim < 1 || embed_dim > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_classifier: 1 <= embed_dim <= 2048, got %d", embed_dim);
+  if (n < 0 || n > INT32_MAX || num_classes < 1 || num_classes > INT32_MAX || ldx < embed_dim || ldc < embed_dim)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: bad dimensions");
+  if (head < XV_LOSS_SOFTMAX || head > XV_LOSS_ARCSOFTMAX) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: unknown head %d", head);
+  if (bias_dev && head != XV_LOSS_SOFTMAX) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: only the softmax head has a bias");
+  int m = 0;
+  if (head == XV_LOSS_ASOFTMAX) {
+    if (margin != 1.0 && margin != 2.0 && margin != 4.0)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_classifier: m=%g is not supported (asoftmax: 1, 2 or 4)", margin);   // loss.py:168
+    m = (int)margin;
+  }
+  if (!(fa >= 0.0 && fa <= 1.0) || !std::isfinite(margin)) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: bad margin or fa");
+  if (ws_bytes < loss_workspace_bytes(n, num_classes))
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_loss_classifier: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)loss_workspace_bytes(n, num_classes));
+  if (n == 0) return XV_OK;
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = launch_loss_rows(x_dev, ldx, n, embed_dim, labels_dev, classes_dev, ldc, num_classes, bias_dev, head, m, margin, fa,
+                                  target_dev, ws_dev, s);
+  int bad = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, ws_dev, sizeof(int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "loss_rows failed: %s", hipGetErrorString(e));
+  if (bad) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: a label lies outside [0, %lld)", (long long)num_classes);
+  e = launch_loss_tiles(x_dev, ldx, (int)n, embed_dim, labels_dev, classes_dev, ldc, (int)num_classes, bias_dev, target_dev,
+                        loss_dev, lse_dev, top1_dev, ws_dev, s);
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "loss_tiles launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
                     int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
                     int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,

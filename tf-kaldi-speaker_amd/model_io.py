@@ -44,10 +44,10 @@ def read_checkpoint_state(nnet_dir):
     return None
 
 
-def load_weights(nnet_dir):
+def load_weights(nnet_dir, name=None):
     """-> (weights dict, step).  Step is the trailing number of the checkpoint name
-    (model/trainer.py:288-289)."""
-    name = read_checkpoint_state(nnet_dir)
+    (model/trainer.py:288-289).  `name` picks a checkpoint other than the one nnet/checkpoint names."""
+    name = name or read_checkpoint_state(nnet_dir)
     if not name:
         return None, None
     path = os.path.join(nnet_dir, name + ".npz")
@@ -66,11 +66,12 @@ def load_weights(nnet_dir):
     return weights, step
 
 
-SOFTMAX_KERNEL = "softmax/output/kernel"    # [E, num_speakers]; only extract_angle.py reads it (extract_angle.py:64-67)
+SOFTMAX_KERNEL = "softmax/output/kernel"    # [E, num_speakers]: extract_angle.py (extract_angle.py:64-67) and the loss heads (losses.py)
+SOFTMAX_BIAS = "softmax/output/bias"        # [num_speakers]: the plain softmax head only (model/loss.py:30-34)
 
 
 def _graph_variable(name):
-    if name == SOFTMAX_KERNEL:
+    if name in (SOFTMAX_KERNEL, SOFTMAX_BIAS):
         return True
     return _network_variable(name)
 

@@ -71,7 +71,12 @@ class Trainer(object):
         self.dim = int(dim)
         self.num_speakers = num_speakers
         self.is_built = False
+        self.is_valid_built = False
         self.is_loaded = False
+        self.valid_accuracy = None        # top-1 accuracy of the last valid() (model/trainer.py:1097, over all batches)
+        self.valid_num_batches = 0
+        self._softmax_host = (None, None)
+        self._head = None
         self.first_feature_split_alert = True
         self.embeddings = None            # name of the endpoint predict() returns
         self._precision = precision or os.environ.get("XVEC_PRECISION") or default_precision(params.network_type)
@@ -107,11 +112,18 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ graph build
     def build(self, mode, noupdate_var_list=None):
-        """model/trainer.py:309-338.  Only `predict` exists here (training is out of scope)."""
+        """model/trainer.py:309-338.  `predict` and `valid` exist here (training is out of scope).  `valid` accepts the four
+        classifier heads of losses.py, refuses the triplet / end-to-end losses and the end2end batch type, and returns the
+        `output` endpoint from valid() (valid_setup, trainer.py:460)."""
         assert mode == "train" or mode == "valid" or mode == "predict"
-        if mode != "predict":
-            raise NotImplementedError("only build('predict') is implemented (extraction path)")
+        if mode == "train":
+            raise NotImplementedError("build('train') is not implemented: no gradients, no optimizers (build 'valid' or 'predict')")
         p = self.params
+        if mode == "valid":
+            from . import losses
+            losses.head_config(p, validation=True)                  # NotImplementedError for a loss outside the softmax family
+            if p.dict.get("batch_type", "softmax") == "end2end":
+                raise NotImplementedError("batch_type 'end2end' (KaldiDataRandomQueue, e2e_valid_loss) is not implemented")
         # defaults the reference writes into params while building (model/tdnn.py:114-116,152-154,163-164,173-174)
         if "num_nodes_pooling_layer" not in p.dict:
             p.dict["num_nodes_pooling_layer"] = 1500
@@ -133,8 +145,9 @@ class Trainer(object):
         if "feature_norm" in p.dict and p.feature_norm:
             assert "feature_scaling_factor" in p.dict, \
                 "If feature normalization is applied, scaling factor is necessary."      # trainer.py:401
-        self.embeddings = p.embedding_node                                              # trainer.py:380
+        self.embeddings = "output" if mode == "valid" else p.embedding_node            # trainer.py:460 / :380
         self.is_built = True
+        self.is_valid_built = self.is_valid_built or mode == "valid"
 
     def set_embedding(self, embedding_node):
         """model/trainer.py:305-307."""
@@ -242,6 +255,7 @@ class Trainer(object):
             self._release()
             raise
         self._unused_variables = unused
+        self._softmax_host = (weights.get(model_io.SOFTMAX_KERNEL), weights.get(model_io.SOFTMAX_BIAS))   # the loss layer: valid() only
         self._step = step
         self._weights_host = weights if self._range_fallback else None
         self.is_loaded = True
@@ -599,6 +613,63 @@ class Trainer(object):
             pos += t - ctx
         return res
 
+    # ------------------------------------------------------------------ Trainer.valid
+    def valid(self, data, spklist, batch_type="softmax", output_embeddings=False, aux_data=None):
+        """Evaluate on the validation set (model/trainer.py:756-884) -> (loss, embeddings or None, labels or None).
+
+        The batches are those of valid.plan_batches (KaldiDataSeqQueue with shuffle off, the length fixed at
+        (min_segment_len + max_segment_len) // 2, at most valid_max_iterations of them); every batch goes through the network to
+        the `output` endpoint and through the loss head of the checkpoint with the validation margins
+        (save_and_set_valid_loss, trainer.py:407-436; losses.valid_params).  The loss is the mean over the batches of the batch
+        mean (tf.metrics.mean of one scalar per batch).  The reference walks the same batches a second time for
+        `output_embeddings`; one walk serves both here, the wrapped duplicates of the last batches included.
+        `valid_accuracy` then holds the top-1 accuracy over all batches.  Without a checkpoint this warns and refuses: there is
+        no random initialisation here."""
+        assert batch_type == "softmax" or batch_type == "end2end", "The batch_type can only be softmax or end2end"
+        if batch_type == "end2end":
+            raise NotImplementedError("batch_type 'end2end' (KaldiDataRandomQueue, e2e_valid_loss) is not implemented")
+        if aux_data is not None:
+            raise NotImplementedError("auxiliary data directories are not implemented")
+        if not self.is_valid_built:
+            sys.exit("The graph has not been build for validation. Call build('valid') first.")
+        from . import losses
+        from . import valid as valid_mod
+        if not self.is_loaded:
+            if self.model is not None and os.path.isfile(os.path.join(self.model, "checkpoint")):
+                self.load()
+            else:
+                import warnings
+                warnings.warn("[Warning] Cannot find model in %s. The reference validates a random initialisation here; "
+                              "this implementation has none and refuses." % self.model)
+                raise RuntimeError("Cannot find model in %s: nothing to validate" % self.model)
+        kernel, bias = self._softmax_host
+        if kernel is None:
+            raise KeyError("the checkpoint holds no %s: the loss layer is needed for validation" % model_io.SOFTMAX_KERNEL)
+        self.embeddings = "output"
+        if self._head is None:
+            self._head = losses.ClassifierHead(np.asarray(kernel), None if bias is None else np.asarray(bias), self.params,
+                                               device=self._device_index)
+        step = int(self._step or 0)
+        batch_losses, correct, seen, embs, labs, cache = [], 0, 0, [], [], {}
+        for batch in valid_mod.plan_for_params(data, spklist, self.params):
+            feats = valid_mod.read_batch(batch, self.dim, cache)
+            emb = self.predict(feats)
+            res = self._head.loss(emb, batch.labels, global_step=step, validation=True)
+            batch_losses.append(res.mean)
+            correct += int(np.sum(res.top1 == batch.labels))
+            seen += len(batch.labels)
+            if output_embeddings:
+                embs.append(emb)
+                labs.append(batch.labels)
+        if not batch_losses:
+            raise ValueError("no validation batch in %s" % data)
+        self.valid_num_batches = len(batch_losses)
+        self.valid_accuracy = correct / float(seen)
+        loss = float(np.mean(np.asarray(batch_losses, dtype=np.float64)))
+        if output_embeddings:
+            return loss, np.concatenate(embs, axis=0), np.concatenate(labs, axis=0)
+        return loss, None, None
+
     # ------------------------------------------------------------------ teardown
     def _release(self):
         if self._lib is not None:
@@ -617,6 +688,7 @@ class Trainer(object):
         self._pinned = None
         self._slots = None
         self._copy_stream = None
+        self._head = None
         self.is_loaded = False
 
     def close(self):
