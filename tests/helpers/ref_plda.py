@@ -70,6 +70,17 @@ def llr_gaussian(psi, e, n, t):
     return out
 
 
+def score_bar(a, b, rho, tau=None):
+    """The derived bar of one GPU score s = sum_k a_ik b_jk + rho_i + tau_j (tests/test_gpu_plda.py has the derivation) from
+    the packed fp32 operands a [n, K], b [m, K] and the biases rho [n], tau [m] (None: 0) as the device holds them ->
+    (K, (K + 8) u sum_k |a_ik b_jk| [n, m], 4 u (|rho_i| + |tau_j|) [n, m]); the caller adds 4 u |s_ref|."""
+    a, b = np.abs(np.asarray(a, np.float64)), np.abs(np.asarray(b, np.float64))
+    k = a.shape[1]
+    rho = np.abs(np.asarray(rho, np.float64))
+    tau = np.zeros(b.shape[0]) if tau is None else np.abs(np.asarray(tau, np.float64))
+    return k, (k + 8) * U * (a @ b.T), 4 * U * (rho[:, None] + tau[None, :])
+
+
 def smooth(mean, transform, psi, factor):
     """ivector-copy-plda --smoothing: within-class covariance I -> w = 1 + factor psi; psi / w, diag(w^-1/2) transform."""
     w = 1.0 + factor * np.asarray(psi, np.float64)

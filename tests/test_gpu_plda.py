@@ -54,11 +54,8 @@ def _counts(rng, kind, n):
 def _bar(e, t, psi=None):
     """The bar above for every pair of an (enroll, test) pair of PldaRows, from the device's packed operands."""
     k = e.k
-    a = np.abs(e.packed.cpu().numpy().astype(np.float64)[:, :k])
-    b = np.abs(t.packed.cpu().numpy().astype(np.float64)[:, :k])
-    rho = np.abs(e.bias.cpu().numpy().astype(np.float64))
-    tau = np.zeros(len(t)) if e.uniform_n is None else np.abs(t.tau(e.uniform_n).cpu().numpy().astype(np.float64))
-    return k, (k + 8) * U * (a @ b.T), 4 * U * (rho[:, None] + tau[None, :])
+    tau = None if e.uniform_n is None else t.tau(e.uniform_n).cpu().numpy()
+    return ref_plda.score_bar(e.packed.cpu().numpy()[:, :k], t.packed.cpu().numpy()[:, :k], e.bias.cpu().numpy(), tau)
 
 
 def _oracle(model, e, t):
