@@ -288,6 +288,47 @@ int xv_mfcc_compute(xv_mfcc* m, const int16_t* wave_dev, const int64_t* sample_o
 int xv_vad_energy(int device, const float* feats_dev, int64_t ld, const int32_t* frame_offsets_dev, int batch, float threshold,
                   float mean_scale, int context, float proportion, float* vad_dev, void* stream);
 
+/* ---- Fbank features on the GPU (csrc/mfcc.hip): steps/make_fbank.sh --fbank-config conf/fbank.conf of the ResNet recipe
+ * (egs/voxceleb/v3/run.sh:54), Kaldi's compute-fbank-feats as published; written out in the header of csrc/mfcc.hip next to the
+ * MFCC, **parity unpinned**.  The frame fields mean what they mean in xv_mfcc_opts and the same values are refused, with the
+ * same messages. */
+typedef struct {
+  int32_t struct_size;             /* sizeof(xv_fbank_opts)                        */
+  float sample_frequency;          /* --sample-frequency          16000            */
+  float frame_length_ms;           /* --frame-length              25               */
+  float frame_shift_ms;            /* --frame-shift               10               */
+  float preemphasis_coefficient;   /* --preemphasis-coefficient   0.97             */
+  int32_t remove_dc_offset;        /* --remove-dc-offset          1                */
+  int32_t window_type;             /* --window-type               XV_WINDOW_POVEY  */
+  int32_t round_to_power_of_two;   /* --round-to-power-of-two     1                */
+  int32_t snip_edges;              /* --snip-edges                1                */
+  float dither;                    /* --dither                    0 (Kaldi: 1.0)   */
+  int32_t num_mel_bins;            /* --num-mel-bins              23 (3..64)       */
+  float low_freq;                  /* --low-freq                  20               */
+  float high_freq;                 /* --high-freq                 0 (<= 0: Nyquist + value) */
+  int32_t use_energy;              /* --use-energy                0                */
+  float energy_floor;              /* --energy-floor              0                */
+  int32_t raw_energy;              /* --raw-energy                1                */
+  int32_t htk_compat;              /* --htk-compat                0 (1 is refused) */
+  int32_t use_log_fbank;           /* --use-log-fbank             1                */
+  int32_t use_power;               /* --use-power                 1                */
+} xv_fbank_opts;
+typedef struct xv_fbank xv_fbank;
+/* xv_fbank_create / xv_fbank_destroy: the tables of one option set on `device`.  Option checks come before the first HIP call.
+ * xv_fbank_num_frames: as xv_mfcc_num_frames.  xv_fbank_num_feats: num_mel_bins + use_energy.
+ * xv_fbank_compute = `compute-fbank-feats`: operands as for xv_mfcc_compute.  Writes the num_feats features of frame t of
+ *   utterance b to feats_dev[(frame_offsets[b] + t) * ld .. ], ld >= num_feats (column 0 is the log energy with use_energy);
+ *   other columns are left alone.  log_energy_dev may be NULL; otherwise log_energy_dev[frame_offsets[b] + t] receives the
+ *   frame's log energy under raw_energy and energy_floor, whatever use_energy says: the bits xv_mfcc_compute puts in
+ *   coefficient 0 with use_energy and the same frame, raw_energy and energy_floor fields, so xv_vad_energy (ld = 1) decides on
+ *   it as it does on an MFCC file.  fp32, no atomics: repeated runs are bit-identical. */
+int xv_fbank_create(const xv_fbank_opts* opts, int device, xv_fbank** out);
+void xv_fbank_destroy(xv_fbank* m);
+int64_t xv_fbank_num_frames(const xv_fbank* m, int64_t num_samples);
+int xv_fbank_num_feats(const xv_fbank* m);
+int xv_fbank_compute(xv_fbank* m, const int16_t* wave_dev, const int64_t* sample_offsets_dev, const int32_t* frame_offsets_dev,
+                     int batch, float* feats_dev, int64_t ld, float* log_energy_dev, void* stream);
+
 /* ---- post-step on the GPU (csrc/post.hip): what the reference runs as Kaldi binaries behind extract.py
  * (egs/voxceleb/v1/nnet/run_extract_embeddings.sh:80-103).
  * xv_length_normalize = `ivector-normalize-length [--scaleup=false]` (:86,88,101): out[r] = x[r] / ratio,

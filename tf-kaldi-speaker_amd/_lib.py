@@ -31,6 +31,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_plan_create", "xv_plan_query", "xv_plan_destroy", "xv_forward", "xv_profile_begin", "xv_profile_end",
            "xv_destroy", "xv_last_error",
            "xv_frontend_cmn_select", "xv_mfcc_create", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_mfcc_compute", "xv_vad_energy",
+           "xv_fbank_create", "xv_fbank_destroy", "xv_fbank_num_frames", "xv_fbank_num_feats", "xv_fbank_compute",
            "xv_length_normalize", "xv_speaker_mean",
            "xv_score_prepare", "xv_score_matrix", "xv_score_pairs", "xv_score_histogram",
            "xv_plda_prepare", "xv_plda_matrix", "xv_plda_pairs", "xv_plda_histogram",
@@ -65,6 +66,17 @@ class MfccOpts(C.Structure):
         ("num_mel_bins", C.c_int32), ("low_freq", C.c_float), ("high_freq", C.c_float), ("num_ceps", C.c_int32),
         ("cepstral_lifter", C.c_float), ("use_energy", C.c_int32), ("energy_floor", C.c_float), ("raw_energy", C.c_int32),
         ("htk_compat", C.c_int32),
+    ]
+
+
+class FbankOpts(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("sample_frequency", C.c_float), ("frame_length_ms", C.c_float),
+        ("frame_shift_ms", C.c_float), ("preemphasis_coefficient", C.c_float), ("remove_dc_offset", C.c_int32),
+        ("window_type", C.c_int32), ("round_to_power_of_two", C.c_int32), ("snip_edges", C.c_int32), ("dither", C.c_float),
+        ("num_mel_bins", C.c_int32), ("low_freq", C.c_float), ("high_freq", C.c_float), ("use_energy", C.c_int32),
+        ("energy_floor", C.c_float), ("raw_energy", C.c_int32), ("htk_compat", C.c_int32), ("use_log_fbank", C.c_int32),
+        ("use_power", C.c_int32),
     ]
 
 
@@ -130,6 +142,13 @@ def load():
     lib.xv_mfcc_num_frames.restype = i64
     lib.xv_mfcc_compute.argtypes = [vp, vp, vp, vp, i32, vp, i64, vp]
     lib.xv_vad_energy.argtypes = [i32, vp, i64, vp, i32, C.c_float, C.c_float, i32, C.c_float, vp, vp]
+    lib.xv_fbank_create.argtypes = [C.POINTER(FbankOpts), i32, C.POINTER(vp)]
+    lib.xv_fbank_destroy.argtypes = [vp]
+    lib.xv_fbank_destroy.restype = None
+    lib.xv_fbank_num_frames.argtypes = [vp, i64]
+    lib.xv_fbank_num_frames.restype = i64
+    lib.xv_fbank_num_feats.argtypes = [vp]
+    lib.xv_fbank_compute.argtypes = [vp, vp, vp, vp, i32, vp, i64, vp, vp]
     lib.xv_length_normalize.argtypes = [i32, vp, i64, i64, i32, i32, vp, i64, vp]
     lib.xv_speaker_mean.argtypes = [i32, vp, i64, i32, vp, vp, i64, vp, i64, vp]
     lib.xv_score_prepare.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, i32, i32, i32, C.c_float, vp, i64, vp]
@@ -172,7 +191,7 @@ def load():
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
                      "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames"):
+                     "xv_loss_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

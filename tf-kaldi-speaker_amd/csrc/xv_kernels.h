@@ -220,6 +220,14 @@ hipError_t launch_mfcc(xv_mfcc* m, const int16_t* wave, const int64_t* sample_of
                        int64_t ld, hipStream_t s);
 hipError_t launch_vad_energy(const float* feats, int64_t ld, const int32_t* frame_off, int B, float threshold, float mean_scale,
                              int context, float proportion, float* vad, hipStream_t s);
+// fbank (csrc/mfcc.hip, next to the MFCC it shares its frame steps with); log_energy may be null
+int fbank_create(const xv_fbank_opts* opts, int device, xv_fbank** out, std::string* err);
+void fbank_destroy(xv_fbank* m);
+int fbank_num_frames(const xv_fbank* m, int64_t num_samples, int64_t* out);
+int fbank_device(const xv_fbank* m);
+int fbank_num_feats(const xv_fbank* m);
+hipError_t launch_fbank(xv_fbank* m, const int16_t* wave, const int64_t* sample_off, const int32_t* frame_off, int B, float* out,
+                        int64_t ld, float* log_energy, hipStream_t s);
 
 // post-step (csrc/post.hip): ivector-normalize-length / ivector-mean of run_extract_embeddings.sh:80-103
 hipError_t launch_length_norm(const float* x, int64_t ldx, int64_t rows, int dim, int scaleup, float* y, int64_t ldy,

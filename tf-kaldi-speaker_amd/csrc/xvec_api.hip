@@ -2159,6 +2159,41 @@ int xv_vad_energy(int device, const float* feats_dev, int64_t ld, const int32_t*
   return XV_OK;
 }
 
+int xv_fbank_create(const xv_fbank_opts* opts, int device, xv_fbank** out) {
+  if (!opts || !out) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_create: null pointer");
+  *out = nullptr;
+  std::string err;
+  const int rc = fbank_create(opts, device, out, &err);
+  if (rc != XV_OK) return fail(nullptr, rc, "xv_fbank_create: %s", err.c_str());
+  return XV_OK;
+}
+
+void xv_fbank_destroy(xv_fbank* m) { fbank_destroy(m); }
+
+int64_t xv_fbank_num_frames(const xv_fbank* m, int64_t num_samples) {
+  int64_t t = 0;
+  if (!m || fbank_num_frames(m, num_samples, &t) != 0) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_num_frames: bad argument");
+  return t;
+}
+
+int xv_fbank_num_feats(const xv_fbank* m) {
+  if (!m) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_num_feats: null pointer");
+  return fbank_num_feats(m);
+}
+
+int xv_fbank_compute(xv_fbank* m, const int16_t* wave_dev, const int64_t* sample_offsets_dev, const int32_t* frame_offsets_dev,
+                     int batch, float* feats_dev, int64_t ld, float* log_energy_dev, void* stream) {
+  if (!m || !wave_dev || !sample_offsets_dev || !frame_offsets_dev || !feats_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_fbank_compute: null pointer");
+  if (batch < 1 || ld < fbank_num_feats(m)) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_compute: bad dimensions (batch >= 1, ld >= num_feats)");
+  DeviceGuard g(fbank_device(m));
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", fbank_device(m));
+  const hipError_t e = launch_fbank(m, wave_dev, sample_offsets_dev, frame_offsets_dev, batch, feats_dev, ld, log_energy_dev,
+                                    static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "fbank launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 int xv_length_normalize(int device, const float* x_dev, int64_t ldx, int64_t rows, int dim, int scaleup, float* out_dev,
                         int64_t ldo, void* stream) {
   if (!x_dev || !out_dev) return fail(nullptr, XV_ERR_INVALID, "xv_length_normalize: null pointer");

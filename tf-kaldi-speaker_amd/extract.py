@@ -61,6 +61,10 @@ def build_parser():
                              "computed on the GPU and handed to the --cmn-window front-end and the network without a feature file "
                              "(extension; replaces steps/make_mfcc.sh + sid/compute_vad_decision.sh of run.sh:57-65).")
     parser.add_argument("--mfcc-config", type=str, default="", help="Kaldi conf/mfcc.conf for --wav-input.")
+    parser.add_argument("--fbank-config", type=str, default="",
+                        help="Kaldi conf/fbank.conf for --wav-input: the features are log mel filterbank energies (the ResNet recipe, "
+                             "egs/voxceleb/v3/run.sh:54) and the energy VAD is decided on the frame log energy computed with them; "
+                             "with --mfcc-config as well, on column 0 of an MFCC pass over the same samples (run.sh:58).")
     parser.add_argument("--vad-config", type=str, default="", help="Kaldi conf/vad.conf for --wav-input (default: Kaldi's defaults).")
     parser.add_argument("--channel", type=int, default=-1, help="Channel of the wav files for --wav-input (-1: they must be mono).")
     parser.add_argument("--batch-samples", type=int, default=32 << 20, help="Samples packed into one device batch with --wav-input.")
@@ -430,16 +434,22 @@ def run_native(trainer, rspecifier, writer, min_chunk_size, chunk_size, normaliz
 
 
 def run_wav(trainer, rspecifier, writer, mopts, vopts, min_chunk_size, chunk_size, normalize, batch_frames, cmn_window=0,
-            channel=-1, batch_samples=32 << 20):
+            channel=-1, batch_samples=32 << 20, fopts=None, config_names=("--mfcc-config", "--fbank-config")):
     """--wav-input: wav.scp -> MFCC -> energy VAD -> sliding CMN + voiced-frame selection -> network, one device batch of about
     batch_samples samples at a time; the features never leave the device.  Utterances without frames, and those left with fewer
-    than min_chunk_size voiced frames, are skipped as on the feature-file route."""
+    than min_chunk_size voiced frames, are skipped as on the feature-file route.
+    With fopts (FbankOptions) the features are fbank; the VAD is decided on the frame log energy of that pass, or, when mopts is
+    given too, on column 0 of an MFCC pass over the same samples (config_names: the two files, for the error message)."""
     import torch
     from .frontend import cmn_select_packed
     from .mfcc import Mfcc, read_wav_scp, vad_packed, wav_batches
     dev_index = trainer._device_index
     devname = "cuda:%d" % dev_index
-    mfcc = Mfcc(mopts, dev_index)
+    mfcc = Mfcc(mopts, dev_index) if mopts is not None else None
+    fbank = None
+    if fopts is not None:
+        from .fbank import Fbank
+        fbank = Fbank(fopts, dev_index)
     done = skipped = 0
 
     def on_error(key, e):
@@ -447,10 +457,24 @@ def run_wav(trainer, rspecifier, writer, mopts, vopts, min_chunk_size, chunk_siz
         skipped += 1
         log.warning("[WARNING] %s: %s" % (key, e))
 
-    for keys, samples, soff in wav_batches(read_wav_scp(rspecifier), mopts, batch_samples, channel, on_error):
+    for keys, samples, soff in wav_batches(read_wav_scp(rspecifier), fopts or mopts, batch_samples, channel, on_error):
         with torch.cuda.device(dev_index):
-            raw, foff = mfcc.compute(torch.from_numpy(samples).to(devname), soff)
-            vad = vad_packed(raw, foff, vopts).cpu().numpy()
+            wave_dev = torch.from_numpy(samples).to(devname)
+            if fbank is None:
+                raw, foff = mfcc.compute(wave_dev, soff)
+                vad = vad_packed(raw, foff, vopts).cpu().numpy()
+            elif mfcc is None:
+                raw, foff, energy = fbank.compute(wave_dev, soff, energy=True)
+                vad = vad_packed(energy.view(-1, 1), foff, vopts).cpu().numpy()
+            else:
+                raw, foff = fbank.compute(wave_dev, soff)
+                c0, moff = mfcc.compute(wave_dev, soff)
+                differ = np.flatnonzero(np.diff(foff) != np.diff(moff))
+                if differ.size:
+                    i = int(differ[0])
+                    sys.exit("--wav-input: %s has %d frames with %s and %d with %s: the VAD of one does not fit the features of the other"
+                             % (keys[i], foff[i + 1] - foff[i], config_names[1], moff[i + 1] - moff[i], config_names[0]))
+                vad = vad_packed(c0, moff, vopts).cpu().numpy()
             vads = [vad[foff[i]:foff[i + 1]] for i in range(len(keys))]
             dev, offsets, kept = cmn_select_packed(raw, foff, vads, cmn_window=cmn_window, min_frames=min_chunk_size)
         skipped += len(keys) - len(kept)
@@ -472,7 +496,10 @@ def run_wav(trainer, rspecifier, writer, mopts, vopts, min_chunk_size, chunk_siz
             emb = emb / np.sqrt(np.sum(np.square(emb), axis=1, keepdims=True))
         writer.write(keys, emb)
         done += len(keys)
-    mfcc.close()
+    if mfcc is not None:
+        mfcc.close()
+    if fbank is not None:
+        fbank.close()
     return done, skipped
 
 
@@ -498,22 +525,32 @@ def main(argv=None):
         dim = int(f.readline().strip())
 
     spec = args.rspecifier.strip()
-    mopts = vopts = None
+    mopts = vopts = fopts = None
     if args.wav_input:
         from .mfcc import MfccOptions, VadOptions
         if not spec.startswith("scp:"):
             sys.exit("--wav-input: the rspecifier must be scp:wav.scp")
-        if not args.mfcc_config or args.vad_rspecifier:
-            sys.exit("--wav-input needs --mfcc-config and computes its own VAD (no --vad-rspecifier)")
+        if not (args.mfcc_config or args.fbank_config) or args.vad_rspecifier:
+            sys.exit("--wav-input needs --mfcc-config or --fbank-config and computes its own VAD (no --vad-rspecifier)")
         try:
-            mopts = MfccOptions.from_config(args.mfcc_config)
+            if args.mfcc_config:
+                mopts = MfccOptions.from_config(args.mfcc_config)
+            if args.fbank_config:
+                from .fbank import FbankOptions
+                fopts = FbankOptions.from_config(args.fbank_config)
             vopts = VadOptions.from_config(args.vad_config) if args.vad_config else VadOptions()
         except ValueError as e:
             sys.exit("--wav-input: %s" % e)
-        if mopts.num_ceps < dim:
+        if fopts is not None:
+            if fopts.num_feats != dim:
+                sys.exit("--wav-input: the model expects %d features, %s gives %d" % (dim, args.fbank_config, fopts.num_feats))
+            if mopts is not None and mopts.sample_frequency != fopts.sample_frequency:
+                sys.exit("--wav-input: --sample-frequency is %g in %s and %g in %s" % (fopts.sample_frequency, args.fbank_config,
+                                                                                     mopts.sample_frequency, args.mfcc_config))
+        elif mopts.num_ceps < dim:
             sys.exit("--wav-input: the model expects %d features, %s gives %d" % (dim, args.mfcc_config, mopts.num_ceps))
-    elif args.mfcc_config or args.vad_config:
-        sys.exit("--mfcc-config / --vad-config go with --wav-input")
+    elif args.mfcc_config or args.fbank_config or args.vad_config:
+        sys.exit("--mfcc-config / --fbank-config / --vad-config go with --wav-input")
     elif spec.rsplit(".", 1)[-1] == "scp" and not (args.scp_input and spec.startswith(("scp:", "scp,"))):   # extract.py:59-61
         sys.exit("The rspecifier must be ark or input pipe")
 
@@ -539,7 +576,8 @@ def main(argv=None):
     t_loop = time.perf_counter()
     if args.wav_input:
         done, skipped = run_wav(trainer, args.rspecifier, writer, mopts, vopts, args.min_chunk_size, args.chunk_size,
-                                args.normalize, args.batch_frames, args.cmn_window, args.channel, args.batch_samples)
+                                args.normalize, args.batch_frames, args.cmn_window, args.channel, args.batch_samples,
+                                fopts, (args.mfcc_config, args.fbank_config))
     elif native:
         done, skipped = run_native(trainer, args.rspecifier, writer, args.min_chunk_size, args.chunk_size,
                                    args.normalize, args.batch_frames, args.cmn_window, args.vad_rspecifier)

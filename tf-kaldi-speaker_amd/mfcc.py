@@ -84,17 +84,18 @@ class _Options(object):
         return {k: getattr(self, k) for k in self.FIELDS}
 
 
-class MfccOptions(_Options):
-    FIELDS = {
-        "sample_frequency": (float, 16000.0), "frame_length": (float, 25.0), "frame_shift": (float, 10.0),
-        "preemphasis_coefficient": (float, 0.97), "remove_dc_offset": (bool, True), "window_type": (str, "povey"),
-        "round_to_power_of_two": (bool, True), "snip_edges": (bool, True), "dither": (float, 0.0),
-        "num_mel_bins": (int, 23), "low_freq": (float, 20.0), "high_freq": (float, 0.0), "num_ceps": (int, 13),
-        "cepstral_lifter": (float, 22.0), "use_energy": (bool, True), "energy_floor": (float, 0.0), "raw_energy": (bool, True),
-        "htk_compat": (bool, False),
-    }
+FRAME_FIELDS = {
+    "sample_frequency": (float, 16000.0), "frame_length": (float, 25.0), "frame_shift": (float, 10.0),
+    "preemphasis_coefficient": (float, 0.97), "remove_dc_offset": (bool, True), "window_type": (str, "povey"),
+    "round_to_power_of_two": (bool, True), "snip_edges": (bool, True), "dither": (float, 0.0),
+}
 
-    def validate(self):
+
+class FrameOptions(_Options):
+    """The frame options and geometry compute-mfcc-feats and compute-fbank-feats share (FRAME_FIELDS plus num_mel_bins and
+    htk_compat in the subclass's FIELDS)."""
+
+    def validate_frame(self):
         if self.dither != 0.0:
             raise ValueError("--dither=%g is not supported: random dither (Kaldi's default 1.0) is not implemented; "
                              "features here are deterministic, use --dither=0" % self.dither)
@@ -104,8 +105,8 @@ class MfccOptions(_Options):
             raise ValueError("--window-type must be one of %s" % ", ".join(WINDOW_TYPES))
         if not self.round_to_power_of_two:
             raise ValueError("--round-to-power-of-two=false is not supported")
-        if self.num_ceps > self.num_mel_bins:
-            raise ValueError("--num-ceps=%d exceeds --num-mel-bins=%d" % (self.num_ceps, self.num_mel_bins))
+
+    def validate_sizes(self):
         if self.num_mel_bins > 64:
             raise ValueError("--num-mel-bins above 64 is not supported")
         if self.padded_length not in (256, 512):
@@ -137,14 +138,31 @@ class MfccOptions(_Options):
         n, s = self.frame_samples, self.shift_samples
         return t * s + (0 if self.snip_edges else s // 2 - n // 2)
 
-    def c_struct(self):
-        o = _lib.MfccOpts()
-        o.struct_size = C.sizeof(_lib.MfccOpts)
+    def frame_fields_into(self, o):
         o.sample_frequency, o.frame_length_ms, o.frame_shift_ms = self.sample_frequency, self.frame_length, self.frame_shift
         o.preemphasis_coefficient = self.preemphasis_coefficient
         o.remove_dc_offset = int(self.remove_dc_offset)
         o.window_type = WINDOW_TYPES.index(self.window_type)
         o.round_to_power_of_two, o.snip_edges, o.dither = int(self.round_to_power_of_two), int(self.snip_edges), self.dither
+
+
+class MfccOptions(FrameOptions):
+    FIELDS = dict(FRAME_FIELDS, **{
+        "num_mel_bins": (int, 23), "low_freq": (float, 20.0), "high_freq": (float, 0.0), "num_ceps": (int, 13),
+        "cepstral_lifter": (float, 22.0), "use_energy": (bool, True), "energy_floor": (float, 0.0), "raw_energy": (bool, True),
+        "htk_compat": (bool, False),
+    })
+
+    def validate(self):
+        self.validate_frame()
+        if self.num_ceps > self.num_mel_bins:
+            raise ValueError("--num-ceps=%d exceeds --num-mel-bins=%d" % (self.num_ceps, self.num_mel_bins))
+        self.validate_sizes()
+
+    def c_struct(self):
+        o = _lib.MfccOpts()
+        o.struct_size = C.sizeof(_lib.MfccOpts)
+        self.frame_fields_into(o)
         o.num_mel_bins, o.low_freq, o.high_freq, o.num_ceps = self.num_mel_bins, self.low_freq, self.high_freq, self.num_ceps
         o.cepstral_lifter, o.use_energy, o.energy_floor = self.cepstral_lifter, int(self.use_energy), self.energy_floor
         o.raw_energy, o.htk_compat = int(self.raw_energy), int(self.htk_compat)
@@ -229,6 +247,23 @@ def read_wav_scp(path):
 
 
 # ------------------------------------------------------------------------------------------------------------ device
+def packed_offsets(opts, wave_dev, sample_offsets):
+    """Checks a packed batch (wave_dev: CUDA int16 [samples], sample_offsets: B+1 offsets) against the frame options `opts`.
+    Returns (int64 sample offsets, int32 frame offsets [B+1])."""
+    import torch
+    sample_offsets = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+    B = len(sample_offsets) - 1
+    if wave_dev.dtype != torch.int16 or not wave_dev.is_contiguous() or wave_dev.dim() != 1:
+        raise ValueError("wave_dev must be a contiguous 1-D int16 tensor")
+    if B < 0 or sample_offsets[0] != 0 or (np.diff(sample_offsets) < 0).any() or sample_offsets[-1] != wave_dev.shape[0]:
+        raise ValueError("sample_offsets must rise from 0 to the number of samples")
+    counts = [opts.num_frames(int(n)) for n in np.diff(sample_offsets)]
+    total = int(np.sum(counts, dtype=np.int64)) if counts else 0
+    if total + B >= 2 ** 31:
+        raise ValueError("batch of %d frames is too large: split it" % total)
+    return sample_offsets, np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+
+
 class Mfcc(object):
     """Tables of one option set on one device (xv_mfcc of include/xvec_hip.h)."""
 
@@ -251,17 +286,8 @@ class Mfcc(object):
         """wave_dev: CUDA int16 [samples] (B utterances back to back); sample_offsets: B+1 offsets.
         Returns (CUDA float32 [frames, ld], int32 frame offsets [B+1])."""
         import torch
-        sample_offsets = np.ascontiguousarray(sample_offsets, dtype=np.int64)
-        B = len(sample_offsets) - 1
-        if wave_dev.dtype != torch.int16 or not wave_dev.is_contiguous() or wave_dev.dim() != 1:
-            raise ValueError("wave_dev must be a contiguous 1-D int16 tensor")
-        if B < 0 or sample_offsets[0] != 0 or (np.diff(sample_offsets) < 0).any() or sample_offsets[-1] != wave_dev.shape[0]:
-            raise ValueError("sample_offsets must rise from 0 to the number of samples")
-        counts = [self.opts.num_frames(int(n)) for n in np.diff(sample_offsets)]
-        total = int(np.sum(counts, dtype=np.int64)) if counts else 0
-        if total + B >= 2 ** 31:
-            raise ValueError("batch of %d frames is too large: split it" % total)
-        frame_offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        sample_offsets, frame_offsets = packed_offsets(self.opts, wave_dev, sample_offsets)
+        B, total = len(sample_offsets) - 1, int(frame_offsets[-1])
         ld = int(ld or self.opts.num_ceps)
         if ld < self.opts.num_ceps:
             raise ValueError("ld %d is smaller than num_ceps %d" % (ld, self.opts.num_ceps))

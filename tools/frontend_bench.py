@@ -4,8 +4,11 @@
   end2end    wav samples on the host -> MFCC -> VAD -> sliding CMN + voiced-frame selection -> x-vector network
 8192 utterances with lengths drawn from U[2 s, 10 s], voxceleb options.  Prints one JSON line; results are kept in
 profiles/frontend.md beside the extractor's own rate.
+  --fbank    adds, on the same utterances and in the same run, fbank (the options of tests/golden/fbank_v3.conf) + energy VAD
+             decided on the kernel's side energy, and its float64 oracle (tests/helpers/ref_fbank.py) on one core;
+             --skip-end2end leaves the network leg out.
 
-    python tools/frontend_bench.py [--utts 8192] [--batch-utts 1024] [--precision f16f6] [--oracle-utts 16]"""
+    python tools/frontend_bench.py [--utts 8192] [--batch-utts 1024] [--precision f16f6] [--oracle-utts 16] [--fbank]"""
 import argparse
 import json
 import os
@@ -26,6 +29,8 @@ def main():
     ap.add_argument("--oracle-utts", type=int, default=16)
     ap.add_argument("--precision", type=str, default="")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--fbank", action="store_true")
+    ap.add_argument("--skip-end2end", action="store_true")
     args = ap.parse_args()
     import torch
     import ref_mfcc
@@ -66,6 +71,36 @@ def main():
         torch.cuda.synchronize()
         best = min(best, time.perf_counter() - t0)
     gpu_fps = frames / best
+    result = {}
+    if args.fbank:
+        import ref_fbank
+        from tf_kaldi_speaker_amd import fbank as F
+        fopts = F.FbankOptions.from_config(os.path.join(ROOT, "tests", "golden", "fbank_v3.conf"))
+        fb = F.Fbank(fopts, 0)
+        fframes = sum(fopts.num_frames(int(n)) for n in lens)
+
+        def front_fbank(dev_batches):
+            for w, off in dev_batches:
+                _, foff, energy = fb.compute(w, off, energy=True)
+                M.vad_packed(energy.view(-1, 1), foff, vopts)
+
+        front_fbank(dev_batches[:1])
+        torch.cuda.synchronize()
+        fbest = 1e30
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            front_fbank(dev_batches)
+            torch.cuda.synchronize()
+            fbest = min(fbest, time.perf_counter() - t0)
+        fb.close()
+        t0 = time.perf_counter()
+        or_frames = 0
+        for s, n in zip(starts[:min(args.oracle_utts, args.utts)], lens[:args.oracle_utts]):
+            f, e = ref_fbank.fbank(pool[s:s + n], ref_fbank.V3)
+            ref_mfcc.vad(e[:, None], ref_mfcc.VAD_VOXCELEB)
+            or_frames += f.shape[0]
+        result.update({"fbank_frames": int(fframes), "gpu_fbank_vad_frames_per_s": fframes / fbest, "gpu_fbank_vad_s": fbest,
+                       "fbank_oracle_one_core_frames_per_s": or_frames / (time.perf_counter() - t0)})
     del dev_batches
 
     n_or = min(args.oracle_utts, args.utts)
@@ -77,6 +112,13 @@ def main():
         or_frames += f.shape[0]
     oracle_fps = or_frames / (time.perf_counter() - t0)
 
+    result.update({"utts": int(args.utts), "frames": int(frames), "audio_hours": float(lens.sum() / fs / 3600.0),
+                   "gpu_mfcc_vad_frames_per_s": gpu_fps, "gpu_mfcc_vad_s": best,
+                   "oracle_one_core_frames_per_s": oracle_fps, "oracle_utts": int(n_or)})
+    if args.skip_end2end:
+        mf.close()
+        print(json.dumps(result))
+        return
     params = Params(**dict(synth.TDNN_STAT_PARAMS))
     tr = Trainer(params, None, 30, single_cpu=True, device=0, precision=args.precision or None)
     tr.build("predict")
@@ -101,11 +143,9 @@ def main():
         best2 = min(best2, time.perf_counter() - t0)
     tr.close()
     mf.close()
-    print(json.dumps({"utts": int(args.utts), "frames": int(frames), "audio_hours": float(lens.sum() / fs / 3600.0),
-                      "gpu_mfcc_vad_frames_per_s": gpu_fps, "gpu_mfcc_vad_s": best,
-                      "oracle_one_core_frames_per_s": oracle_fps, "oracle_utts": int(n_or),
-                      "end2end_frames_per_s": frames / best2, "end2end_s": best2, "voiced_fraction": kept_frames / float(frames),
-                      "precision": args.precision or "default"}))
+    result.update({"end2end_frames_per_s": frames / best2, "end2end_s": best2, "voiced_fraction": kept_frames / float(frames),
+                   "precision": args.precision or "default"})
+    print(json.dumps(result))
 
 
 if __name__ == "__main__":
