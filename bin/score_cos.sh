@@ -8,6 +8,10 @@ mean=
 transform=
 normalize=true
 eer=false
+cohort=
+norm=
+top_k=
+exclude_utt2spk=
 
 if [ -f path.sh ]; then . ./path.sh; fi
 if [ -f parse_options.sh ] || command -v parse_options.sh >/dev/null 2>&1; then
@@ -30,6 +34,10 @@ if [ $# != 4 ]; then
   echo "  --transform <transform.mat>"
   echo "  --normalize <true>"
   echo "  --eer <false>"
+  echo "  --cohort <cohort-rspecifier>        # score normalisation; the three below need it"
+  echo "  --norm <s>                          # z, t or s"
+  echo "  --top-k <0>                         # adaptive cohort size; 0: the whole cohort"
+  echo "  --exclude-utt2spk <utt2spk>"
   echo ""
   exit 100
 fi
@@ -38,6 +46,10 @@ opts=
 if [ -n "$mean" ]; then opts="$opts --mean $mean"; fi
 if [ -n "$transform" ]; then opts="$opts --transform $transform"; fi
 if $eer; then opts="$opts --eer"; fi
+if [ -n "$cohort" ]; then opts="$opts --cohort $cohort"; fi
+if [ -n "$norm" ]; then opts="$opts --norm $norm"; fi
+if [ -n "$top_k" ]; then opts="$opts --top-k $top_k"; fi
+if [ -n "$exclude_utt2spk" ]; then opts="$opts --exclude-utt2spk $exclude_utt2spk"; fi
 
 here=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export PYTHONPATH=$here:$PYTHONPATH

@@ -14,6 +14,10 @@ num_utts=
 smoothing=0.0
 eer=false
 min_dcf=
+cohort=
+norm=
+top_k=
+exclude_utt2spk=
 
 if [ -f path.sh ]; then . ./path.sh; fi
 if [ -f parse_options.sh ] || command -v parse_options.sh >/dev/null 2>&1; then
@@ -41,6 +45,10 @@ if [ $# != 5 ]; then
   echo "  --smoothing <0.0>"
   echo "  --eer <false>"
   echo "  --min-dcf <p_target[,c_miss[,c_fa]]>"
+  echo "  --cohort <cohort-rspecifier>        # score normalisation; the three below need it"
+  echo "  --norm <s>                          # z, t or s"
+  echo "  --top-k <0>                         # adaptive cohort size; 0: the whole cohort"
+  echo "  --exclude-utt2spk <utt2spk>"
   echo ""
   exit 100
 fi
@@ -51,6 +59,10 @@ if [ -n "$transform" ]; then opts="$opts --transform $transform"; fi
 if [ -n "$num_utts" ]; then opts="$opts --num-utts $num_utts"; fi
 if [ -n "$min_dcf" ]; then opts="$opts --min-dcf $min_dcf"; fi
 if $eer; then opts="$opts --eer"; fi
+if [ -n "$cohort" ]; then opts="$opts --cohort $cohort"; fi
+if [ -n "$norm" ]; then opts="$opts --norm $norm"; fi
+if [ -n "$top_k" ]; then opts="$opts --top-k $top_k"; fi
+if [ -n "$exclude_utt2spk" ]; then opts="$opts --exclude-utt2spk $exclude_utt2spk"; fi
 
 here=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export PYTHONPATH=$here:$PYTHONPATH

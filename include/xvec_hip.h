@@ -409,6 +409,44 @@ int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, co
                       const float* b_dev, int64_t ldb, int64_t m, const float* tau_dev, const int32_t* labels_b_dev, int k, double lo,
                       double hi, int nbins, uint64_t* hist_same_dev, uint64_t* hist_diff_dev, void* stream);
 
+/* ---- score normalisation on the GPU (csrc/score.hip): Z/T/S-norm with adaptive top-K cohorts.  The reference has no such step
+ * (egs/sre/v1/run.sh:13, "In the future, we will add score-normalization"), so this is **parity unpinned**; the oracle is
+ * tests/helpers/ref_snorm.py.  Definitions:
+ *   e is an enrolment row and t is a test row.  The cohort has rows c_1..c_m.
+ *   score() is either the cosine of prepared rows or the PLDA log likelihood ratio.
+ *   S_e = { score(e, c_j) }: for PLDA the cohort stands on the *test* side.
+ *   S_t = { score(c_j, t) }: for PLDA the cohort stands on the *enrolment* side, num_utts 1.
+ *   top_K(S) is the K largest values of S, with multiplicity.  Ties at the boundary are harmless, because equal values
+ *   contribute equally.  mu(S) is the mean of top_K(S).  sigma(S) is the population standard deviation (divide by K, numpy's
+ *   default), computed centred on mu.
+ *   top_k = 0 means K = all eligible columns: plain Z-norm / T-norm.  Otherwise K_eff = min(top_k, eligible).  This is adaptive
+ *   S-norm in its "AS-norm1" form: each side picks its own top-K cohort.
+ *   z: (s - mu(S_e)) / sigma(S_e).  t: (s - mu(S_t)) / sigma(S_t).  s: (z + t) / 2.
+ *   Optional exclusion labels: a column whose label equals the row's label is not eligible.  Use this when the cohort is drawn
+ *   from the set being scored, or holds the same speaker.
+ *   If K_eff = 0, mean and std are NaN.  If K_eff = 1, or all selected values are equal, std is exactly 0.  This is why the
+ *   variance is taken centred (two-pass), not as E[s^2] - E[s]^2.
+ *   AS-norm2 (cohort chosen by the other side of the trial) is out of scope and is not offered.
+ * xv_cohort_stats = per row i of a [n, k]: mean_dev[i] = mu, std_dev[i] = sigma and count_dev[i] = K_eff (count_dev may be NULL) of
+ *   the scores a[i] . b[j] + row_bias[i] + col_bias[j] against the m rows of b [m, k] (either bias NULL: 0).  One entry point
+ *   serves cosine (no biases) and PLDA (the operands of xv_plda_matrix); the form is symmetric in its two sides, so the statistics
+ *   per test row over cohort enrolments are the same call with the operands swapped.  Every score is produced by the tile kernel
+ *   of xv_score_matrix / xv_plda_matrix and is bit-identical to what those calls write for the same operand order (the biases
+ *   are added as (a . b + row_bias) + col_bias).  Selection is an exact radix select per row (no sampling); mean and centred sum
+ *   of squares are accumulated in double in a fixed order without floating-point atomics and rounded once: repeats are
+ *   bit-identical.  labels_a_dev [n] / labels_b_dev [m] are both NULL (no exclusion) or both given.
+ *   The scores pass through ws_dev in panels of whole 128-row tile rows; xv_cohort_stats_workspace(n, m, top_k) is the least
+ *   ws_bytes (one 128-row panel of m scores, rows padded to 4 floats) and XV_ERR_WORKSPACE is returned below it.  The result is
+ *   bit-identical for every legal ws_bytes: more workspace only means more rows per launch.
+ *   1 <= k <= 2048 (XV_ERR_UNSUPPORTED otherwise), 0 <= top_k <= m, m < 2^31, n < 2^31 (XV_ERR_INVALID otherwise); all argument
+ *   checks come before the first HIP call.  n = 0 returns XV_OK and touches nothing. */
+int64_t xv_cohort_stats_workspace(int64_t n, int64_t m, int top_k);
+int xv_cohort_stats(int device, const float* a_dev, int64_t lda, int64_t n, const float* row_bias_dev /* NULL: 0 */,
+                    const int32_t* labels_a_dev /* NULL: no exclusion */, const float* b_dev, int64_t ldb, int64_t m,
+                    const float* col_bias_dev /* NULL: 0 */, const int32_t* labels_b_dev, int k, int top_k,
+                    float* mean_dev, float* std_dev, int32_t* count_dev /* K_eff per row; may be NULL */,
+                    void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- classifier-head validation loss on the GPU (csrc/loss.hip): what Trainer.valid evaluates per batch
  * (model/trainer.py:756-884), loss_i = logsumexp_c(z_ic) - z_i,label as tf.losses.sparse_softmax_cross_entropy takes it, without
  * ever writing the [n, C] logits.  Products are exact fp32 with fp32 accumulation (the tile arithmetic of the scoring calls);

@@ -43,6 +43,17 @@
 //    in double so that rows of any fp32 magnitude neither overflow nor flush and a zero row stays zero; then the packed operand
 //    y_d p_d (and the second half, W_d on the enrolment side or y_d^2 on the test side, for sets of mixed n) and the bias
 //    logdet + sum_d q_d y_d^2.  The per-n vectors inv, p, q, w come from the host in float64, one table per distinct n.
+//
+// Score normalisation (Z/T/S-norm with adaptive top-K cohorts; include/xvec_hip.h has the definitions) is missing from the
+// reference (egs/sre/v1/run.sh:13) and from Kaldi's binaries: **parity unpinned**, checked against tests/helpers/ref_snorm.py.
+//  * launch_cohort_stats: score_tile_kernel (EPI_MATRIX, or EPI_PLDA when a bias is given) writes a panel of whole tile rows of
+//    scores into the workspace, so every score is the one xv_score_matrix / xv_plda_matrix would write; then
+//  * cohort_select_kernel: one workgroup per panel row.  Rows of up to 12288 scores are copied into LDS once and every sweep
+//    reads them there; longer rows are swept in global memory (L2).  An exact radix select on the order-preserving uint32
+//    image of the float (digits of 11, 11 and 10 bits, histograms in LDS with ds_add_u32) finds the K-th largest score and
+//    its multiplicity inside the top K; one sweep sums what lies above it, one more takes the centred squares, both in
+//    double and in a fixed order.  top_k = 0 (or K = all eligible columns) skips the select.  A fused epilogue that never
+//    writes the panel has not been built.
 #include <mutex>
 
 #include "xv_kernels.h"
@@ -435,6 +446,162 @@ __global__ __launch_bounds__(256) void plda_rows_kernel(const float* u, int64_t 
   if (bias && lane == 0) bias[r] = (float)((logdet ? logdet[k] : 0.0) + acc);
 }
 
+// ---------------------------------------------------------------------------------------------- cohort statistics
+constexpr int kSelBins = 2048;                // digit histogram of the radix select: digits of 11, 11 and 10 bits
+constexpr int kSelStageMax = 12288;           // rows of up to this many scores are kept in LDS for all sweeps (48 KB)
+constexpr size_t kSelFixedBytes = kSelBins * sizeof(unsigned) + 8 * sizeof(double) + 8 * sizeof(unsigned);
+
+// order-preserving uint32 image of a float: a < b  <=>  key(a) < key(b); -0.0 and +0.0 share the key of +0.0
+__device__ __forceinline__ unsigned score_key(float v) {
+  unsigned u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float score_unkey(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// sum over the workgroup (4 waves), the same bits in every thread and in every run: xor butterfly per wave, then the four
+// wave sums in a fixed order.  `slot` [4] is LDS of the caller; it is free again when the call returns.
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* slot) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const T r = (slot[0] + slot[1]) + (slot[2] + slot[3]);
+  __syncthreads();
+  return r;
+}
+
+// One workgroup per row of a panel of scores [rows, ldp]: mean and population standard deviation of the K largest eligible
+// scores of the row (K = top_k, or all of them for top_k == 0, capped by the number of eligible columns; a column j is
+// eligible unless la[row] == lb[j]).  Selection is an exact radix select on score_key: three digit histograms in LDS
+// (ds_add_u32; integer counts commute) fix the key T of the K-th largest score and how many copies of it belong to the
+// top K; the sums then take every score above T and that many copies of T.  Mean and centred sum of squares are
+// accumulated in double, thread-strided and combined in a fixed order, and rounded once.
+template <bool STAGE>
+__global__ __launch_bounds__(256) void cohort_select_kernel(const float* __restrict__ panel, int64_t ldp, int m,
+                                                            const int32_t* __restrict__ la, const int32_t* __restrict__ lb,
+                                                            int top_k, float* __restrict__ mean, float* __restrict__ stdv,
+                                                            int32_t* __restrict__ count) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char sel_raw[];
+  unsigned* hist = reinterpret_cast<unsigned*>(sel_raw);                 // [kSelBins]
+  double* dslot = reinterpret_cast<double*>(hist + kSelBins);            // [8]
+  unsigned* uslot = reinterpret_cast<unsigned*>(dslot + 8);              // [8]: 0-3 wave sums, 4 digit found, 5 rank left in it
+  float* stage = reinterpret_cast<float*>(uslot + 8);                    // [m] when STAGE
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t r = blockIdx.x;
+  const float* src = panel + r * ldp;
+  if (STAGE) {
+    for (int j = tid; j < m; j += 256) stage[j] = src[j];
+    __syncthreads();
+  }
+  auto val = [&](int j) { return STAGE ? stage[j] : src[j]; };
+  const bool excl = la != nullptr;
+  const int32_t mine = excl ? la[r] : 0;
+  auto eligible = [&](int j) { return !excl || lb[j] != mine; };
+
+  unsigned elig = (unsigned)m;
+  if (excl) {
+    unsigned c = 0;
+    for (int j = tid; j < m; j += 256) c += lb[j] != mine ? 1u : 0u;
+    elig = block_sum(c, uslot);
+  }
+  const unsigned K = top_k > 0 && (unsigned)top_k < elig ? (unsigned)top_k : elig;
+  if (K == 0) {                                  // uniform: nothing to take the statistics of
+    if (tid == 0) {
+      mean[r] = __builtin_nanf("");
+      stdv[r] = __builtin_nanf("");
+      if (count) count[r] = 0;
+    }
+    return;
+  }
+
+  const bool all = K == elig;
+  unsigned T = 0u, ties = 0u;                    // key of the K-th largest score; copies of it inside the top K
+  if (!all) {
+    unsigned prefix = 0u, mask = 0u, rank = K;   // the rank-th largest of the scores whose key matches prefix under mask
+#pragma unroll 1
+    for (int pass = 0; pass < 3; ++pass) {
+      const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
+      const unsigned dmask = pass == 2 ? 0x3ffu : 0x7ffu;
+      for (int i = tid; i < kSelBins; i += 256) hist[i] = 0u;
+      __syncthreads();
+      for (int j = tid; j < m; j += 256) {
+        if (!eligible(j)) continue;
+        const unsigned key = score_key(val(j));
+        if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & dmask], 1u);
+      }
+      __syncthreads();
+      // thread t owns digits 2047 - 8 t down to 2040 - 8 t; an inclusive scan over the threads walks the digits downwards
+      const int top = kSelBins - 1 - 8 * tid;
+      unsigned c[8], mysum = 0u;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        c[i] = hist[top - i];
+        mysum += c[i];
+      }
+      unsigned incl = mysum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned y = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += y;
+      }
+      if (lane == 63) uslot[wave] = incl;
+      __syncthreads();
+      for (int w = 0; w < wave; ++w) incl += uslot[w];
+      unsigned above = incl - mysum;             // matching scores in the digits above this thread's
+      if (above < rank && rank <= incl) {        // exactly one thread: the counts below rank are monotone
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if (above + c[i] >= rank) {
+            uslot[4] = (unsigned)(top - i);
+            uslot[5] = rank - above;
+            break;
+          }
+          above += c[i];
+        }
+      }
+      __syncthreads();
+      prefix |= uslot[4] << shift;
+      mask |= dmask << shift;
+      rank = uslot[5];
+    }
+    T = prefix;
+    ties = rank;
+  }
+  const double tval = (double)score_unkey(T);
+
+  double acc = 0.0;
+  for (int j = tid; j < m; j += 256) {
+    if (!eligible(j)) continue;
+    const float v = val(j);
+    if (all || score_key(v) > T) acc += (double)v;
+  }
+  double total = block_sum(acc, dslot);
+  if (!all) total += (double)ties * tval;
+  const double mu = total / (double)K;
+
+  acc = 0.0;
+  for (int j = tid; j < m; j += 256) {
+    if (!eligible(j)) continue;
+    const float v = val(j);
+    if (all || score_key(v) > T) {
+      const double dv = (double)v - mu;
+      acc = fma(dv, dv, acc);
+    }
+  }
+  double ss = block_sum(acc, dslot + 4);
+  if (!all) ss += (double)ties * ((tval - mu) * (tval - mu));
+  if (tid == 0) {
+    mean[r] = (float)mu;
+    stdv[r] = (float)sqrt(ss / (double)K);
+    if (count) count[r] = (int32_t)K;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_score_prepare_rows(const float* x, int64_t ldx, int64_t rows, int dim, const float* mean, int normalize,
@@ -561,6 +728,58 @@ hipError_t launch_plda_pairs(const float* a, int64_t lda, int n, const float* ro
   else
     hipLaunchKernelGGL((score_pairs_kernel<false, true>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, k, ia, ib, npairs, out, row_bias, col_bias);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- cohort launches
+static int64_t cohort_panel_ld(int64_t m) { return m < 4 ? 4 : (m + 3) / 4 * 4; }
+
+int64_t cohort_stats_workspace_bytes(int64_t n, int64_t m) {
+  (void)n;                                       // one panel of SBM rows serves any n; more only means fewer launches
+  return (int64_t)SBM * cohort_panel_ld(m) * (int64_t)sizeof(float);
+}
+
+hipError_t launch_cohort_stats(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
+                               int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* mean,
+                               float* stdv, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int64_t ldp = cohort_panel_ld(m);
+  int64_t prows = ws_bytes / (ldp * (int64_t)sizeof(float)) / SBM * SBM;      // whole tile rows per panel
+  const int64_t nceil = ((int64_t)n + SBM - 1) / SBM * SBM;
+  if (prows > nceil) prows = nceil;
+  if (prows < SBM) return hipErrorInvalidValue;                              // the caller checked ws_bytes
+  int cus = 0;
+  hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  float* panel = static_cast<float*>(ws);
+  const bool stage = m <= kSelStageMax;
+  const size_t sel_smem = kSelFixedBytes + (stage ? (size_t)m * sizeof(float) : 0);
+  for (int64_t r0 = 0; r0 < n; r0 += prows) {
+    const int rows = (int)(n - r0 < prows ? n - r0 : prows);
+    if (m > 0) {
+      ScoreArgs p = {};
+      p.A = a + r0 * lda; p.lda = lda; p.n = rows; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
+      p.C = panel; p.ldc = ldp;
+      p.row_bias = row_bias ? row_bias + r0 : nullptr; p.col_bias = col_bias;
+      tile_counts(p);
+      const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+      const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
+      // the epilogues of xv_score_matrix / xv_plda_matrix: the panel holds the bits those calls would write
+      e = (row_bias || col_bias) ? launch_tiles_v<EPI_PLDA>(p, grid, kOperandBytes + kBiasBytes, s)
+                                 : launch_tiles_v<EPI_MATRIX>(p, grid, kOperandBytes, s);
+      if (e != hipSuccess) return e;
+    }
+    const int32_t* lar = la ? la + r0 : nullptr;
+    int32_t* cnt = count ? count + r0 : nullptr;
+    if (stage)
+      hipLaunchKernelGGL((cohort_select_kernel<true>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
+                         mean + r0, stdv + r0, cnt);
+    else
+      hipLaunchKernelGGL((cohort_select_kernel<false>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
+                         mean + r0, stdv + r0, cnt);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace xv

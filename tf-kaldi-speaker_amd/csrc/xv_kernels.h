@@ -265,6 +265,14 @@ hipError_t launch_plda_pairs(const float* a, int64_t lda, int n, const float* ro
                              const float* col_bias, int k, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
                              hipStream_t s);
 
+// Cohort statistics for score normalisation (csrc/score.hip): per row i of a, mean and population std of the top_k largest
+// scores a[i] . b[j] + row_bias[i] + col_bias[j] over the columns j with la[i] != lb[j] (top_k 0: all of them).  The scores go
+// through a panel of whole tile rows in `ws` (at least cohort_stats_workspace_bytes), written by the matrix epilogues.
+int64_t cohort_stats_workspace_bytes(int64_t n, int64_t m);
+hipError_t launch_cohort_stats(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
+                               int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* mean,
+                               float* stdv, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s);
+
 // classifier-head validation loss (csrc/loss.hip): model/loss.py:9-48,80-384 without the logit matrix
 // kernel [E, ldk] -> class rows [C, ldr], columns normalised (tf.nn.l2_normalize) when `normalize`
 hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,

@@ -2498,6 +2498,32 @@ int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, co
   return XV_OK;
 }
 
+int64_t xv_cohort_stats_workspace(int64_t n, int64_t m, int top_k) {
+  if (n < 0 || m < 0 || m > INT32_MAX || top_k < 0) return XV_ERR_INVALID;
+  return cohort_stats_workspace_bytes(n, m);
+}
+
+int xv_cohort_stats(int device, const float* a_dev, int64_t lda, int64_t n, const float* row_bias_dev, const int32_t* labels_a_dev,
+                    const float* b_dev, int64_t ldb, int64_t m, const float* col_bias_dev, const int32_t* labels_b_dev, int k,
+                    int top_k, float* mean_dev, float* std_dev, int32_t* count_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = score_operands("xv_cohort_stats", a_dev, lda, n, b_dev, ldb, m, k)) return rc;
+  if (top_k < 0 || top_k > m) return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: 0 <= top_k <= m, got %d for m = %lld", top_k, (long long)m);
+  if ((labels_a_dev == nullptr) != (labels_b_dev == nullptr))
+    return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: exclusion labels are given for both sides or for neither");
+  if (n == 0) return XV_OK;
+  if (!mean_dev || !std_dev) return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: null pointer");
+  const int64_t need = cohort_stats_workspace_bytes(n, m);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_cohort_stats: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_cohort_stats(a_dev, lda, (int)n, row_bias_dev, labels_a_dev, b_dev, ldb, (int)m, col_bias_dev, labels_b_dev,
+                                           k, top_k, mean_dev, std_dev, count_dev, ws_dev, ws_bytes, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "cohort_stats launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 void xv_destroy(xv_handle* h) {
   if (!h) return;
   {

@@ -9,6 +9,7 @@ binaries (egs/voxceleb/v1/run.sh:410-426, egs/sre/v1/run.sh:415-491, egs/fisher/
     python -m tf_kaldi_speaker_amd.score_plda [--gpu 0] [--normalize-length true] [--simple-length-normalization false]
            [--num-utts ark:num_utts.ark] [--smoothing 0.0] [--mean mean.vec] [--transform transform.mat]
            [--front-normalize true] [--eer] [--min-dcf P_TARGET[,C_MISS[,C_FA]] ...]
+           [--cohort <rspecifier> [--norm z|t|s] [--top-k N] [--exclude-utt2spk FILE]]
            <plda> <enroll-rspecifier> <test-rspecifier> <trials> <scores-out>
 
 The positional order is ivector-plda-scoring's (model first, trials fourth; score_cos takes the trials first).  --mean,
@@ -19,7 +20,9 @@ the speaker means (an enrolment key without an entry counts as 1; how many is re
 score` in trial order.  A trial whose key is missing is skipped and counted on stderr; the exit status is non-zero only if
 no trial was scored.  --eer and --min-dcf need the third column and print `EER: x%` and `minDCF(p-target=P): x` of the
 scores as written (sid/compute_min_dcf.py; exact, from the sorted scores, on the host).  Kaldi is absent from the reference
-tree: **parity unpinned**.  Training the model (ivector-compute-lda / -plda) is compute_lda.py / compute_plda.py; ivector-adapt-plda stays with Kaldi."""
+tree: **parity unpinned**.  --cohort and its options are score_cos's (score normalisation, snorm.py): the cohort goes through
+the same front, then through prepare_test for the statistics of the enrolment rows and through prepare_enroll (num_utts 1) for
+those of the test rows; the scores written and --eer / --min-dcf are then the normalised ones.  Training the model (ivector-compute-lda / -plda) is compute_lda.py / compute_plda.py; ivector-adapt-plda stays with Kaldi."""
 import argparse
 import sys
 
@@ -28,7 +31,7 @@ import numpy as np
 from . import kaldi_io
 from . import plda
 from . import scoring
-from .score_cos import _bool, _table, select_trials, write_scores
+from .score_cos import _bool, _table, add_snorm_options, check_snorm_options, normalise_scores, select_trials, write_scores
 
 
 def _min_dcf_arg(s):
@@ -70,6 +73,7 @@ def main(argv=None):
     ap.add_argument("--eer", action="store_true", help="print the exact EER of the scored trials (needs labelled trials)")
     ap.add_argument("--min-dcf", type=_min_dcf_arg, action="append", default=[], metavar="P_TARGET[,C_MISS[,C_FA]]",
                     help="print the minimum normalised DCF of the scored trials; may be given more than once")
+    add_snorm_options(ap)
     ap.add_argument("plda")
     ap.add_argument("enroll_rspecifier")
     ap.add_argument("test_rspecifier")
@@ -78,6 +82,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 0.0 <= args.smoothing <= 1.0:
         ap.error("--smoothing must be in [0, 1]")
+    check_snorm_options(ap, args)
 
     keys1, keys2, targets = scoring.read_trials(args.trials)
     if (args.eer or args.min_dcf) and targets is None:
@@ -105,7 +110,24 @@ def main(argv=None):
     test = plda.prepare_test(model, x2, **norm)
     ia = np.fromiter((row1[keys1[t]] for t in kept), dtype=np.int64, count=len(kept))
     ib = np.fromiter((row2[keys2[t]] for t in kept), dtype=np.int64, count=len(kept))
-    printed = write_scores("score_plda", args.scores_out, keys1, keys2, kept, plda.llr_pairs(enroll, test, ia, ib))
+    scores = plda.llr_pairs(enroll, test, ia, ib)
+    if args.cohort:
+        from . import snorm
+        rowc, xc = _table(args.cohort, mean, transform, args.front_normalize, args.gpu)
+        if not rowc:
+            sys.stderr.write("score_plda: the cohort table is empty\n")
+            return 1
+
+        def stats(side, labels, cohort_labels):
+            if side == "enroll":
+                return snorm.plda_cohort_stats(enroll, plda.prepare_test(model, xc, **norm), per="enroll", top_k=args.top_k,
+                                               labels=labels, cohort_labels=cohort_labels)
+            return snorm.plda_cohort_stats(plda.prepare_enroll(model, xc, **norm), test, per="test", top_k=args.top_k,
+                                           labels=labels, cohort_labels=cohort_labels)
+        scores = normalise_scores("score_plda", args, scores, ia, ib, row1, row2, rowc, stats)
+        if scores is None:
+            return 1
+    printed = write_scores("score_plda", args.scores_out, keys1, keys2, kept, scores)
     labels = [targets[t] for t in kept] if targets is not None else None
     if args.eer:
         print("EER: %.4g%%" % (100.0 * scoring.exact_eer(printed, labels)))

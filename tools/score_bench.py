@@ -10,6 +10,11 @@
   --plda     instead of the above: the PLDA entry points (xv_plda_matrix / _pairs / _histogram / _prepare) beside the cosine
              entry point of the same (n, m, K), D = 200 and 512, enrolment sets of uniform and of mixed num_utts
 
+  --snorm    instead of the above: cohort statistics for score normalisation (xv_cohort_stats): --snorm-rows rows (40 000)
+             against a cohort of --snorm-cohort (10 000), top-300 and top_k = 0, cosine and PLDA operands, at several workspace
+             sizes, beside xv_score_matrix alone and beside torch.matmul + torch.topk + mean / std of the same shape;
+             `panel_gbytes_per_s` counts the panel written once and read once (rows of up to 12 288 scores are swept in LDS)
+
 Device times are hipEvent times around repeated calls of one entry point (warmed up, at least --seconds of work each); the
 host-side setup of scoring.py (uploads, label coding) is outside them.  Rates: useful FLOP = 2 d per score (the self
 histogram computes n (n - 1) / 2 scores, plus the lower halves of the diagonal tiles, which are not counted); `of_peak` is
@@ -110,6 +115,56 @@ def plda_leg(args, torch, lib, _lib, scoring):
     print(json.dumps(out))
 
 
+def snorm_leg(args, torch, lib, _lib, scoring):
+    """xv_cohort_stats over prepared rows, and over PLDA-shaped operands (both biases), beside the stand-ins of torch."""
+    dev = torch.device("cuda:0")
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    P = lambda t: C.c_void_p(t.data_ptr())           # noqa: E731
+    n, m, d = args.snorm_rows, args.snorm_cohort, args.dim
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2)
+    a = scoring.prepare(torch.randn((n, d), device=dev, generator=gen), as_tensor=True)
+    b = scoring.prepare(torch.randn((m, d), device=dev, generator=gen), as_tensor=True)
+    rho, tau = torch.randn((n,), device=dev, generator=gen), torch.randn((m,), device=dev, generator=gen)
+    mean, std = torch.empty((n,), device=dev), torch.empty((n,), device=dev)
+    cnt = torch.empty((n,), dtype=torch.int32, device=dev)
+    least = int(lib.xv_cohort_stats_workspace(n, m, 0))
+    whole = (n + 127) // 128 * least
+    out = {"device": torch.cuda.get_device_name(0), "rows": n, "cohort": m, "dim": d, "workspace_least_bytes": least, "cases": []}
+    mat = torch.empty((n, m), device=dev)
+    t, _ = timed(torch, lambda: _lib.check(lib.xv_score_matrix(0, P(a), d, n, P(b), d, m, d, P(mat), m, stream)), args.seconds)
+    out["score_matrix_alone_ms"] = t * 1e3
+    del mat
+    sizes = sorted(set(min(w, whole) for w in (least, 16 * least, 64 << 20, 256 << 20, whole) if w >= least))
+    for kind in ("cosine", "plda"):
+        rb, cb = (None, None) if kind == "cosine" else (P(rho), P(tau))
+        for top_k in (300, 0):
+            row = {"kind": kind, "top_k": top_k, "workspace": []}
+            for w in sizes:
+                ws = torch.empty((w,), dtype=torch.uint8, device=dev)
+                t, it = timed(torch, lambda: _lib.check(lib.xv_cohort_stats(0, P(a), d, n, rb, None, P(b), d, m, cb, None, d, top_k, P(mean),
+                                                                            P(std), P(cnt), P(ws), w, stream)), args.seconds)
+                row["workspace"].append({"bytes": w, "ms": t * 1e3, "iters": it, "tflops": 2.0 * n * m * d / t / 1e12,
+                                         "panel_gbytes_per_s": 2.0 * n * m * 4 / t / 1e9})
+                del ws
+            got_mean, got_std = mean.clone(), std.clone()
+
+            def standin():
+                s = torch.matmul(a, b.t())
+                if kind == "plda":
+                    s = s + rho[:, None] + tau[None, :]
+                v = torch.topk(s, top_k, dim=1).values if top_k else s
+                return v.mean(1), v.std(1, unbiased=False)
+            t, _ = timed(torch, standin, args.seconds, warmup=1)
+            tm, ts = standin()
+            row["torch_matmul_topk_ms"] = t * 1e3
+            row["max_abs_diff_mean_vs_torch"] = float((got_mean - tm).abs().max())
+            row["max_abs_diff_std_vs_torch"] = float((got_std - ts).abs().max())
+            out["cases"].append(row)
+            torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=0.5, help="least device time per measurement")
@@ -117,6 +172,9 @@ def main():
     ap.add_argument("--dim", type=int, default=512)
     ap.add_argument("--plda", action="store_true", help="time the PLDA entry points beside their cosine twins instead")
     ap.add_argument("--plda-rows", type=int, default=8192, help="rows on either side of the PLDA leg")
+    ap.add_argument("--snorm", action="store_true", help="time the cohort statistics of score normalisation instead")
+    ap.add_argument("--snorm-rows", type=int, default=40000)
+    ap.add_argument("--snorm-cohort", type=int, default=10000)
     args = ap.parse_args()
     import torch
     import __graft_entry__ as g
@@ -127,6 +185,8 @@ def main():
     lib = _lib.load()
     if args.plda:
         return plda_leg(args, torch, lib, _lib, scoring)
+    if args.snorm:
+        return snorm_leg(args, torch, lib, _lib, scoring)
     dev = torch.device("cuda:0")
     stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
     d = args.dim
