@@ -447,6 +447,39 @@ int xv_cohort_stats(int device, const float* a_dev, int64_t lda, int64_t n, cons
                     float* mean_dev, float* std_dev, int32_t* count_dev /* K_eff per row; may be NULL */,
                     void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- identification on the GPU (csrc/score.hip): top-K search of a gallery, cosine and PLDA.  The reference has no
+ * identification step, so this is **parity unpinned**; the rule below is the specification and tests/helpers/ref_topk.py states it
+ * in numpy.  Definitions:
+ *   The score of (i, j) is (a[i] . b[j] + row_bias[i]) + col_bias[j] over a [n, k] and b [m, k] (either bias NULL: 0).  It is
+ *   produced by the tile kernel of xv_score_matrix / xv_plda_matrix and is bit-identical to what those calls write for the same
+ *   operand order.  One entry point serves cosine (no biases) and PLDA (the packed operands, rho and tau of xv_plda_matrix).
+ *   Column j is eligible for row i unless both label arrays are given and labels_a[i] == labels_b[j].  labels_a_dev [n] /
+ *   labels_b_dev [m] are both NULL (no exclusion) or both given.  This is how a set is searched against itself without each
+ *   row finding itself.
+ *   K_eff = min(top_k, eligible columns).  Row i of scores_dev / index_dev [n, ldo] holds the K_eff eligible columns with the
+ *   largest scores, by score descending and, among equal scores, by column ascending; ties at the selection boundary go to the
+ *   lowest columns too.  -0.0 and +0.0 are equal scores.  Positions K_eff .. top_k - 1 hold -inf and -1; nothing is written
+ *   past column top_k - 1 of a row.  count_dev[i] = K_eff (count_dev may be NULL).
+ *   Order is that of the integer image the select uses (sign-flipped bits of the float): a NaN with the sign bit clear sorts
+ *   above +inf and one with the sign bit set below -inf, by payload; NaN scores of equal bits tie like any other.
+ *   The result is a pure function of the inputs: an exact radix select per row, a compaction whose slots come from a prefix
+ *   scan in column order (no atomic counter) and a sort of distinct (score, column) keys.  Repeats are bit-identical.
+ *   The scores pass through ws_dev in panels of whole 128-row tile rows, as in xv_cohort_stats;
+ *   xv_score_topk_workspace(n, m, top_k) is the least ws_bytes (one 128-row panel of m scores, rows padded to 4 floats; it
+ *   depends on m alone) or XV_ERR_INVALID for arguments xv_score_topk refuses.  The result is the same bits for every legal
+ *   ws_bytes: more workspace only means more rows per launch.  One workgroup selects one row, so for a gallery of many
+ *   thousands of rows several panels (512 rows per launch or more) are considerably faster than the least (profiles/scoring.md).
+ *   1 <= k <= 2048 and 1 <= top_k <= 1024 (XV_ERR_UNSUPPORTED otherwise; top_k > m is legal, the row is padded); m < 2^31,
+ *   n < 2^31, lda, ldb >= k, ldo >= top_k, the label arrays as above (XV_ERR_INVALID otherwise); ws_bytes below the least is
+ *   XV_ERR_WORKSPACE.  Every argument check comes before the first HIP call.  n = 0 returns XV_OK and touches nothing; m = 0
+ *   writes the padding. */
+int64_t xv_score_topk_workspace(int64_t n, int64_t m, int top_k);
+int xv_score_topk(int device, const float* a_dev, int64_t lda, int64_t n, const float* row_bias_dev /* NULL: 0 */,
+                  const int32_t* labels_a_dev /* NULL: no exclusion */, const float* b_dev, int64_t ldb, int64_t m,
+                  const float* col_bias_dev /* NULL: 0 */, const int32_t* labels_b_dev, int k, int top_k,
+                  float* scores_dev /* [n, ldo] */, int32_t* index_dev /* [n, ldo] */, int64_t ldo,
+                  int32_t* count_dev /* K_eff per row; may be NULL */, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- classifier-head validation loss on the GPU (csrc/loss.hip): what Trainer.valid evaluates per batch
  * (model/trainer.py:756-884), loss_i = logsumexp_c(z_ic) - z_i,label as tf.losses.sparse_softmax_cross_entropy takes it, without
  * ever writing the [n, C] logits.  Products are exact fp32 with fp32 accumulation (the tile arithmetic of the scoring calls);

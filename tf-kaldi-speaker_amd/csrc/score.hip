@@ -54,6 +54,10 @@
 //    its multiplicity inside the top K; one sweep sums what lies above it, one more takes the centred squares, both in
 //    double and in a fixed order.  top_k = 0 (or K = all eligible columns) skips the select.  A fused epilogue that never
 //    writes the panel has not been built.
+//
+// Identification (top-K gallery search; include/xvec_hip.h has the rule) is the same panel walk with topk_select_kernel in
+// place of the statistics: the select, an ordered compaction of the hits into LDS and a bitonic sort of (score, column) keys.
+// The reference has no identification step: **parity unpinned**, checked against tests/helpers/ref_topk.py.
 #include <mutex>
 
 #include "xv_kernels.h"
@@ -602,6 +606,317 @@ __global__ __launch_bounds__(256) void cohort_select_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------- top-K search
+constexpr int kTopkMax = 1024;                // keys of the LDS sort: 8 KB, the bytes of the digit histogram they take over
+constexpr int kTopkChunk = 128;               // keys one wave sorts in registers: two per lane
+
+// compare-exchange steps j = 64 .. 1 of the bitonic merges k = k_lo .. k_hi (powers of two, k_lo <= k_hi) on the 128 keys a
+// wave holds in registers: lane l has element i0 = base + l in x0 and i0 + 64 in x1.  Descending: in a block with
+// (i & k) == 0 the larger key moves to the lower index.  j = 64 pairs a lane's own two keys; below it the partner sits in
+// lane l ^ j (a 64-bit shuffle: no LDS bank is touched).  k = 128 starts at j = 64, a smaller k at j = k / 2.
+__device__ __forceinline__ void topk_sort_local(unsigned long long& x0, unsigned long long& x1, int i0, int lane, int k_lo,
+                                                int k_hi) {
+  for (int k = k_lo; k <= k_hi; k <<= 1) {
+    const bool desc0 = (i0 & k) == 0, desc1 = ((i0 + 64) & k) == 0;      // equal unless k == 64
+    if (k > 64) {
+      const unsigned long long hi = x0 > x1 ? x0 : x1, lo = x0 > x1 ? x1 : x0;
+      x0 = desc0 ? hi : lo;
+      x1 = desc0 ? lo : hi;
+    }
+    for (int j = k > 64 ? 32 : k >> 1; j > 0; j >>= 1) {
+      const unsigned long long y0 = __shfl_xor(x0, j, 64), y1 = __shfl_xor(x1, j, 64);
+      const bool lower = (lane & j) == 0;
+      x0 = (lower == desc0) ? (x0 > y0 ? x0 : y0) : (x0 > y0 ? y0 : x0);
+      x1 = (lower == desc1) ? (x1 > y1 ? x1 : y1) : (x1 > y1 ? y1 : x1);
+    }
+  }
+}
+
+// One workgroup per row of a panel of scores [rows, ldp]: the K = min(top_k, eligible) largest eligible scores of the row and
+// their columns, by score descending and by column ascending among equal scores (a column j is eligible unless
+// la[row] == lb[j]); positions K .. top_k - 1 get -inf / -1.  Four steps:
+//  1. the radix select of cohort_select_kernel fixes the key T of the K-th largest score and how many copies of it (`ties`)
+//     belong to the top K.  It stops early when everything from the digit it has just fixed upwards is at most 1024 scores:
+//     those are then all candidates (`whole_digit`, more than K of them) and the sort picks the K best, ties included;
+//  2. an ordered compaction: wave w owns the w-th quarter of the columns and walks it in column order, so a ballot and a count
+//     of the lower lanes (v_mbcnt) number the hits of a walk.  A first walk counts per wave, a prefix over the four counts
+//     gives every wave its base, a second walk writes the 64-bit key (score_key << 32 | ~column) of every score above T and
+//     of the first `ties` scores equal to T in column order.  No atomic counter: a slot depends on the data alone;
+//  3. a bitonic sort of the candidates, padded with zeros (below every real key: ~column has its top bit set) to a power of two
+//     P >= 128.  Merge steps with a distance of 128 or more go through LDS, a thread reading and writing keys[i] and
+//     keys[i + j] with consecutive lanes on consecutive 8-byte keys: the 32 lanes of a ds_read_b64 group cover one 256-byte
+//     bank row and the 16 lanes of a ds_write_b64 group 128 bytes, both conflict-free.  Steps with a smaller distance would
+//     fold two lanes of a group onto one bank, so they run in registers (topk_sort_local), 128 keys per wave;
+//  4. thread p writes output position p: the column from the key, the score read back from the row (the bits the panel holds,
+//     -0.0 included).
+// The keys take over the bytes of the digit histogram, which is dead after step 1.  A row too long for LDS is swept in global
+// memory with 16-byte loads, four in flight per thread, when the workspace is 16-byte aligned (`vec`; panel rows are padded
+// to 4 floats): one 4-byte load per thread and sweep step leaves the walk bound by memory latency.
+template <bool STAGE>
+__global__ __launch_bounds__(256) void topk_select_kernel(const float* __restrict__ panel, int64_t ldp, int m,
+                                                          const int32_t* __restrict__ la, const int32_t* __restrict__ lb,
+                                                          int top_k, float* __restrict__ scores, int32_t* __restrict__ index,
+                                                          int64_t ldo, int32_t* __restrict__ count, int vec) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char topk_raw[];
+  unsigned* hist = reinterpret_cast<unsigned*>(topk_raw);                          // [kSelBins], step 1
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(topk_raw);      // [kTopkMax], steps 2-4
+  static_assert(kTopkMax * sizeof(unsigned long long) <= kSelBins * sizeof(unsigned), "the keys reuse the histogram");
+  unsigned* uslot = hist + kSelBins + 16;                                          // [8], where kSelFixedBytes has them
+  float* stage = reinterpret_cast<float*>(uslot + 8);                              // [m] when STAGE
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t r = blockIdx.x;
+  const float* src = panel + r * ldp;
+  if (STAGE) {
+    for (int j = tid; j < m; j += 256) stage[j] = src[j];
+    __syncthreads();
+  }
+  auto val = [&](int j) { return STAGE ? stage[j] : src[j]; };
+  const bool excl = la != nullptr;
+  const int32_t mine = excl ? la[r] : 0;
+  auto eligible = [&](int j) { return !excl || lb[j] != mine; };
+
+  unsigned elig = (unsigned)m;
+  if (excl) {
+    unsigned c = 0;
+    for (int j = tid; j < m; j += 256) c += lb[j] != mine ? 1u : 0u;
+    elig = block_sum(c, uslot);
+  }
+  const unsigned K = (unsigned)top_k < elig ? (unsigned)top_k : elig;
+  float* out_s = scores + r * ldo;
+  int32_t* out_i = index + r * ldo;
+  if (tid == 0 && count) count[r] = (int32_t)K;
+  if (K == 0) {                                  // uniform: a fully padded row
+    for (int p = tid; p < top_k; p += 256) {
+      out_s[p] = -__builtin_inff();
+      out_i[p] = -1;
+    }
+    return;
+  }
+
+  const bool all = K == elig;
+  unsigned T = 0u, ties = 0u;                    // key of the K-th largest score; copies of it inside the top K
+  unsigned ncand = K;                            // keys that go into the sort
+  bool whole_digit = false;                      // the candidates are all scores with a key >= T, more than K of them
+  if (!all) {
+    unsigned prefix = 0u, mask = 0u, rank = K;   // the rank-th largest of the scores whose key matches prefix under mask
+#pragma unroll 1
+    for (int pass = 0; pass < 3; ++pass) {
+      const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
+      const unsigned dmask = pass == 2 ? 0x3ffu : 0x7ffu;
+      for (int i = tid; i < kSelBins; i += 256) hist[i] = 0u;
+      __syncthreads();
+      auto tally = [&](int j, float v) {
+        if (!eligible(j)) return;
+        const unsigned key = score_key(v);
+        if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & dmask], 1u);
+      };
+      if (!STAGE && vec) {                       // a long row in global memory: four 16-byte loads in flight per thread
+        const sf32x4* src4 = reinterpret_cast<const sf32x4*>(src);
+        const int m4 = m >> 2;
+        for (int q0 = 0; q0 < m4; q0 += 1024) {
+          sf32x4 v[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int q = q0 + u * 256 + tid;
+            v[u] = q < m4 ? src4[q] : sf32x4{0.f, 0.f, 0.f, 0.f};
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int q = q0 + u * 256 + tid;
+            if (q < m4) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) tally(4 * q + e, v[u][e]);
+            }
+          }
+        }
+        for (int j = 4 * m4 + tid; j < m; j += 256) tally(j, src[j]);
+      } else {
+        for (int j = tid; j < m; j += 256) tally(j, val(j));
+      }
+      __syncthreads();
+      // thread t owns digits 2047 - 8 t down to 2040 - 8 t; an inclusive scan over the threads walks the digits downwards
+      const int top = kSelBins - 1 - 8 * tid;
+      unsigned c[8], mysum = 0u;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        c[i] = hist[top - i];
+        mysum += c[i];
+      }
+      unsigned incl = mysum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned y = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += y;
+      }
+      if (lane == 63) uslot[wave] = incl;
+      __syncthreads();
+      for (int w = 0; w < wave; ++w) incl += uslot[w];
+      unsigned above = incl - mysum;             // matching scores in the digits above this thread's
+      if (above < rank && rank <= incl) {        // exactly one thread: the counts below rank are monotone
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if (above + c[i] >= rank) {
+            uslot[4] = (unsigned)(top - i);
+            uslot[5] = rank - above;
+            uslot[6] = above + c[i];             // matching scores down to and including this digit
+            break;
+          }
+          above += c[i];
+        }
+      }
+      __syncthreads();
+      // K - rank scores lie above the prefix group, uslot[6] more from this digit upwards inside it.  When all of them fit
+      // the sort there is nothing to refine: take every score from this digit upwards and let the sort find the K best
+      // (the usual case of a small K in a long row: one sweep instead of three).  Uniform: every operand comes from LDS.
+      const unsigned from_here_up = (K - rank) + uslot[6];
+      prefix |= uslot[4] << shift;
+      mask |= dmask << shift;
+      rank = uslot[5];
+      if (pass < 2 && from_here_up <= (unsigned)kTopkMax) {
+        whole_digit = true;
+        ncand = from_here_up;
+        break;
+      }
+    }
+    T = prefix;                                  // whole_digit: the lowest key of the digit (the bits below it are zero)
+    ties = rank;
+    __syncthreads();                             // uslot and the histogram are rewritten below
+  }
+
+  // step 2: wave w owns columns [w * seg, (w + 1) * seg), seg a multiple of 1024.  A walk takes 64 columns at a time, one per
+  // lane, or, for a long row in global memory, 1024 at a time as four 16-byte loads per lane (lane l holds columns
+  // 4 l .. 4 l + 3 of each 256): the hits below a column are those of the lower lanes in all four components plus the lane's
+  // own lower components.
+  const int64_t seg = (((int64_t)m + 3) / 4 + 1023) / 1024 * 1024;
+  const int c_lo = (int)(wave * seg < m ? wave * seg : m), c_hi = (int)((wave + 1) * seg < m ? (wave + 1) * seg : m);
+  auto classify = [&](int j, float v, bool& g, bool& e) {
+    g = e = false;
+    if (j < c_hi && eligible(j)) {
+      const unsigned key = score_key(v);
+      g = all || (whole_digit ? key >= T : key > T);
+      e = !all && !whole_digit && key == T;
+    }
+  };
+  auto below = [&](unsigned long long b) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+  };
+  unsigned gbase = 0u, ebase = 0u, gtotal = 0u;
+  // walk(false) counts into gbase / ebase; walk(true) writes the keys from the bases it is given
+  auto walk = [&](bool write) {
+    auto place = [&](int j, float v, bool g, bool e, unsigned rank_g, unsigned rank_e) {
+      if (!(g || e)) return;
+      const unsigned slot = g ? gbase + rank_g : gtotal + ebase + rank_e;
+      // gtotal + ties == ncand by the select; the bounds keep a slot inside the keys whatever the data
+      if ((g || ebase + rank_e < ties) && slot < ncand)
+        keys[slot] = ((unsigned long long)score_key(v) << 32) | (unsigned)~(unsigned)j;
+    };
+    if (!STAGE && vec) {
+      const int a_hi = c_hi & ~3;                // c_lo is a multiple of 4; the last m % 4 columns are walked one by one
+      for (int j0 = c_lo; j0 < a_hi; j0 += 1024) {
+        sf32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int j = j0 + u * 256 + 4 * lane;
+          v[u] = j < a_hi ? *reinterpret_cast<const sf32x4*>(src + j) : sf32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int j = j0 + u * 256 + 4 * lane;
+          bool g[4], e[4];
+          unsigned rank_g = 0u, rank_e = 0u, ng = 0u, ne = 0u;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            classify(j < a_hi ? j + c : c_hi, v[u][c], g[c], e[c]);
+            const unsigned long long bg = __ballot(g[c]), be = __ballot(e[c]);
+            rank_g += below(bg);
+            rank_e += below(be);
+            ng += (unsigned)__popcll(bg);
+            ne += (unsigned)__popcll(be);
+          }
+          if (write) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              place(j + c, v[u][c], g[c], e[c], rank_g, rank_e);
+              rank_g += g[c] ? 1u : 0u;
+              rank_e += e[c] ? 1u : 0u;
+            }
+          }
+          gbase += ng;
+          ebase += ne;
+        }
+      }
+    }
+    for (int j0 = (!STAGE && vec) ? (c_lo > (c_hi & ~3) ? c_lo : (c_hi & ~3)) : c_lo; j0 < c_hi; j0 += 64) {
+      bool g, e;
+      const int j = j0 + lane;
+      const float v = j < c_hi ? val(j) : 0.f;
+      classify(j, v, g, e);
+      const unsigned long long bg = __ballot(g), be = __ballot(e);
+      if (write) place(j, v, g, e, below(bg), below(be));
+      gbase += (unsigned)__popcll(bg);
+      ebase += (unsigned)__popcll(be);
+    }
+  };
+  walk(false);
+  if (lane == 0) {
+    uslot[wave] = gbase;
+    uslot[4 + wave] = ebase;
+  }
+  __syncthreads();
+  gbase = ebase = 0u;
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) {
+      gbase += uslot[w];
+      ebase += uslot[4 + w];
+    }
+    gtotal += uslot[w];
+  }
+  walk(true);
+  int P = kTopkChunk;
+  while (P < (int)ncand) P <<= 1;
+  for (int i = (int)ncand + tid; i < P; i += 256) keys[i] = 0ull;
+  __syncthreads();
+
+  // step 3
+  auto local_phase = [&](int k_lo, int k_hi) {
+    for (int base = wave * kTopkChunk; base < P; base += 4 * kTopkChunk) {
+      unsigned long long x0 = keys[base + lane], x1 = keys[base + 64 + lane];
+      topk_sort_local(x0, x1, base + lane, lane, k_lo, k_hi);
+      keys[base + lane] = x0;
+      keys[base + 64 + lane] = x1;
+    }
+    __syncthreads();
+  };
+  local_phase(2, kTopkChunk);
+  for (int k = 2 * kTopkChunk; k <= P; k <<= 1) {
+    for (int j = k >> 1; j >= kTopkChunk; j >>= 1) {
+      for (int t = tid; t < P / 2; t += 256) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const unsigned long long x = keys[i], y = keys[i + j];
+        if ((x < y) == ((i & k) == 0)) {
+          keys[i] = y;
+          keys[i + j] = x;
+        }
+      }
+      __syncthreads();
+    }
+    local_phase(k, k);
+  }
+
+  // step 4
+  for (int p = tid; p < top_k; p += 256) {
+    float s = -__builtin_inff();
+    int32_t c = -1;
+    if (p < (int)K) {
+      c = (int32_t)~(unsigned)keys[p];
+      s = val(c);
+    }
+    out_s[p] = s;
+    out_i[p] = c;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_score_prepare_rows(const float* x, int64_t ldx, int64_t rows, int dim, const float* mean, int normalize,
@@ -776,6 +1091,54 @@ hipError_t launch_cohort_stats(const float* a, int64_t lda, int n, const float* 
     else
       hipLaunchKernelGGL((cohort_select_kernel<false>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
                          mean + r0, stdv + r0, cnt);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------------- top-K launches
+int64_t score_topk_workspace_bytes(int64_t n, int64_t m) { return cohort_stats_workspace_bytes(n, m); }
+
+hipError_t launch_score_topk(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
+                             int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* scores,
+                             int32_t* index, int64_t ldo, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int64_t ldp = cohort_panel_ld(m);
+  int64_t prows = ws_bytes / (ldp * (int64_t)sizeof(float)) / SBM * SBM;      // whole tile rows per panel
+  const int64_t nceil = ((int64_t)n + SBM - 1) / SBM * SBM;
+  if (prows > nceil) prows = nceil;
+  if (prows < SBM) return hipErrorInvalidValue;                              // the caller checked ws_bytes
+  int cus = 0;
+  hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  float* panel = static_cast<float*>(ws);
+  const bool stage = m <= kSelStageMax;
+  const size_t sel_smem = kSelFixedBytes + (stage ? (size_t)m * sizeof(float) : 0);
+  const int vec = aligned16(ws) ? 1 : 0;         // panel rows are padded to 4 floats: 16-byte loads when the base allows
+  for (int64_t r0 = 0; r0 < n; r0 += prows) {
+    const int rows = (int)(n - r0 < prows ? n - r0 : prows);
+    if (m > 0) {
+      ScoreArgs p = {};
+      p.A = a + r0 * lda; p.lda = lda; p.n = rows; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
+      p.C = panel; p.ldc = ldp;
+      p.row_bias = row_bias ? row_bias + r0 : nullptr; p.col_bias = col_bias;
+      tile_counts(p);
+      const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+      const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
+      // the epilogues of xv_score_matrix / xv_plda_matrix: the panel holds the bits those calls would write
+      e = (row_bias || col_bias) ? launch_tiles_v<EPI_PLDA>(p, grid, kOperandBytes + kBiasBytes, s)
+                                 : launch_tiles_v<EPI_MATRIX>(p, grid, kOperandBytes, s);
+      if (e != hipSuccess) return e;
+    }
+    const int32_t* lar = la ? la + r0 : nullptr;
+    int32_t* cnt = count ? count + r0 : nullptr;
+    if (stage)
+      hipLaunchKernelGGL((topk_select_kernel<true>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
+                         scores + r0 * ldo, index + r0 * ldo, ldo, cnt, vec);
+    else
+      hipLaunchKernelGGL((topk_select_kernel<false>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
+                         scores + r0 * ldo, index + r0 * ldo, ldo, cnt, vec);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -273,6 +273,14 @@ hipError_t launch_cohort_stats(const float* a, int64_t lda, int n, const float* 
                                int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* mean,
                                float* stdv, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s);
 
+// Top-K search (csrc/score.hip): per row i of a, the top_k largest scores a[i] . b[j] + row_bias[i] + col_bias[j] over the
+// columns j with la[i] != lb[j] and their columns, by score descending then column ascending, into scores / index [n, ldo]
+// (padded with -inf / -1); count [n] (or null) gets the number of hits.  The panel and its workspace are the cohort call's.
+int64_t score_topk_workspace_bytes(int64_t n, int64_t m);
+hipError_t launch_score_topk(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
+                             int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* scores,
+                             int32_t* index, int64_t ldo, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s);
+
 // classifier-head validation loss (csrc/loss.hip): model/loss.py:9-48,80-384 without the logit matrix
 // kernel [E, ldk] -> class rows [C, ldr], columns normalised (tf.nn.l2_normalize) when `normalize`
 hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,

@@ -2524,6 +2524,34 @@ int xv_cohort_stats(int device, const float* a_dev, int64_t lda, int64_t n, cons
   return XV_OK;
 }
 
+int64_t xv_score_topk_workspace(int64_t n, int64_t m, int top_k) {
+  if (n < 0 || m < 0 || m > INT32_MAX || top_k < 1 || top_k > 1024) return XV_ERR_INVALID;
+  return score_topk_workspace_bytes(n, m);
+}
+
+int xv_score_topk(int device, const float* a_dev, int64_t lda, int64_t n, const float* row_bias_dev, const int32_t* labels_a_dev,
+                  const float* b_dev, int64_t ldb, int64_t m, const float* col_bias_dev, const int32_t* labels_b_dev, int k, int top_k,
+                  float* scores_dev, int32_t* index_dev, int64_t ldo, int32_t* count_dev, void* ws_dev, int64_t ws_bytes,
+                  void* stream) {
+  if (const int rc = score_operands("xv_score_topk", a_dev, lda, n, b_dev, ldb, m, k)) return rc;
+  if (top_k < 1 || top_k > 1024) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_score_topk: 1 <= top_k <= 1024, got %d", top_k);
+  if (ldo < top_k) return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: ldo = %lld for top_k = %d", (long long)ldo, top_k);
+  if ((labels_a_dev == nullptr) != (labels_b_dev == nullptr))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: exclusion labels are given for both sides or for neither");
+  if (n == 0) return XV_OK;
+  if (!scores_dev || !index_dev) return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: null pointer");
+  const int64_t need = score_topk_workspace_bytes(n, m);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_score_topk: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_score_topk(a_dev, lda, (int)n, row_bias_dev, labels_a_dev, b_dev, ldb, (int)m, col_bias_dev, labels_b_dev, k,
+                                         top_k, scores_dev, index_dev, ldo, count_dev, ws_dev, ws_bytes, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "score_topk launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 void xv_destroy(xv_handle* h) {
   if (!h) return;
   {

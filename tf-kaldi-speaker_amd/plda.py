@@ -334,6 +334,28 @@ def llr_matrix(enroll, test, as_tensor=False):
         return out if as_tensor else out.cpu().numpy()
 
 
+def llr_top_k(enroll, test, k, per="test", labels_enroll=None, labels_test=None, as_tensor=False):
+    """Identification with PLDA, on what prepare_enroll / prepare_test return -> scoring.TopK(scores, indices, count).
+    per="test": for every test row the k enrolment rows with the largest LLR (who is this?); per="enroll": for every
+    enrolment row the k best test rows.  Order, ties, padding and the exclusion labels (`labels_enroll` [n] and `labels_test`
+    [m], given together) are those of scoring.top_k; the [n, m] matrix is never written.
+
+    The score is llr_matrix(enroll, test)[i, j] = (a_i . b_j + rho_i) + tau_j.  per="enroll" takes exactly these bits: it is
+    xv_plda_matrix's operand order.  per="test" is the same call with the operands swapped and adds the two biases in the
+    other order, (b_j . a_i + tau_j) + rho_i: the bits of xv_plda_matrix called with the test side first, which can differ
+    from the entry of llr_matrix in the last place."""
+    if per not in ("enroll", "test"):
+        raise ValueError('per must be "enroll" or "test", got %r' % (per,))
+    kk, tau = _operands(enroll, test, "llr_top_k")
+    n, m, dev = len(enroll), len(test), enroll.device
+    ids_e, ids_t = scoring._label_ids(labels_enroll, labels_test, n, m)
+    if per == "enroll":
+        return scoring._top_k(enroll.packed, enroll.packed.shape[1], n, enroll.bias, test.packed, test.packed.shape[1], m, tau,
+                              kk, k, ids_e, ids_t, dev, as_tensor)
+    return scoring._top_k(test.packed, test.packed.shape[1], m, tau, enroll.packed, enroll.packed.shape[1], n, enroll.bias, kk, k,
+                          ids_t, ids_e, dev, as_tensor)
+
+
 def llr_pairs(enroll, test, ia, ib, as_tensor=False):
     """`ivector-plda-scoring` over a trial list: LLR of enrolment row ia[k] against test row ib[k] -> [npairs] float32.
     An index out of range raises XvError(XV_ERR_INVALID) here, on the host; repeated calls are bit-identical."""

@@ -8,7 +8,12 @@ backend.py.
 Everything is fp32 with exact products: a score of two prepared rows of length d is within (d + 8) * 2^-24 of the exact
 value.  Arrays go in and come out as numpy; a float32 torch tensor that already lives on the device is taken as it is,
 and `as_tensor=True` keeps a result there.  No CPU path: without a HIP device every function here except
-eer_from_histograms, exact_eer, min_dcf and read_trials raises RuntimeError."""
+eer_from_histograms, exact_eer, min_dcf, read_trials and identification_rate raises RuntimeError.
+
+Identification (top_k, identification_rate; plda.llr_top_k is the PLDA form) answers "which gallery rows score highest for
+this query" through xv_score_topk, without the [n, m] score matrix.  The reference has no identification step: **parity
+unpinned**; include/xvec_hip.h states the rule and tests/helpers/ref_topk.py restates it in numpy."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -126,6 +131,110 @@ def cosine_pairs(a, b, ia, ib, device=0, as_tensor=False):
         _lib.check(lib.xv_score_pairs(device, _p(ad), d, n, _p(bd), d, m, d, _p(iad), _p(ibd), ia.size, _p(out),
                                       C.c_void_p(stream)))
         return out if as_tensor else out.cpu().numpy()
+
+
+TopK = collections.namedtuple("TopK", ["scores", "indices", "count"])
+
+TOPK_WORKSPACE_BYTES = 256 << 20        # what top_k lets its workspace grow to on its own: whole 128-row panels up to this,
+TOPK_WORKSPACE_PANELS = 4               # or this many panels when they are larger (a long gallery: 512 rows per launch)
+_topk_ws = {}                           # device -> uint8 tensor, kept between calls and grown on demand
+
+
+def topk_workspace_min_bytes(n, m, top_k=1):
+    """The least workspace for n rows against a gallery of m: one 128-row panel of m scores."""
+    need = int(_lib.load().xv_score_topk_workspace(int(n), int(m), int(top_k)))
+    if need < 0:
+        raise _lib.XvError(need, "xv_score_topk_workspace: bad dimensions")
+    return need
+
+
+def _label_ids(labels_a, labels_b, n, m):
+    if (labels_a is None) != (labels_b is None):
+        raise ValueError("labels_a and labels_b are given together or not at all")
+    if labels_a is None:
+        return None, None
+    la, lb = np.asarray(labels_a).reshape(-1), np.asarray(labels_b).reshape(-1)
+    if la.shape[0] != n or lb.shape[0] != m:
+        raise ValueError("labels_a: %d for %d rows, labels_b: %d for %d rows" % (la.shape[0], n, lb.shape[0], m))
+    ids = np.unique(np.concatenate([la, lb]), return_inverse=True)[1].astype(np.int32)
+    return np.ascontiguousarray(ids[:n]), np.ascontiguousarray(ids[n:])
+
+
+def _top_k(ad, lda, n, row_bias, bd, ldb, m, col_bias, d, k, ids_a, ids_b, device, as_tensor):
+    """xv_score_topk on operands that already live on cuda:device -> TopK."""
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be in 1..1024, got %d" % k)
+    torch = _need_device()
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        dev = ad.device
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        indices = torch.empty((n, k), dtype=torch.int32, device=dev)
+        count = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n:
+            need = topk_workspace_min_bytes(n, m, k)
+            want = min((n + 127) // 128 * need, max(TOPK_WORKSPACE_PANELS * need, TOPK_WORKSPACE_BYTES // need * need))
+            ws = _topk_ws.get(device)
+            if ws is None or ws.numel() < want:
+                _topk_ws[device] = ws = torch.empty((want,), dtype=torch.uint8, device=dev)
+            lad = None if ids_a is None else torch.from_numpy(ids_a).to(dev)
+            lbd = None if ids_b is None else torch.from_numpy(ids_b).to(dev)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(lib.xv_score_topk(device, _p(ad), lda, n, None if row_bias is None else _p(row_bias),
+                                         None if lad is None else _p(lad), _p(bd), ldb, m,
+                                         None if col_bias is None else _p(col_bias), None if lbd is None else _p(lbd), d, k,
+                                         _p(scores), _p(indices), k, _p(count), _p(ws), ws.numel(), C.c_void_p(stream)))
+        if as_tensor:
+            return TopK(scores, indices, count)
+        return TopK(scores.cpu().numpy(), indices.cpu().numpy(), count.cpu().numpy())
+
+
+def top_k(a, b, k, labels_a=None, labels_b=None, device=0, as_tensor=False):
+    """Prepared rows a [n, d] (queries) against prepared rows b [m, d] (the gallery) -> TopK(scores [n, k] float32,
+    indices [n, k] int32, count [n] int32): for every row of a the k rows of b with the largest cosine, by score descending
+    and by row number ascending among equal scores; count is min(k, eligible rows) and the positions past it hold -inf / -1.
+    `labels_a` [n] / `labels_b` [m] (anything np.unique sorts) make the rows of b that carry a query's label ineligible for
+    it: labels_a = labels_b = arange searches a set against itself without a row finding itself.  1 <= k <= 1024; k may
+    exceed m.  The scores are the bits cosine_matrix(a, b) holds; the [n, m] matrix is never written: the scores pass through
+    a workspace of whole 128-row panels that is kept between calls and grows on demand (up to TOPK_WORKSPACE_BYTES, or
+    TOPK_WORKSPACE_PANELS panels if that is more: a row is selected by one workgroup, so a long gallery wants several hundred
+    rows per launch); its size does not change the result."""
+    (n, d), (m, db) = _shape2(a, "a"), _shape2(b, "b")
+    if d != db:
+        raise ValueError("a and b have different dimensions: %d, %d" % (d, db))
+    ids_a, ids_b = _label_ids(labels_a, labels_b, n, m)
+    torch = _need_device()
+    with torch.cuda.device(device):
+        ad, bd = _rows(a, device, "a"), _rows(b, device, "b")
+        return _top_k(ad, d, n, None, bd, d, m, None, d, k, ids_a, ids_b, device, as_tensor)
+
+
+def identification_rate(indices, query_labels, gallery_labels, ranks=(1, 5, 10)):
+    """Closed-set identification rates from the indices of top_k (host numpy) -> (rates, absent): rates[r] is the fraction of
+    all queries whose own label is carried by one of their first r hits, for every r of `ranks` (r beyond the width of
+    `indices` raises ValueError); padding (-1) never matches.  A query whose label no gallery row carries counts as a miss,
+    and `absent` is the number of such queries.  No queries: every rate is 0.0."""
+    idx = np.asarray(indices)
+    if idx.ndim != 2:
+        raise ValueError("indices: expected a [n, k] array, got shape %s" % (tuple(idx.shape),))
+    ql, gl = np.asarray(query_labels).reshape(-1), np.asarray(gallery_labels).reshape(-1)
+    n, width = idx.shape
+    if ql.shape[0] != n:
+        raise ValueError("query_labels: %d labels for %d queries" % (ql.shape[0], n))
+    if idx.size and (idx.min() < -1 or idx.max() >= gl.shape[0]):
+        raise ValueError("indices: an entry is outside the gallery of %d rows" % gl.shape[0])
+    ranks = [int(r) for r in ranks]
+    if any(r < 1 or r > width for r in ranks):
+        raise ValueError("ranks %r for hits %d wide" % (tuple(ranks), width))
+    valid = idx >= 0
+    hit = np.zeros((n, width), dtype=bool)
+    if gl.size:
+        hit = valid & (gl[np.where(valid, idx, 0)] == ql[:, None])
+    first = np.where(hit.any(axis=1), hit.argmax(axis=1), width)        # position of the first correct hit, or `width`
+    rates = collections.OrderedDict((r, float(np.count_nonzero(first < r)) / n if n else 0.0) for r in ranks)
+    absent = int(np.count_nonzero(~np.isin(ql, gl)))
+    return rates, absent
 
 
 def _check_nbins(nbins):

@@ -15,6 +15,11 @@
              sizes, beside xv_score_matrix alone and beside torch.matmul + torch.topk + mean / std of the same shape;
              `panel_gbytes_per_s` counts the panel written once and read once (rows of up to 12 288 scores are swept in LDS)
 
+  --topk     instead of the above: identification (xv_score_topk): --topk-queries queries (10 000) against a gallery of
+             --topk-gallery rows (1 000 000), d = --topk-dim (200), K = 10 and K = 300, cosine, at several workspace sizes,
+             beside the only way without it: xv_score_matrix over row chunks (a chunk buffer of the same bytes as the
+             workspace) and torch.topk on every chunk.  The two alternate in one process; medians of --topk-repeats runs
+
 Device times are hipEvent times around repeated calls of one entry point (warmed up, at least --seconds of work each); the
 host-side setup of scoring.py (uploads, label coding) is outside them.  Rates: useful FLOP = 2 d per score (the self
 histogram computes n (n - 1) / 2 scores, plus the lower halves of the diagonal tiles, which are not counted); `of_peak` is
@@ -165,6 +170,70 @@ def snorm_leg(args, torch, lib, _lib, scoring):
     print(json.dumps(out))
 
 
+def topk_leg(args, torch, lib, _lib, scoring):
+    """xv_score_topk beside xv_score_matrix in row chunks + torch.topk per chunk, same operands, same scratch bytes."""
+    dev = torch.device("cuda:0")
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    P = lambda t: C.c_void_p(t.data_ptr())           # noqa: E731
+    n, m, d = args.topk_queries, args.topk_gallery, args.topk_dim
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(4)
+    a = scoring.prepare(torch.randn((n, d), device=dev, generator=gen), as_tensor=True)
+    b = scoring.prepare(torch.randn((m, d), device=dev, generator=gen), as_tensor=True)
+    least = int(lib.xv_score_topk_workspace(n, m, 10))
+    per_row = least // 128
+    whole = (n + 127) // 128 * least
+    out = {"device": torch.cuda.get_device_name(0), "queries": n, "gallery": m, "dim": d, "workspace_least_bytes": least,
+           "repeats": args.topk_repeats, "cases": []}
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    for top_k in (10, 300):
+        sc = torch.empty((n, top_k), device=dev)
+        ix = torch.empty((n, top_k), dtype=torch.int32, device=dev)
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev)
+        tv = torch.empty((n, top_k), device=dev)
+        ti = torch.empty((n, top_k), dtype=torch.int64, device=dev)
+        row = {"top_k": top_k, "workspace": []}
+        for w in sorted(set(min(f * least, whole) for f in (1, 4, 8))):
+            ws = torch.empty((w,), dtype=torch.uint8, device=dev)
+            chunk_rows = w // per_row                                     # the rows xv_score_topk takes per launch
+            chunk = ws.view(torch.float32)[:chunk_rows * (per_row // 4)].view(chunk_rows, per_row // 4)
+
+            def ours():
+                _lib.check(lib.xv_score_topk(0, P(a), d, n, None, None, P(b), d, m, None, None, d, top_k, P(sc), P(ix), top_k, P(cnt),
+                                             P(ws), w, stream))
+
+            def chunked():
+                for r0 in range(0, n, chunk_rows):
+                    r = min(chunk_rows, n - r0)
+                    _lib.check(lib.xv_score_matrix(0, C.c_void_p(a.data_ptr() + 4 * d * r0), d, r, P(b), d, m, d, P(chunk), per_row // 4, stream))
+                    torch.topk(chunk[:r, :m], top_k, dim=1, out=(tv[r0:r0 + r], ti[r0:r0 + r]))
+            ours()
+            chunked()
+            torch.cuda.synchronize()
+            t_ours, t_chunk = [], []
+            for _ in range(args.topk_repeats):                            # alternating: drift of the box hits both alike
+                t_ours.append(once(ours))
+                t_chunk.append(once(chunked))
+            mo, mc = float(np.median(t_ours)), float(np.median(t_chunk))
+            row["workspace"].append({"bytes": w, "rows_per_launch": chunk_rows, "score_topk_ms": mo, "score_topk_all_ms": t_ours,
+                                     "matrix_chunks_torch_topk_ms": mc, "matrix_chunks_torch_topk_all_ms": t_chunk,
+                                     "ratio_chunked_over_score_topk": mc / mo, "tflops": 2.0 * n * m * d / (mo * 1e-3) / 1e12,
+                                     "values_equal": bool(torch.equal(sc, tv)),
+                                     "indices_equal_fraction": float((ix.long() == ti).float().mean())})
+            del ws, chunk
+            torch.cuda.empty_cache()
+        out["cases"].append(row)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=0.5, help="least device time per measurement")
@@ -175,6 +244,11 @@ def main():
     ap.add_argument("--snorm", action="store_true", help="time the cohort statistics of score normalisation instead")
     ap.add_argument("--snorm-rows", type=int, default=40000)
     ap.add_argument("--snorm-cohort", type=int, default=10000)
+    ap.add_argument("--topk", action="store_true", help="time identification (xv_score_topk) beside matrix chunks + torch.topk instead")
+    ap.add_argument("--topk-queries", type=int, default=10000)
+    ap.add_argument("--topk-gallery", type=int, default=1000000)
+    ap.add_argument("--topk-dim", type=int, default=200)
+    ap.add_argument("--topk-repeats", type=int, default=5)
     args = ap.parse_args()
     import torch
     import __graft_entry__ as g
@@ -187,6 +261,8 @@ def main():
         return plda_leg(args, torch, lib, _lib, scoring)
     if args.snorm:
         return snorm_leg(args, torch, lib, _lib, scoring)
+    if args.topk:
+        return topk_leg(args, torch, lib, _lib, scoring)
     dev = torch.device("cuda:0")
     stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
     d = args.dim
