@@ -480,6 +480,49 @@ int xv_score_topk(int device, const float* a_dev, int64_t lda, int64_t n, const 
                   float* scores_dev /* [n, ldo] */, int32_t* index_dev /* [n, ldo] */, int64_t ldo,
                   int32_t* count_dev /* K_eff per row; may be NULL */, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- speaker clustering on the GPU (csrc/cluster.hip): average-linkage agglomerative clustering per recording, the step of
+ * Kaldi's diarization/cluster.sh (agglomerative-cluster over a dense cosine or PLDA score matrix).  The reference has no
+ * clustering step, so this is **parity unpinned**; the rule below is the specification and tests/helpers/ref_cluster.py states
+ * it in numpy.  One group is one recording with n rows:
+ *   Input: a score matrix s [n, ld] float32, larger = more similar, ld = max(4, n rounded up to 4).  Only entries with column >
+ *   row are ever read: s(i, j), i < j, is the similarity of rows i and j.  The diagonal, the lower triangle and the padding
+ *   columns may hold anything, NaN included, and are never written.
+ *   State: every row starts as a cluster of size 1; a cluster is named by its lowest member row.  S(A, B) is a float32 sum that
+ *   starts as s(a, b).  When clusters a < b merge, the merged cluster keeps the name a and for every other live cluster k
+ *   S(a, k) <- S(a, k) + S(b, k), one float32 addition: every sum is a fixed chain of float32 additions given by the merge order.
+ *   Linkage: L(A, B) = double(S(A, B)) / double(|A| * |B|), the size product formed in int64, one correctly rounded division.
+ *   |L - exact mean of the original scores| <= (n - 2) 2^-24 (1 + small) max|s| (derived in the header of csrc/cluster.hip).
+ *   Step: among all live pairs a < b whose L is not NaN take the largest L; among equal L (-0.0 equals +0.0) the lowest a, then
+ *   the lowest b.  Stop without merging if there is no such pair, or clusters <= target, or not (L >= threshold).  Otherwise
+ *   merge and record (a, b, L).  The loop is a for over at most n - 1 steps.
+ *   Output: labels[i] = the cluster of row i, clusters numbered 0, 1, ... in the order of their lowest rows; num_clusters; the
+ *   merge log merge_a, merge_b (int32) and merge_height (double, the L of the step), whose positions past the merges performed
+ *   hold -1 / -1 / NaN.  Average linkage has no inversions beyond rounding, so stopping at a threshold equals cutting the
+ *   finished dendrogram, and the log lets a caller re-cut on the host.
+ *   threshold is in score terms (Kaldi's --threshold negated when the scores are negated costs); -inf means none.  target_host[g]
+ *   >= 1 is the number of clusters to stop at (reco2num_spk); NULL means 1 everywhere; a target of n or more merges nothing.
+ *   The result is a pure function of the group's own matrix, threshold and target: the same bits on every repeat, alone or
+ *   inside any batch, for every legal ws_bytes.
+ * Layout: the group matrices lie back to back in s_dev, group g at the float offset sum_{h<g} xv_ahc_matrix_floats(rows[h])
+ *   (xv_ahc_matrix_floats(n) = n * ld(n); 0 for n <= 0).  s_dev is the working matrix: the upper triangles are unspecified on
+ *   return.  labels_dev, merge_a_dev, merge_b_dev and merge_height_dev are packed by the prefix sum of rows: a group has n slots
+ *   in each (n - 1 possible merges plus one slot that is always -1 / -1 / NaN).  num_clusters_dev [num_groups].  rows_host and
+ *   target_host are host arrays and are consumed before the call returns; the library copies the group table into ws_dev,
+ *   stream-ordered.  xv_ahc_workspace(num_groups, rows_host) is the least ws_bytes (32 bytes per group rounded up to 256), or
+ *   the code xv_ahc returns for the same rows (XV_ERR_INVALID, XV_ERR_UNSUPPORTED).  ws_dev must be 8-byte aligned
+ *   (XV_ERR_INVALID otherwise): it holds 64-bit offsets.
+ * One 256-thread workgroup clusters one group, the large groups first; no workgroup waits for another and there is no atomic.
+ *   A row-best cache (per live row the best partner to its right) lives in LDS, 16 bytes per row, which bounds n:
+ *   0 <= rows[g] <= 8192, above that XV_ERR_UNSUPPORTED.  A negative row count, target < 1 or a NaN threshold is
+ *   XV_ERR_INVALID; too little workspace XV_ERR_WORKSPACE.  Every argument check comes before the first HIP call and the outputs
+ *   are untouched on any error.  num_groups = 0 returns XV_OK and touches nothing; a group of 0 rows writes only
+ *   num_clusters = 0; a group of 1 row gets label 0, count 1 and an empty log. */
+int64_t xv_ahc_matrix_floats(int64_t n);
+int64_t xv_ahc_workspace(int64_t num_groups, const int32_t* rows_host);
+int xv_ahc(int device, float* s_dev, const int32_t* rows_host, const int32_t* target_host /* NULL: 1 */, int64_t num_groups,
+           double threshold, int32_t* labels_dev, int32_t* num_clusters_dev, int32_t* merge_a_dev, int32_t* merge_b_dev,
+           double* merge_height_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- classifier-head validation loss on the GPU (csrc/loss.hip): what Trainer.valid evaluates per batch
  * (model/trainer.py:756-884), loss_i = logsumexp_c(z_ic) - z_i,label as tf.losses.sparse_softmax_cross_entropy takes it, without
  * ever writing the [n, C] logits.  Products are exact fp32 with fp32 accumulation (the tile arithmetic of the scoring calls);

@@ -36,6 +36,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_score_prepare", "xv_score_matrix", "xv_score_pairs", "xv_score_histogram",
            "xv_plda_prepare", "xv_plda_matrix", "xv_plda_pairs", "xv_plda_histogram",
            "xv_cohort_stats_workspace", "xv_cohort_stats", "xv_score_topk_workspace", "xv_score_topk",
+           "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_ahc",
            "xv_loss_prepare_classes", "xv_loss_workspace", "xv_loss_classifier",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
            "xv_ark_open", "xv_ark_open_scp", "xv_ark_scp_count", "xv_ark_scp_shapes", "xv_ark_next_batch", "xv_ark_pending_shape", "xv_ark_skipped", "xv_ark_set_copy_threads", "xv_ark_error", "xv_ark_close", "xv_ark_format_vectors", "xv_crc32c", "xv_pack_rows"]
@@ -166,6 +167,11 @@ def load():
     lib.xv_score_topk_workspace.argtypes = [i64, i64, i32]
     lib.xv_score_topk_workspace.restype = i64
     lib.xv_score_topk.argtypes = [i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, vp]
+    lib.xv_ahc_matrix_floats.argtypes = [i64]
+    lib.xv_ahc_matrix_floats.restype = i64
+    lib.xv_ahc_workspace.argtypes = [i64, vp]
+    lib.xv_ahc_workspace.restype = i64
+    lib.xv_ahc.argtypes = [i32, vp, vp, vp, i64, C.c_double, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.xv_loss_prepare_classes.argtypes = [i32, vp, i64, i32, i64, i32, vp, i64, vp]
     lib.xv_loss_workspace.argtypes = [i64, i64]
     lib.xv_loss_workspace.restype = i64
@@ -198,7 +204,7 @@ def load():
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
                      "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
+                     "xv_loss_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

@@ -281,6 +281,14 @@ hipError_t launch_score_topk(const float* a, int64_t lda, int n, const float* ro
                              int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* scores,
                              int32_t* index, int64_t ldo, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s);
 
+// Speaker clustering (csrc/cluster.hip): average-linkage AHC of every group's rows from its score matrix, one workgroup per group.
+// rows / target are host arrays (target may be null: 1); ws holds ahc_workspace_bytes(num_groups) bytes and receives the group
+// table, stream-ordered.  The caller has checked every argument; num_groups >= 1.
+int64_t ahc_matrix_floats(int64_t n);
+int64_t ahc_workspace_bytes(int64_t num_groups);
+hipError_t launch_ahc(float* s, const int32_t* rows, const int32_t* target, int64_t num_groups, double threshold, int32_t* labels,
+                      int32_t* num_clusters, int32_t* merge_a, int32_t* merge_b, double* merge_height, void* ws, hipStream_t stream);
+
 // classifier-head validation loss (csrc/loss.hip): model/loss.py:9-48,80-384 without the logit matrix
 // kernel [E, ldk] -> class rows [C, ldr], columns normalised (tf.nn.l2_normalize) when `normalize`
 hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,

@@ -2552,6 +2552,48 @@ int xv_score_topk(int device, const float* a_dev, int64_t lda, int64_t n, const 
   return XV_OK;
 }
 
+int64_t xv_ahc_matrix_floats(int64_t n) { return ahc_matrix_floats(n); }
+
+int64_t xv_ahc_workspace(int64_t num_groups, const int32_t* rows_host) {
+  if (num_groups < 0 || num_groups > INT32_MAX || (num_groups > 0 && !rows_host)) return XV_ERR_INVALID;
+  for (int64_t g = 0; g < num_groups; ++g) {      // group by group, as xv_ahc does
+    if (rows_host[g] < 0) return XV_ERR_INVALID;
+    if (rows_host[g] > 8192) return XV_ERR_UNSUPPORTED;
+  }
+  return ahc_workspace_bytes(num_groups);
+}
+
+int xv_ahc(int device, float* s_dev, const int32_t* rows_host, const int32_t* target_host, int64_t num_groups, double threshold,
+           int32_t* labels_dev, int32_t* num_clusters_dev, int32_t* merge_a_dev, int32_t* merge_b_dev, double* merge_height_dev,
+           void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (num_groups < 0 || num_groups > INT32_MAX) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: bad group count %lld", (long long)num_groups);
+  if (num_groups == 0) return XV_OK;
+  if (!rows_host) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: null pointer");
+  if (threshold != threshold) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: the threshold is NaN (-inf means none)");
+  int64_t total = 0;
+  for (int64_t g = 0; g < num_groups; ++g) {
+    if (rows_host[g] < 0) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: group %lld has %d rows", (long long)g, rows_host[g]);
+    if (rows_host[g] > 8192)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_ahc: group %lld has %d rows, at most 8192", (long long)g, rows_host[g]);
+    if (target_host && target_host[g] < 1)
+      return fail(nullptr, XV_ERR_INVALID, "xv_ahc: group %lld has target %d, at least 1", (long long)g, target_host[g]);
+    total += rows_host[g];
+  }
+  if (!num_clusters_dev || (total > 0 && (!s_dev || !labels_dev || !merge_a_dev || !merge_b_dev || !merge_height_dev)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_ahc: null pointer");
+  const int64_t need = ahc_workspace_bytes(num_groups);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_ahc: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0), (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7)
+    return fail(nullptr, XV_ERR_INVALID, "xv_ahc: the workspace must be 8-byte aligned (it holds the group table)");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_ahc(s_dev, rows_host, target_host, num_groups, threshold, labels_dev, num_clusters_dev, merge_a_dev,
+                                  merge_b_dev, merge_height_dev, ws_dev, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "xv_ahc launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 void xv_destroy(xv_handle* h) {
   if (!h) return;
   {
