@@ -204,3 +204,136 @@ def test_create_refuses_what_it_cannot_honour():
                            ({"round_to_power_of_two": 0}, _lib.XV_ERR_UNSUPPORTED, "power-of-two"), ({"struct_size": 8}, _lib.XV_ERR_INVALID, "struct_size")):
         rc, msg = create(**kw)
         assert rc == code and word in msg, (kw, rc, msg)
+
+
+# ------------------------------------------------------------------------- what tests/test_gpu_frontend_edges.py stands on
+@pytest.mark.parametrize("proportion,above,voiced", [(0.6, 15, 0.0), (0.28, 7, 1.0), (0.56, 14, 1.0)])
+def test_vad_decides_exact_counts_in_float_as_kaldi_does(proportion, above, voiced):
+    """A full window of 25 frames (context 12): the only window sizes up to 41 and proportions 0.01 .. 0.99 at which the float
+    product window * proportion lands on the other side of the count than the double product does."""
+    e = np.full(25, 4.0)
+    e[np.arange(above) * 25 // above] = 6.0                            # spread over the window; the constant threshold is 5
+    assert int((e > 5.0).sum()) == above
+    o = dict(vad_energy_threshold=5.0, vad_energy_mean_scale=0.0, vad_frames_context=12, vad_proportion_threshold=proportion)
+    got = ref_mfcc.vad(e[:, None], o)
+    assert got[12] == voiced
+    assert (above >= 25 * proportion) != bool(voiced)                   # the double comparison says the opposite
+    assert (np.float32(above) >= np.float32(25) * np.float32(proportion)) == bool(voiced)
+    # one frame more (less) above the threshold and both comparisons agree again
+    e2 = e.copy()
+    e2[np.flatnonzero(e2 < 5.0 if not voiced else e2 > 5.0)[0]] = 6.0 if not voiced else 4.0
+    assert ref_mfcc.vad(e2[:, None], o)[12] == 1.0 - voiced
+
+
+def test_float_and_double_vad_comparisons_differ_in_three_places_only():
+    differ = []
+    for p in range(1, 100):
+        for w in range(1, 42):
+            for c in range(w + 1):
+                if (np.float32(c) >= np.float32(w) * np.float32(p / 100.0)) != (c >= w * (p / 100.0)):
+                    differ.append((p, w, c))
+    assert differ == [(28, 25, 7), (56, 25, 14), (60, 25, 15)]
+
+
+@pytest.mark.parametrize("name", sorted(mfcc_cases.EDGE_CONFIGS))
+def test_edge_sets_have_the_sizes_they_are_named_for(name):
+    o = mfcc_cases.EDGE_CONFIGS[name]
+    po = M.MfccOptions(**o)
+    assert ref_mfcc.frame_sizes(o) == mfcc_cases.EDGE_SIZES[name]
+    assert (po.frame_samples, po.shift_samples, po.padded_length) == mfcc_cases.EDGE_SIZES[name]
+    assert {k: v for k, v in po.as_dict().items() if k in o} == o
+    counts = [ref_mfcc.num_frames(len(u), o) for u in mfcc_cases.edge_batch(name, o)]
+    assert sum(counts) > 40 and max(counts) < 600
+
+
+def test_edge_sets_cover_every_option_value_between_them():
+    sets = list(mfcc_cases.EDGE_CONFIGS.values())
+    seen = lambda key: {o[key] for o in sets}                                                             # noqa: E731
+    assert {"hanning", "rectangular", "hamming"} <= seen("window_type")
+    assert {0.0, 1.0} <= seen("preemphasis_coefficient")
+    assert seen("remove_dc_offset") == {True, False} and seen("raw_energy") == {True, False}
+    assert seen("use_energy") == {True, False} and seen("snip_edges") == {True, False}
+    assert 0.0 in seen("cepstral_lifter") and 0.0 in seen("low_freq") and min(seen("high_freq")) < 0
+    assert {3, 64} <= seen("num_mel_bins") and max(seen("energy_floor")) > 0
+    assert any(s == n for n, s, _ in mfcc_cases.EDGE_SIZES.values()) and any(s == 1 for _, s, _ in mfcc_cases.EDGE_SIZES.values())
+    assert {n for n, _, _ in mfcc_cases.EDGE_SIZES.values()} == {129, 256, 257, 512}
+    assert any(n % 2 and s % 2 == 0 and n > 129 for n, s, _ in mfcc_cases.EDGE_SIZES.values())
+    import ref_fbank
+    f = mfcc_cases.FBANK_EDGE_CONFIGS
+    assert not f["amp256"]["use_power"] and ref_mfcc.frame_sizes(f["amp256"])[2] == 256
+    assert not f["lin512"]["use_log_fbank"] and ref_mfcc.frame_sizes(f["lin512"]) == (512, 512, 512)
+    for o in f.values():
+        assert set(o) == set(ref_fbank.DEFAULTS)
+
+
+def test_wide16ms_has_a_mel_filter_without_an_fft_bin():
+    w = ref_mfcc.mel_bank(mfcc_cases.EDGE_CONFIGS["wide16ms"])
+    assert w.shape == (64, 128)
+    empty = int((w.sum(axis=1) == 0).sum())
+    assert empty >= 1
+    for name in ("min129", "full512", "n257"):
+        assert (ref_mfcc.mel_bank(mfcc_cases.EDGE_CONFIGS[name]).sum(axis=1) > 0).all()
+    # such a filter gives log(FLT_EPSILON) on every frame
+    x = mfcc_cases.signal(2000, 16000.0, seed=3)
+    log_mel = ref_mfcc.mfcc(x, mfcc_cases.EDGE_CONFIGS["wide16ms"], return_mel=True)
+    assert int((log_mel == np.log(EPS)).all(axis=0).sum()) == empty
+
+
+def test_full512_energy_floor_splits_the_batch():
+    """From the oracle alone: windowed energies of the batch on both sides of the floor, none within 1e-3 of it."""
+    o = mfcc_cases.EDGE_CONFIGS["full512"]
+    floor = np.log(o["energy_floor"])
+    raw = np.concatenate([ref_mfcc.mfcc(x, dict(o, energy_floor=0.0))[:, 0] for x in mfcc_cases.edge_batch("full512", o)])
+    assert np.abs(raw - floor).min() > 1e-3
+    assert (raw > floor).sum() >= 10 and (raw < floor).sum() >= 10
+    assert ((raw < floor) & (raw > np.log(EPS) + 1.0)).sum() >= 3       # floored frames that are not digital silence
+    got = np.concatenate([ref_mfcc.mfcc(x, o)[:, 0] for x in mfcc_cases.edge_batch("full512", o)])
+    assert np.array_equal(got, np.maximum(raw, floor))
+
+
+def test_tile_map_covers_every_frame_exactly_once():
+    """Pure-Python model of the tile map of csrc/mfcc.hip: base(b) = off[b] // 16 + b, tile w belongs to utterance b iff
+    base(b) <= w < base(b + 1).  Every frame lies in exactly one (tile, slot), a busy tile's frames are one utterance's, and at
+    most B tiles are idle -- what the many-tile GPU test relies on when it sizes its batch by off[B] // 16 + B."""
+    rng = np.random.RandomState(5)
+    for trial in range(60):
+        B = int(rng.randint(1, 70))
+        counts = rng.randint(0, 70, size=B)
+        counts[rng.rand(B) < 0.3] = 0
+        if trial % 4 == 0:
+            counts[:int(rng.randint(0, B + 1))] = 0                    # a run of empty utterances at the start
+        if trial % 5 == 0:
+            counts[B // 2:B // 2 + 9] = 0                              # ... in the middle
+        if trial % 7 == 0:
+            counts[rng.rand(B) < 0.5] = 16 * rng.randint(1, 4)        # exact multiples of the run
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        tiles = int(off[-1]) // 16 + B
+        assert mfcc_cases.tile_base(off, 0) == 0 and mfcc_cases.tile_base(off, B) == tiles
+        busy, idle = mfcc_cases.tile_cover(off)
+        assert len(busy) + idle == tiles and idle <= B
+        hits = np.zeros(int(off[-1]), dtype=np.int64)
+        for w, b, t0, nf in busy:
+            assert 0 <= w < tiles and 1 <= nf <= 16 and t0 % 16 == 0 and t0 + nf <= counts[b]
+            hits[off[b] + t0:off[b] + t0 + nf] += 1
+        assert (hits == 1).all()
+        assert sorted(w for w, _, _, _ in busy) == sorted(set(w for w, _, _, _ in busy))
+        # the binary search of the kernel: the last b with base(b) <= w
+        bases = [mfcc_cases.tile_base(off, b) for b in range(B)]
+        for w, b, _, _ in busy:
+            lo, hi = 0, B - 1
+            while lo < hi:
+                mid = (lo + hi + 1) >> 1
+                if bases[mid] <= w:
+                    lo = mid
+                else:
+                    hi = mid - 1
+            assert lo == b
+
+
+def test_grid_lengths_hit_the_tile_edges():
+    for o in (ref_mfcc.VOXCELEB, ref_mfcc.DEFAULTS):
+        lengths = mfcc_cases.grid_lengths(o)
+        counts = [ref_mfcc.num_frames(n, o) for n in lengths]
+        assert lengths[:9] == [0, 1, 79, 80, 81, 399, 400, 401, 560] and counts[9:] == [15, 16, 17, 32, 33]
+        # the first frame appears at 400 samples with snip_edges and at 80 (half a shift) without
+        assert counts[:9] == ([0, 0, 0, 0, 0, 0, 1, 1, 2] if o["snip_edges"] else [0, 0, 0, 1, 1, 2, 3, 3, 4])

@@ -557,7 +557,7 @@ int mfcc_create(const xv_mfcc_opts* o, int device, xv_mfcc** out, std::string* e
   h->p.dct_t = (const float*)h->bufs[7];
   h->p.dct_rowsum = (const float*)h->bufs[8];
   const int H = t.P / 2;
-  h->lds_bytes = sizeof(float) * (size_t)(4 * H + kWaves * (t.P + H + kMaxMel) + (kRun - 1) * t.S + t.N);   // <= 47 KiB
+  h->lds_bytes = sizeof(float) * (size_t)(4 * H + kWaves * (t.P + H + kMaxMel) + (kRun - 1) * t.S + t.N);   // <= 49 KiB (N = S = 512: 12544 floats)
   *out = h;
   return XV_OK;
 }
@@ -595,7 +595,7 @@ int fbank_create(const xv_fbank_opts* o, int device, xv_fbank** out, std::string
   h->p.use_log = o->use_log_fbank ? 1 : 0;
   h->p.use_power = o->use_power ? 1 : 0;
   const int H = t.P / 2;
-  h->lds_bytes = sizeof(float) * (size_t)(4 * H + kWaves * (t.P + H) + (kRun - 1) * t.S + t.N);             // <= 46 KiB
+  h->lds_bytes = sizeof(float) * (size_t)(4 * H + kWaves * (t.P + H) + (kRun - 1) * t.S + t.N);             // <= 48 KiB (N = S = 512: 12288 floats)
   *out = h;
   return XV_OK;
 }
