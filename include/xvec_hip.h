@@ -575,6 +575,45 @@ int xv_class_mean_f64(int device, const float* x_dev, int64_t ldx, int64_t n, in
                       const int32_t* utt_index_dev, int64_t num_classes, const double* c_dev, double* out_dev, int64_t ldo,
                       void* stream);
 
+/* ---- score calibration and fusion on the GPU (csrc/calibrate.hip): the statistics of a prior-weighted logistic regression
+ * over a trial list, and the affine fusion it fits.  The reference has no such step (its only fusion is the equal-weight mean
+ * of misc/utils/average_score.py): **parity unpinned**; tests/helpers/ref_calibration.py restates the rules below in numpy.
+ * A trial i has k scores s_i1 .. s_ik (1 <= k <= XV_LOGREG_MAX_SYSTEMS, XV_ERR_UNSUPPORTED otherwise), row i of scores_dev
+ * [n, lds] float32 with lds >= k (the columns k .. lds - 1 are never read), and a flag targets_dev[i] (uint8, non-zero: target).
+ * theta_host = (w_1 .. w_k, b), host doubles.  llr_i = ((w_1 s_i1 + w_2 s_i2) + ...) + b in double, ascending k, the bias last,
+ * every product and sum rounded on its own (no fused multiply-add), so that numpy written in this order gives the same bits.
+ * xv_score_fuse = out_dev[i] = (float)llr_i, one rounding.  n = 0 touches nothing.
+ * xv_logreg_stats = one pass over the trials.  With z_i = llr_i + tau, softplus(x) = max(x, 0) + log1p(exp(-|x|)), sigma
+ *   evaluated from exp(-|z|) (no overflow for either sign), c_i = c_tar, x_i = -z_i, r_i = -sigma(-z_i) for a target and
+ *   c_i = c_non, x_i = z_i, r_i = sigma(z_i) otherwise, and a_i = (s_i1, .., s_ik, 1):
+ *     stats_dev[0]                F = sum_i c_i softplus(x_i)
+ *     stats_dev[1 .. k + 1]       g = sum_i c_i r_i a_i
+ *     stats_dev[k + 2 ..]         the upper triangle of H = sum_i c_i sigma(z_i) sigma(-z_i) a_i a_i^T, row by row
+ *                                 ((0,0) .. (0,k), (1,1) .. (k,k)): 1 + (k + 1) + (k + 1)(k + 2) / 2 doubles in all;
+ *     counts_dev[0 .. 2]          targets, non-targets, and rows with a score that is not finite: such a row is counted here
+ *                                 and left out of everything else, the class counts included;
+ *     counts_dev[3 + j], [11 + j] for threshold j < num_thresholds <= XV_LOGREG_MAX_THRESHOLDS (thresholds_host, doubles):
+ *                                 #{target: (float)llr_i < eta_j} and #{non-target: (float)llr_i >= eta_j}, compared in double;
+ *                                 0 for j >= num_thresholds.  19 int64 in all.
+ *   c_tar = pi / N_tar, c_non = (1 - pi) / N_non and tau = log(pi / (1 - pi)) make F the objective of the calibration at prior
+ *   pi; k = 1, theta = (1, 0), tau = 0 and c = 1 / (2 N) give Cllr ln 2.  The caller passes the weights (it knows the class
+ *   counts), which keeps one set of sums.  All sums are double; no atomics, neither floating-point nor integer: a workgroup
+ *   owns 16384 consecutive rows, adds them in a fixed order and a second launch adds the workgroups' partials in a fixed order,
+ *   so the result is a pure function of (scores, targets, the host arguments): every repeat, every workspace at or above
+ *   xv_logreg_workspace(n, k) bytes (XV_ERR_WORKSPACE below it; 0 for n = 0, then ws_dev may be NULL) and whatever lies
+ *   behind row n give the same bits.  |entry - exact sum| is far below 1e-12 sum_i |term_i| (a term is a handful of
+ *   roundings; a sum is at most 64 serial additions and a tree).  n = 0 writes zeros.  n < 0, n >= 2^40, lds < k, a null
+ *   pointer or num_thresholds outside 0..8 is XV_ERR_INVALID; every argument check comes before the first HIP call, and
+ *   everything is stream-ordered: the call never waits for the device. */
+#define XV_LOGREG_MAX_SYSTEMS 8
+#define XV_LOGREG_MAX_THRESHOLDS 8
+int64_t xv_logreg_workspace(int64_t n, int k);
+int xv_logreg_stats(int device, const float* scores_dev, int64_t lds, int64_t n, int k, const uint8_t* targets_dev,
+                    const double* theta_host, double tau, double c_tar, double c_non, const double* thresholds_host,
+                    int num_thresholds, double* stats_dev, int64_t* counts_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+int xv_score_fuse(int device, const float* scores_dev, int64_t lds, int64_t n, int k, const double* theta_host, float* out_dev,
+                  void* stream);
+
 /* ---- host-side ark I/O (csrc/ark_io.cpp; no HIP calls, usable without a GPU) ---------------------
  * Batch counterpart of dataset/kaldi_io.py read_mat_ark (:974-994, records per _read_mat_binary
  * :1014-1031 / _read_compressed_mat :1071-1115) and write_vec_flt (:915-946): the extraction driver

@@ -26,6 +26,8 @@ XV_POOL_STATISTICS = 0
 XV_POOL_SELF_ATTENTION = 1
 XV_ACT_RELU, XV_ACT_LRELU, XV_ACT_PRELU = 0, 1, 2
 XV_LOSS_SOFTMAX, XV_LOSS_ASOFTMAX, XV_LOSS_AMSOFTMAX, XV_LOSS_ARCSOFTMAX = 0, 1, 2, 3
+XV_LOGREG_MAX_SYSTEMS = 8
+XV_LOGREG_MAX_THRESHOLDS = 8
 
 EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_option", "xv_check_overflow", "xv_flags_async", "xv_flags_decode", "xv_node_id", "xv_node_context", "xv_layer_two_unit",
            "xv_plan_create", "xv_plan_query", "xv_plan_destroy", "xv_forward", "xv_profile_begin", "xv_profile_end",
@@ -39,6 +41,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_ahc",
            "xv_loss_prepare_classes", "xv_loss_workspace", "xv_loss_classifier",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
+           "xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse",
            "xv_ark_open", "xv_ark_open_scp", "xv_ark_scp_count", "xv_ark_scp_shapes", "xv_ark_next_batch", "xv_ark_pending_shape", "xv_ark_skipped", "xv_ark_set_copy_threads", "xv_ark_error", "xv_ark_close", "xv_ark_format_vectors", "xv_crc32c", "xv_pack_rows"]
 
 
@@ -181,6 +184,10 @@ def load():
     lib.xv_gram_f64.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
     lib.xv_gram_f64_rows64.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
     lib.xv_class_mean_f64.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, vp, vp, i64, vp]
+    lib.xv_logreg_workspace.argtypes = [i64, i32]
+    lib.xv_logreg_workspace.restype = i64
+    lib.xv_logreg_stats.argtypes = [i32, vp, i64, i64, i32, vp, vp, C.c_double, C.c_double, C.c_double, vp, i32, vp, vp, vp, i64, vp]
+    lib.xv_score_fuse.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp]
     lib.xv_ark_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
     lib.xv_ark_open_scp.argtypes = [C.c_char_p, C.POINTER(vp)]
     lib.xv_ark_scp_count.argtypes = [vp]
@@ -204,7 +211,7 @@ def load():
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
                      "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
+                     "xv_loss_workspace", "xv_logreg_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

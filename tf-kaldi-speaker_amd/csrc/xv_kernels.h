@@ -315,6 +315,15 @@ hipError_t launch_gram_f64_rows64(const double* x, int64_t ldx, int64_t n, int d
 hipError_t launch_class_mean_f64(const float* x, int64_t ldx, int64_t n, int dim, const int32_t* off, const int32_t* index,
                                  int64_t num_classes, const double* c, double* out, int64_t ldo, hipStream_t s);
 
+// calibration statistics (csrc/calibrate.hip): F, g and the upper triangle of H of the prior-weighted logistic regression in
+// double plus 19 int64 counters, see include/xvec_hip.h; theta [k + 1] and thresholds are host arrays, ws holds
+// logreg_workspace_bytes(n, k) bytes.  launch_score_fuse: out[i] = float(llr_i)
+int64_t logreg_workspace_bytes(int64_t n, int k);
+hipError_t launch_logreg_stats(const float* scores, int64_t lds, int64_t n, int k, const uint8_t* targets, const double* theta,
+                               double tau, double c_tar, double c_non, const double* thresholds, int num_thresholds, double* stats,
+                               int64_t* counts, void* ws, hipStream_t s);
+hipError_t launch_score_fuse(const float* scores, int64_t lds, int64_t n, int k, const double* theta, float* out, hipStream_t s);
+
 // attention scores (model/pooling.py:189-194): score[r, h] = scale * sum_d key[r, h*dk_h + d] * q[h, d]
 // (split_key) or sum_d key[r, d] * q[h, d] (no split; dk_h == dk).
 hipError_t launch_att_scores(const float* key, int64_t ldk, int64_t rows, const float* query, int H,

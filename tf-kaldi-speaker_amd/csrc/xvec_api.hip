@@ -2269,6 +2269,44 @@ int xv_class_mean_f64(int device, const float* x_dev, int64_t ldx, int64_t n, in
   return XV_OK;
 }
 
+int64_t xv_logreg_workspace(int64_t n, int k) {
+  if (k < 1 || k > XV_LOGREG_MAX_SYSTEMS) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_logreg_workspace: 1 <= k <= 8, got %d", k);
+  if (n < 0 || n >= ((int64_t)1 << 40)) return fail(nullptr, XV_ERR_INVALID, "xv_logreg_workspace: n outside [0, 2^40)");
+  return logreg_workspace_bytes(n, k);
+}
+
+int xv_logreg_stats(int device, const float* scores_dev, int64_t lds, int64_t n, int k, const uint8_t* targets_dev,
+                    const double* theta_host, double tau, double c_tar, double c_non, const double* thresholds_host,
+                    int num_thresholds, double* stats_dev, int64_t* counts_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (k < 1 || k > XV_LOGREG_MAX_SYSTEMS) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_logreg_stats: 1 <= k <= 8, got %d", k);
+  if (n < 0 || n >= ((int64_t)1 << 40) || lds < k || !theta_host || !stats_dev || !counts_dev ||
+      (n > 0 && (!scores_dev || !targets_dev)) || num_thresholds < 0 || num_thresholds > XV_LOGREG_MAX_THRESHOLDS ||
+      (num_thresholds > 0 && !thresholds_host))
+    return fail(nullptr, XV_ERR_INVALID, "xv_logreg_stats: bad arguments");
+  const int64_t need = logreg_workspace_bytes(n, k);
+  if (ws_bytes < need || (need > 0 && !ws_dev))
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_logreg_stats: workspace %lld bytes < %lld", (long long)ws_bytes, (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7) return fail(nullptr, XV_ERR_INVALID, "xv_logreg_stats: the workspace must be 8-byte aligned");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_logreg_stats(scores_dev, lds, n, k, targets_dev, theta_host, tau, c_tar, c_non, thresholds_host,
+                                           num_thresholds, stats_dev, counts_dev, ws_dev, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "logreg_stats launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_score_fuse(int device, const float* scores_dev, int64_t lds, int64_t n, int k, const double* theta_host, float* out_dev,
+                  void* stream) {
+  if (k < 1 || k > XV_LOGREG_MAX_SYSTEMS) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_score_fuse: 1 <= k <= 8, got %d", k);
+  if (n < 0 || n >= ((int64_t)1 << 40) || lds < k || !theta_host || (n > 0 && (!scores_dev || !out_dev)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_fuse: bad arguments");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch_score_fuse(scores_dev, lds, n, k, theta_host, out_dev, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "score_fuse launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
 int xv_score_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* mean_dev,
                      const float* transform_dev, int64_t ldt, int d_out, int t_cols, int normalize, float eps, float* out_dev,
                      int64_t ldo, void* stream) {
