@@ -174,7 +174,7 @@ int xv_check_overflow(xv_handle* h, int reset);
  * endpoints) -- rescale the features or use XV_PREC_BF16X3.  The test is per utterance (a batch-wide maximum would let one
  * small utterance among ordinary ones through).
  * Hidden activations have no flag: each layer's split copy is kept at a power-of-two scale derived from the rms of its
- * batch-normalisation gamma / beta (csrc/xvec_api.hip, act_exponent), which keeps channels of ordinary magnitude clear of
+ * batch-normalisation gamma / beta (csrc/api_weights.hip, act_exponent), which keeps channels of ordinary magnitude clear of
  * both ends of the fp16 range; per-channel spread inside a 32-channel block is what XV_PREC_F16F6's block scales cannot
  * hold, and xv_finalize demotes such layers (xv_layer_two_unit).  xv_check_overflow returns the same codes. */
 int xv_flags_async(xv_handle* h, int32_t* host_flags, void* stream);

@@ -338,7 +338,7 @@ def test_split_formats_survive_a_rescaled_layer(precision, layer, shift):
     whose layer `layer` has its batch-normalisation gamma / beta scaled by 2^-shift and the next layer's kernel by 2^shift
     computes the same function (ReLU is positively homogeneous; the float64 oracle agrees to rounding) but its activations
     sit at ~1e-3 (shift 10) or ~6e-5 (shift 14: below the smallest normal fp16 number) -- or at ~500 (shift -9).  The
-    library keeps every layer's split copy at a power-of-two scale derived from gamma / beta (csrc/xvec_api.hip,
+    library keeps every layer's split copy at a power-of-two scale derived from gamma / beta (csrc/api_weights.hip,
     act_exponent), so all three split precisions must stay at their usual accuracy: 1e-4 is the path's bar, 2e-5 what
     they deliver on the unscaled model."""
     from tf_kaldi_speaker_amd import synth

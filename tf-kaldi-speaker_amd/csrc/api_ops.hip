@@ -1,0 +1,511 @@
+// C ABI of libxvec_hip.so, the stateless ops: front-end, scoring, PLDA, back-end statistics, loss heads, clustering and
+// calibration.  Every wrapper validates its arguments and hands one launch (or a short chain) to with_device().
+#include "xv_model.h"
+
+using namespace xv;
+using namespace xv::api;
+
+namespace {
+
+hipStream_t to_stream(void* stream) { return static_cast<hipStream_t>(stream); }
+
+// The common tail of every device wrapper: select `device` (the caller's current device is restored on return), run `launch`
+// and turn its hipError_t into the op's message.
+template <class Launch>
+int with_device(int device, const char* op, Launch&& launch) {
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  const hipError_t e = launch();
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "%s launch failed: %s", op, hipGetErrorString(e));
+  return XV_OK;
+}
+
+}  // namespace
+
+
+extern "C" {
+
+int xv_frontend_cmn_select(int device, const float* feats_dev, int ld, int dim, const int32_t* frame_offsets_dev,
+                           int batch, const int32_t* src_rows_dev, int64_t out_rows, int cmn_window, int center,
+                           int min_window, double* scratch_dev, float* out_dev, void* stream) {
+  if (!feats_dev || !frame_offsets_dev || !src_rows_dev || !scratch_dev || !out_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_frontend_cmn_select: null pointer");
+  if (dim < 1 || dim > 1024 || ld < dim || batch < 1 || out_rows < 0 || cmn_window < 0)
+    return fail(nullptr, XV_ERR_INVALID, "xv_frontend_cmn_select: bad dimensions");
+  return with_device(device, "cmn_select", [&] {
+    return launch_cmn_select(feats_dev, ld, dim, frame_offsets_dev, batch, scratch_dev, src_rows_dev, out_rows,
+                             cmn_window, center, min_window, out_dev, to_stream(stream));
+  });
+}
+
+int xv_mfcc_create(const xv_mfcc_opts* opts, int device, xv_mfcc** out) {
+  if (!opts || !out) return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_create: null pointer");
+  *out = nullptr;
+  std::string err;
+  const int rc = mfcc_create(opts, device, out, &err);
+  if (rc != XV_OK) return fail(nullptr, rc, "xv_mfcc_create: %s", err.c_str());
+  return XV_OK;
+}
+
+void xv_mfcc_destroy(xv_mfcc* m) { mfcc_destroy(m); }
+
+int64_t xv_mfcc_num_frames(const xv_mfcc* m, int64_t num_samples) {
+  int64_t t = 0;
+  if (!m || mfcc_num_frames(m, num_samples, &t) != 0) return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_num_frames: bad argument");
+  return t;
+}
+
+int xv_mfcc_compute(xv_mfcc* m, const int16_t* wave_dev, const int64_t* sample_offsets_dev, const int32_t* frame_offsets_dev,
+                    int batch, float* feats_dev, int64_t ld, void* stream) {
+  if (!m || !wave_dev || !sample_offsets_dev || !frame_offsets_dev || !feats_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_compute: null pointer");
+  if (batch < 1 || ld < mfcc_num_ceps(m)) return fail(nullptr, XV_ERR_INVALID, "xv_mfcc_compute: bad dimensions (batch >= 1, ld >= num_ceps)");
+  return with_device(mfcc_device(m), "mfcc", [&] {
+    return launch_mfcc(m, wave_dev, sample_offsets_dev, frame_offsets_dev, batch, feats_dev, ld,
+                       to_stream(stream));
+  });
+}
+
+int xv_vad_energy(int device, const float* feats_dev, int64_t ld, const int32_t* frame_offsets_dev, int batch, float threshold,
+                  float mean_scale, int context, float proportion, float* vad_dev, void* stream) {
+  if (!feats_dev || !frame_offsets_dev || !vad_dev) return fail(nullptr, XV_ERR_INVALID, "xv_vad_energy: null pointer");
+  if (batch < 1 || ld < 1 || context < 0 || !(proportion >= 0.f && proportion <= 1.f))
+    return fail(nullptr, XV_ERR_INVALID, "xv_vad_energy: bad arguments (batch >= 1, ld >= 1, context >= 0, 0 <= proportion <= 1)");
+  return with_device(device, "vad", [&] {
+    return launch_vad_energy(feats_dev, ld, frame_offsets_dev, batch, threshold, mean_scale, context, proportion,
+                             vad_dev, to_stream(stream));
+  });
+}
+
+int xv_fbank_create(const xv_fbank_opts* opts, int device, xv_fbank** out) {
+  if (!opts || !out) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_create: null pointer");
+  *out = nullptr;
+  std::string err;
+  const int rc = fbank_create(opts, device, out, &err);
+  if (rc != XV_OK) return fail(nullptr, rc, "xv_fbank_create: %s", err.c_str());
+  return XV_OK;
+}
+
+void xv_fbank_destroy(xv_fbank* m) { fbank_destroy(m); }
+
+int64_t xv_fbank_num_frames(const xv_fbank* m, int64_t num_samples) {
+  int64_t t = 0;
+  if (!m || fbank_num_frames(m, num_samples, &t) != 0) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_num_frames: bad argument");
+  return t;
+}
+
+int xv_fbank_num_feats(const xv_fbank* m) {
+  if (!m) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_num_feats: null pointer");
+  return fbank_num_feats(m);
+}
+
+int xv_fbank_compute(xv_fbank* m, const int16_t* wave_dev, const int64_t* sample_offsets_dev, const int32_t* frame_offsets_dev,
+                     int batch, float* feats_dev, int64_t ld, float* log_energy_dev, void* stream) {
+  if (!m || !wave_dev || !sample_offsets_dev || !frame_offsets_dev || !feats_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_fbank_compute: null pointer");
+  if (batch < 1 || ld < fbank_num_feats(m)) return fail(nullptr, XV_ERR_INVALID, "xv_fbank_compute: bad dimensions (batch >= 1, ld >= num_feats)");
+  return with_device(fbank_device(m), "fbank", [&] {
+    return launch_fbank(m, wave_dev, sample_offsets_dev, frame_offsets_dev, batch, feats_dev, ld, log_energy_dev,
+                        to_stream(stream));
+  });
+}
+
+int xv_length_normalize(int device, const float* x_dev, int64_t ldx, int64_t rows, int dim, int scaleup, float* out_dev,
+                        int64_t ldo, void* stream) {
+  if (!x_dev || !out_dev) return fail(nullptr, XV_ERR_INVALID, "xv_length_normalize: null pointer");
+  if (rows < 0 || dim < 1 || ldx < dim || ldo < dim) return fail(nullptr, XV_ERR_INVALID, "xv_length_normalize: bad dimensions");
+  return with_device(device, "length_norm", [&] {
+    return launch_length_norm(x_dev, ldx, rows, dim, scaleup, out_dev, ldo, to_stream(stream));
+  });
+}
+
+int xv_speaker_mean(int device, const float* x_dev, int64_t ldx, int dim, const int32_t* spk_offsets_dev,
+                    const int32_t* utt_index_dev, int64_t num_speakers, float* out_dev, int64_t ldo, void* stream) {
+  if (!x_dev || !out_dev || !spk_offsets_dev || !utt_index_dev) return fail(nullptr, XV_ERR_INVALID, "xv_speaker_mean: null pointer");
+  if (num_speakers < 0 || dim < 1 || ldx < dim || ldo < dim) return fail(nullptr, XV_ERR_INVALID, "xv_speaker_mean: bad dimensions");
+  return with_device(device, "speaker_mean", [&] {
+    return launch_speaker_mean(x_dev, ldx, dim, spk_offsets_dev, utt_index_dev, num_speakers, out_dev, ldo,
+                               to_stream(stream));
+  });
+}
+
+// shared argument check of the two Gram entry points
+static int gram_operands(const char* who, const void* x, int64_t ldx, int64_t n, int d, const double* g, const void* ws,
+                         int64_t ws_bytes) {
+  if (d < 1 || d > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= d <= 2048, got %d", who, d);
+  if (n < 0 || ldx < d || !g || (n > 0 && !x)) return fail(nullptr, XV_ERR_INVALID, "%s: bad arguments", who);
+  const int64_t need = gram_f64_workspace_bytes(n, d);
+  if (ws_bytes < need || (need > 0 && !ws))
+    return fail(nullptr, XV_ERR_WORKSPACE, "%s: workspace %lld bytes < %lld", who, (long long)ws_bytes, (long long)need);
+  return XV_OK;
+}
+
+int64_t xv_gram_f64_workspace(int64_t n, int d) {
+  if (d < 1 || d > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_gram_f64_workspace: 1 <= d <= 2048, got %d", d);
+  if (n < 0) return fail(nullptr, XV_ERR_INVALID, "xv_gram_f64_workspace: n < 0");
+  return gram_f64_workspace_bytes(n, d);
+}
+
+int xv_gram_f64(int device, const float* x_dev, int64_t ldx, int64_t n, int d, const double* c_dev, const double* w_dev,
+                double* g_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = gram_operands("xv_gram_f64", x_dev, ldx, n, d, g_dev, ws_dev, ws_bytes)) return rc;
+  return with_device(device, "gram_f64", [&] {
+    return launch_gram_f64(x_dev, ldx, n, d, c_dev, w_dev, g_dev, static_cast<double*>(ws_dev),
+                           to_stream(stream));
+  });
+}
+
+int xv_gram_f64_rows64(int device, const double* x_dev, int64_t ldx, int64_t n, int d, const double* c_dev, const double* w_dev,
+                       double* g_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = gram_operands("xv_gram_f64_rows64", x_dev, ldx, n, d, g_dev, ws_dev, ws_bytes)) return rc;
+  return with_device(device, "gram_f64_rows64", [&] {
+    return launch_gram_f64_rows64(x_dev, ldx, n, d, c_dev, w_dev, g_dev, static_cast<double*>(ws_dev),
+                                  to_stream(stream));
+  });
+}
+
+int xv_class_mean_f64(int device, const float* x_dev, int64_t ldx, int64_t n, int dim, const int32_t* spk_offsets_dev,
+                      const int32_t* utt_index_dev, int64_t num_classes, const double* c_dev, double* out_dev, int64_t ldo,
+                      void* stream) {
+  if (!x_dev || !out_dev || !spk_offsets_dev || !utt_index_dev) return fail(nullptr, XV_ERR_INVALID, "xv_class_mean_f64: null pointer");
+  if (num_classes < 0 || n < 0 || dim < 1 || ldx < dim || ldo < dim) return fail(nullptr, XV_ERR_INVALID, "xv_class_mean_f64: bad dimensions");
+  return with_device(device, "class_mean_f64", [&] {
+    return launch_class_mean_f64(x_dev, ldx, n, dim, spk_offsets_dev, utt_index_dev, num_classes, c_dev, out_dev, ldo,
+                                 to_stream(stream));
+  });
+}
+
+int64_t xv_logreg_workspace(int64_t n, int k) {
+  if (k < 1 || k > XV_LOGREG_MAX_SYSTEMS) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_logreg_workspace: 1 <= k <= 8, got %d", k);
+  if (n < 0 || n >= ((int64_t)1 << 40)) return fail(nullptr, XV_ERR_INVALID, "xv_logreg_workspace: n outside [0, 2^40)");
+  return logreg_workspace_bytes(n, k);
+}
+
+int xv_logreg_stats(int device, const float* scores_dev, int64_t lds, int64_t n, int k, const uint8_t* targets_dev,
+                    const double* theta_host, double tau, double c_tar, double c_non, const double* thresholds_host,
+                    int num_thresholds, double* stats_dev, int64_t* counts_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (k < 1 || k > XV_LOGREG_MAX_SYSTEMS) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_logreg_stats: 1 <= k <= 8, got %d", k);
+  if (n < 0 || n >= ((int64_t)1 << 40) || lds < k || !theta_host || !stats_dev || !counts_dev ||
+      (n > 0 && (!scores_dev || !targets_dev)) || num_thresholds < 0 || num_thresholds > XV_LOGREG_MAX_THRESHOLDS ||
+      (num_thresholds > 0 && !thresholds_host))
+    return fail(nullptr, XV_ERR_INVALID, "xv_logreg_stats: bad arguments");
+  const int64_t need = logreg_workspace_bytes(n, k);
+  if (ws_bytes < need || (need > 0 && !ws_dev))
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_logreg_stats: workspace %lld bytes < %lld", (long long)ws_bytes, (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7) return fail(nullptr, XV_ERR_INVALID, "xv_logreg_stats: the workspace must be 8-byte aligned");
+  return with_device(device, "logreg_stats", [&] {
+    return launch_logreg_stats(scores_dev, lds, n, k, targets_dev, theta_host, tau, c_tar, c_non, thresholds_host,
+                               num_thresholds, stats_dev, counts_dev, ws_dev, to_stream(stream));
+  });
+}
+
+int xv_score_fuse(int device, const float* scores_dev, int64_t lds, int64_t n, int k, const double* theta_host, float* out_dev,
+                  void* stream) {
+  if (k < 1 || k > XV_LOGREG_MAX_SYSTEMS) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_score_fuse: 1 <= k <= 8, got %d", k);
+  if (n < 0 || n >= ((int64_t)1 << 40) || lds < k || !theta_host || (n > 0 && (!scores_dev || !out_dev)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_fuse: bad arguments");
+  return with_device(device, "score_fuse", [&] {
+    return launch_score_fuse(scores_dev, lds, n, k, theta_host, out_dev, to_stream(stream));
+  });
+}
+
+int xv_score_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* mean_dev,
+                     const float* transform_dev, int64_t ldt, int d_out, int t_cols, int normalize, float eps, float* out_dev,
+                     int64_t ldo, void* stream) {
+  if (!x_dev || !out_dev) return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: null pointer");
+  if (n < 0 || n > INT32_MAX || d_in < 1 || d_out < 1 || ldx < d_in || ldo < d_out || !(eps >= 0.f))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: bad dimensions");
+  if (transform_dev) {
+    if (t_cols != d_in && t_cols != d_in + 1)
+      return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: a transform for %d-dimensional rows has %d or %d columns, not %d", d_in,
+                  d_in, d_in + 1, t_cols);
+    if (ldt < t_cols) return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: bad dimensions");
+    if (out_dev == x_dev) return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: a transform cannot run in place");
+    if (d_in > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_score_prepare: transforms of more than 2048 columns");
+  } else if (d_out != d_in) {
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_prepare: d_out != d_in without a transform");
+  }
+  return with_device(device, "score_prepare", [&] {
+    hipStream_t s = to_stream(stream);
+    if (!transform_dev) return launch_score_prepare_rows(x_dev, ldx, n, d_in, mean_dev, normalize, eps, out_dev, ldo, s);
+    hipError_t e = launch_score_matrix(x_dev, ldx, (int)n, transform_dev, ldt, d_out, d_in, mean_dev, t_cols == d_in + 1, out_dev, ldo, s);
+    if (e == hipSuccess && normalize) e = launch_score_prepare_rows(out_dev, ldo, n, d_out, nullptr, 1, eps, out_dev, ldo, s);
+    return e;
+  });
+}
+
+// shared argument check of the three scoring entry points: prepared rows a [n, d], b [m, d]
+static int score_operands(const char* who, const float* a, int64_t lda, int64_t n, const float* b, int64_t ldb, int64_t m, int d) {
+  if (!a || !b) return fail(nullptr, XV_ERR_INVALID, "%s: null pointer", who);
+  if (d < 1 || d > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= d <= 2048, got %d", who, d);
+  if (n < 0 || m < 0 || n > INT32_MAX || m > INT32_MAX || lda < d || ldb < d) return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", who);
+  return XV_OK;
+}
+
+int xv_score_matrix(int device, const float* a_dev, int64_t lda, int64_t n, const float* b_dev, int64_t ldb, int64_t m, int d,
+                    float* out_dev, int64_t ldo, void* stream) {
+  if (const int rc = score_operands("xv_score_matrix", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
+  if (!out_dev || ldo < m) return fail(nullptr, XV_ERR_INVALID, "xv_score_matrix: bad output");
+  return with_device(device, "score_matrix", [&] {
+    return launch_score_matrix(a_dev, lda, (int)n, b_dev, ldb, (int)m, d, nullptr, 0, out_dev, ldo,
+                               to_stream(stream));
+  });
+}
+
+int xv_score_pairs(int device, const float* a_dev, int64_t lda, int64_t n, const float* b_dev, int64_t ldb, int64_t m, int d,
+                   const int32_t* ia_dev, const int32_t* ib_dev, int64_t npairs, float* out_dev, void* stream) {
+  if (const int rc = score_operands("xv_score_pairs", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
+  if (npairs < 0 || npairs > ((int64_t)1 << 34)) return fail(nullptr, XV_ERR_INVALID, "xv_score_pairs: bad pair count");
+  if (npairs > 0 && (!ia_dev || !ib_dev || !out_dev)) return fail(nullptr, XV_ERR_INVALID, "xv_score_pairs: null pointer");
+  return with_device(device, "score_pairs", [&] {
+    return launch_score_pairs(a_dev, lda, (int)n, b_dev, ldb, (int)m, d, ia_dev, ib_dev, npairs, out_dev,
+                              to_stream(stream));
+  });
+}
+
+int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, const int32_t* labels_a_dev, const float* b_dev,
+                       int64_t ldb, int64_t m, const int32_t* labels_b_dev, int d, int self, int nbins, uint64_t* hist_same_dev,
+                       uint64_t* hist_diff_dev, void* stream) {
+  if (const int rc = score_operands("xv_score_histogram", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
+  if (nbins < 256 || nbins > 65536 || (nbins & (nbins - 1)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: nbins is a power of two in 256..65536, got %d", nbins);
+  if (!labels_a_dev || !labels_b_dev || !hist_same_dev || !hist_diff_dev || hist_same_dev == hist_diff_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: null pointer");
+  if (self && (a_dev != b_dev || n != m || lda != ldb || labels_a_dev != labels_b_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: self needs the same rows and labels on both sides");
+  return with_device(device, "score_histogram", [&] {
+    return launch_score_histogram(a_dev, lda, (int)n, labels_a_dev, b_dev, ldb, (int)m, labels_b_dev, d, self ? 1 : 0, nbins,
+                                  reinterpret_cast<unsigned long long*>(hist_same_dev),
+                                  reinterpret_cast<unsigned long long*>(hist_diff_dev), to_stream(stream));
+  });
+}
+
+// model/loss.py:133,242,328 (tf.nn.l2_normalize(w, dim=0)) and the transpose tf.layers.dense implies (:30-34)
+int xv_loss_prepare_classes(int device, const float* kernel_dev, int64_t ldk, int embed_dim, int64_t num_classes, int normalize,
+                            float* classes_dev, int64_t ldc, void* stream) {
+  if (!kernel_dev || !classes_dev) return fail(nullptr, XV_ERR_INVALID, "xv_loss_prepare_classes: null pointer");
+  if (embed_dim < 1 || embed_dim > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_prepare_classes: 1 <= embed_dim <= 2048, got %d", embed_dim);
+  if (num_classes < 0 || num_classes > INT32_MAX || ldk < num_classes || ldc < embed_dim)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_prepare_classes: bad dimensions");
+  return with_device(device, "loss_classes", [&] {
+    return launch_loss_classes(kernel_dev, ldk, embed_dim, num_classes, normalize ? 1 : 0, classes_dev, ldc,
+                               to_stream(stream));
+  });
+}
+
+int64_t xv_loss_workspace(int64_t n, int64_t num_classes) { return loss_workspace_bytes(n, num_classes); }
+
+// model/loss.py:9-48 (softmax), :80-198 (asoftmax), :201-286 (additive margin), :289-384 (additive angular margin), each
+// followed by tf.losses.sparse_softmax_cross_entropy; top1 = the argmax of model/trainer.py:1097
+int xv_loss_classifier(int device, const float* x_dev, int64_t ldx, int64_t n, int embed_dim, const int32_t* labels_dev,
+                       const float* classes_dev, int64_t ldc, int64_t num_classes, const float* bias_dev, int head, double margin,
+                       double fa, float* loss_dev, float* target_dev, float* lse_dev, int32_t* top1_dev, void* ws_dev,
+                       int64_t ws_bytes, void* stream) {
+  if (!x_dev || !labels_dev || !classes_dev || !loss_dev || !target_dev || !lse_dev || !top1_dev || !ws_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: null pointer");
+  if (embed_dim < 1 || embed_dim > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_classifier: 1 <= embed_dim <= 2048, got %d", embed_dim);
+  if (n < 0 || n > INT32_MAX || num_classes < 1 || num_classes > INT32_MAX || ldx < embed_dim || ldc < embed_dim)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: bad dimensions");
+  if (head < XV_LOSS_SOFTMAX || head > XV_LOSS_ARCSOFTMAX) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: unknown head %d", head);
+  if (bias_dev && head != XV_LOSS_SOFTMAX) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: only the softmax head has a bias");
+  int m = 0;
+  if (head == XV_LOSS_ASOFTMAX) {
+    if (margin != 1.0 && margin != 2.0 && margin != 4.0)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_classifier: m=%g is not supported (asoftmax: 1, 2 or 4)", margin);   // loss.py:168
+    m = (int)margin;
+  }
+  if (!(fa >= 0.0 && fa <= 1.0) || !std::isfinite(margin)) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: bad margin or fa");
+  if (ws_bytes < loss_workspace_bytes(n, num_classes))
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_loss_classifier: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)loss_workspace_bytes(n, num_classes));
+  if (n == 0) return XV_OK;
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  hipStream_t s = to_stream(stream);
+  hipError_t e = launch_loss_rows(x_dev, ldx, n, embed_dim, labels_dev, classes_dev, ldc, num_classes, bias_dev, head, m, margin, fa,
+                                  target_dev, ws_dev, s);
+  int bad = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, ws_dev, sizeof(int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "loss_rows failed: %s", hipGetErrorString(e));
+  if (bad) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier: a label lies outside [0, %lld)", (long long)num_classes);
+  e = launch_loss_tiles(x_dev, ldx, (int)n, embed_dim, labels_dev, classes_dev, ldc, (int)num_classes, bias_dev, target_dev,
+                        loss_dev, lse_dev, top1_dev, ws_dev, s);
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "loss_tiles launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
+                    int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
+                    int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,
+                    float* bias_dev, void* stream) {
+  if (!x_dev || !tables_dev) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: null pointer");
+  if (d < 1 || d > 2048 || d_in < 1 || d_in > 2048)
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_plda_prepare: 1 <= d, d_in <= 2048, got %d, %d", d, d_in);
+  if (n < 0 || n > INT32_MAX || ldx < d_in || num_tables < 1 || norm < 0 || norm > 2 || side < 0 || side > 1)
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: bad dimensions");
+  if (rows_dev && ldr < d) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: bad dimensions");
+  if (packed_dev && (ldp < (pack_second ? 2 * (int64_t)d : d) || packed_dev == x_dev || packed_dev == rows_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: packed rows of dimension %d need a buffer of their own with ldp >= %d", d,
+                pack_second ? 2 * d : d);
+  if (transform_dev) {
+    if (ldt < d_in + 1) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: the transform is [d, d_in + 1] (last column: offset)");
+    if (!rows_dev || rows_dev == x_dev) return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: a transform needs rows_dev, not in place");
+  } else if (d_in != d) {
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_prepare: d_in != d without a transform");
+  }
+  return with_device(device, "plda_prepare", [&] {
+    hipStream_t s = to_stream(stream);
+    hipError_t e = hipSuccess;
+    const float* u = x_dev;
+    int64_t ldu = ldx;
+    if (transform_dev) {
+      e = launch_score_matrix(x_dev, ldx, (int)n, transform_dev, ldt, d, d_in, nullptr, 1, rows_dev, ldr, s);
+      u = rows_dev;
+      ldu = ldr;
+    }
+    if (e == hipSuccess)
+      e = launch_plda_rows(u, ldu, n, d, norm, side, pack_second ? 1 : 0, tables_dev, logdet_dev, table_index_dev, num_tables, rows_dev,
+                           ldr, packed_dev, ldp, bias_dev, s);
+    return e;
+  });
+}
+
+// shared argument check of the three PLDA scoring entry points: packed rows a [n, k], b [m, k], rho [n], tau [m] or null
+static int plda_operands(const char* who, const float* a, int64_t lda, int64_t n, const float* rho, const float* b, int64_t ldb,
+                         int64_t m, int k) {
+  if (const int rc = score_operands(who, a, lda, n, b, ldb, m, k)) return rc;
+  if (!rho) return fail(nullptr, XV_ERR_INVALID, "%s: null pointer", who);
+  return XV_OK;
+}
+
+int xv_plda_matrix(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const float* b_dev, int64_t ldb,
+                   int64_t m, const float* tau_dev, int k, float* out_dev, int64_t ldo, void* stream) {
+  if (const int rc = plda_operands("xv_plda_matrix", a_dev, lda, n, rho_dev, b_dev, ldb, m, k)) return rc;
+  if (!out_dev || ldo < m) return fail(nullptr, XV_ERR_INVALID, "xv_plda_matrix: bad output");
+  return with_device(device, "plda_matrix", [&] {
+    return launch_plda_matrix(a_dev, lda, (int)n, rho_dev, b_dev, ldb, (int)m, tau_dev, k, out_dev, ldo,
+                              to_stream(stream));
+  });
+}
+
+int xv_plda_pairs(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const float* b_dev, int64_t ldb,
+                  int64_t m, const float* tau_dev, int k, const int32_t* ia_dev, const int32_t* ib_dev, int64_t npairs,
+                  float* out_dev, void* stream) {
+  if (const int rc = plda_operands("xv_plda_pairs", a_dev, lda, n, rho_dev, b_dev, ldb, m, k)) return rc;
+  if (npairs < 0 || npairs > ((int64_t)1 << 34)) return fail(nullptr, XV_ERR_INVALID, "xv_plda_pairs: bad pair count");
+  if (npairs > 0 && (!ia_dev || !ib_dev || !out_dev)) return fail(nullptr, XV_ERR_INVALID, "xv_plda_pairs: null pointer");
+  return with_device(device, "plda_pairs", [&] {
+    return launch_plda_pairs(a_dev, lda, (int)n, rho_dev, b_dev, ldb, (int)m, tau_dev, k, ia_dev, ib_dev, npairs, out_dev,
+                             to_stream(stream));
+  });
+}
+
+int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, const float* rho_dev, const int32_t* labels_a_dev,
+                      const float* b_dev, int64_t ldb, int64_t m, const float* tau_dev, const int32_t* labels_b_dev, int k, double lo,
+                      double hi, int nbins, uint64_t* hist_same_dev, uint64_t* hist_diff_dev, void* stream) {
+  if (const int rc = plda_operands("xv_plda_histogram", a_dev, lda, n, rho_dev, b_dev, ldb, m, k)) return rc;
+  if (nbins < 256 || nbins > 65536 || (nbins & (nbins - 1)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: nbins is a power of two in 256..65536, got %d", nbins);
+  if (!(lo < hi) || !(hi - lo <= 1.7976931348623157e308))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: the range [lo, hi) is empty or not finite");
+  if (!labels_a_dev || !labels_b_dev || !hist_same_dev || !hist_diff_dev || hist_same_dev == hist_diff_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: null pointer");
+  return with_device(device, "plda_histogram", [&] {
+    return launch_plda_histogram(a_dev, lda, (int)n, rho_dev, labels_a_dev, b_dev, ldb, (int)m, tau_dev, labels_b_dev, k, lo,
+                                 hi, nbins, reinterpret_cast<unsigned long long*>(hist_same_dev),
+                                 reinterpret_cast<unsigned long long*>(hist_diff_dev), to_stream(stream));
+  });
+}
+
+int64_t xv_cohort_stats_workspace(int64_t n, int64_t m, int top_k) {
+  if (n < 0 || m < 0 || m > INT32_MAX || top_k < 0) return XV_ERR_INVALID;
+  return cohort_stats_workspace_bytes(n, m);
+}
+
+int xv_cohort_stats(int device, const float* a_dev, int64_t lda, int64_t n, const float* row_bias_dev, const int32_t* labels_a_dev,
+                    const float* b_dev, int64_t ldb, int64_t m, const float* col_bias_dev, const int32_t* labels_b_dev, int k,
+                    int top_k, float* mean_dev, float* std_dev, int32_t* count_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = score_operands("xv_cohort_stats", a_dev, lda, n, b_dev, ldb, m, k)) return rc;
+  if (top_k < 0 || top_k > m) return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: 0 <= top_k <= m, got %d for m = %lld", top_k, (long long)m);
+  if ((labels_a_dev == nullptr) != (labels_b_dev == nullptr))
+    return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: exclusion labels are given for both sides or for neither");
+  if (n == 0) return XV_OK;
+  if (!mean_dev || !std_dev) return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: null pointer");
+  const int64_t need = cohort_stats_workspace_bytes(n, m);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_cohort_stats: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  return with_device(device, "cohort_stats", [&] {
+    return launch_cohort_stats(a_dev, lda, (int)n, row_bias_dev, labels_a_dev, b_dev, ldb, (int)m, col_bias_dev, labels_b_dev,
+                               k, top_k, mean_dev, std_dev, count_dev, ws_dev, ws_bytes, to_stream(stream));
+  });
+}
+
+int64_t xv_score_topk_workspace(int64_t n, int64_t m, int top_k) {
+  if (n < 0 || m < 0 || m > INT32_MAX || top_k < 1 || top_k > 1024) return XV_ERR_INVALID;
+  return score_topk_workspace_bytes(n, m);
+}
+
+int xv_score_topk(int device, const float* a_dev, int64_t lda, int64_t n, const float* row_bias_dev, const int32_t* labels_a_dev,
+                  const float* b_dev, int64_t ldb, int64_t m, const float* col_bias_dev, const int32_t* labels_b_dev, int k, int top_k,
+                  float* scores_dev, int32_t* index_dev, int64_t ldo, int32_t* count_dev, void* ws_dev, int64_t ws_bytes,
+                  void* stream) {
+  if (const int rc = score_operands("xv_score_topk", a_dev, lda, n, b_dev, ldb, m, k)) return rc;
+  if (top_k < 1 || top_k > 1024) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_score_topk: 1 <= top_k <= 1024, got %d", top_k);
+  if (ldo < top_k) return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: ldo = %lld for top_k = %d", (long long)ldo, top_k);
+  if ((labels_a_dev == nullptr) != (labels_b_dev == nullptr))
+    return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: exclusion labels are given for both sides or for neither");
+  if (n == 0) return XV_OK;
+  if (!scores_dev || !index_dev) return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: null pointer");
+  const int64_t need = score_topk_workspace_bytes(n, m);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_score_topk: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  return with_device(device, "score_topk", [&] {
+    return launch_score_topk(a_dev, lda, (int)n, row_bias_dev, labels_a_dev, b_dev, ldb, (int)m, col_bias_dev, labels_b_dev, k,
+                             top_k, scores_dev, index_dev, ldo, count_dev, ws_dev, ws_bytes, to_stream(stream));
+  });
+}
+
+int64_t xv_ahc_matrix_floats(int64_t n) { return ahc_matrix_floats(n); }
+
+int64_t xv_ahc_workspace(int64_t num_groups, const int32_t* rows_host) {
+  if (num_groups < 0 || num_groups > INT32_MAX || (num_groups > 0 && !rows_host)) return XV_ERR_INVALID;
+  for (int64_t g = 0; g < num_groups; ++g) {      // group by group, as xv_ahc does
+    if (rows_host[g] < 0) return XV_ERR_INVALID;
+    if (rows_host[g] > 8192) return XV_ERR_UNSUPPORTED;
+  }
+  return ahc_workspace_bytes(num_groups);
+}
+
+int xv_ahc(int device, float* s_dev, const int32_t* rows_host, const int32_t* target_host, int64_t num_groups, double threshold,
+           int32_t* labels_dev, int32_t* num_clusters_dev, int32_t* merge_a_dev, int32_t* merge_b_dev, double* merge_height_dev,
+           void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (num_groups < 0 || num_groups > INT32_MAX) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: bad group count %lld", (long long)num_groups);
+  if (num_groups == 0) return XV_OK;
+  if (!rows_host) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: null pointer");
+  if (threshold != threshold) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: the threshold is NaN (-inf means none)");
+  int64_t total = 0;
+  for (int64_t g = 0; g < num_groups; ++g) {
+    if (rows_host[g] < 0) return fail(nullptr, XV_ERR_INVALID, "xv_ahc: group %lld has %d rows", (long long)g, rows_host[g]);
+    if (rows_host[g] > 8192)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_ahc: group %lld has %d rows, at most 8192", (long long)g, rows_host[g]);
+    if (target_host && target_host[g] < 1)
+      return fail(nullptr, XV_ERR_INVALID, "xv_ahc: group %lld has target %d, at least 1", (long long)g, target_host[g]);
+    total += rows_host[g];
+  }
+  if (!num_clusters_dev || (total > 0 && (!s_dev || !labels_dev || !merge_a_dev || !merge_b_dev || !merge_height_dev)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_ahc: null pointer");
+  const int64_t need = ahc_workspace_bytes(num_groups);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_ahc: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0), (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7)
+    return fail(nullptr, XV_ERR_INVALID, "xv_ahc: the workspace must be 8-byte aligned (it holds the group table)");
+  return with_device(device, "xv_ahc", [&] {
+    return launch_ahc(s_dev, rows_host, target_host, num_groups, threshold, labels_dev, num_clusters_dev, merge_a_dev,
+                      merge_b_dev, merge_height_dev, ws_dev, to_stream(stream));
+  });
+}
+
+}  // extern "C"

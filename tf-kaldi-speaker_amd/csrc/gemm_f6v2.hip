@@ -530,7 +530,7 @@ __global__ __launch_bounds__(256) void f6v2_tail_reduce_kernel(GemmArgs p, int m
 #undef V2_GLD16
 
 // a.Xsb = activations in the two-unit block format (row stride a.ldsbx channels), a.Wfr / a.Wx6 = main / cross weights
-// (xvec_api.hip, upload_layer), a.K = taps * a.cin, taps 5, 7 or 9, a.cin % 32 == 0.  a.tail_mt / a.ksplit / a.partial: the K-split tail
+// (api_weights.hip, upload_layer), a.K = taps * a.cin, taps 5, 7 or 9, a.cin % 32 == 0.  a.tail_mt / a.ksplit / a.partial: the K-split tail
 // (gemm_bf16x3_tail_plan), decided at plan time.
 hipError_t launch_gemm_f16f6(const GemmArgs& a, hipStream_t s) {
   if (a.M <= 0) return hipSuccess;

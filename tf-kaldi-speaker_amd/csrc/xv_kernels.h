@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI layer (xvec_api.hip) and the gfx950 kernels.
+// Internal launch interface between the C-ABI layer (api_*.hip) and the gfx950 kernels.
 // Host-side structs only; nothing here is exported from the shared library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -59,7 +59,7 @@ struct GemmArgs {
   int64_t bin_x_bytes = 0;     // offset of a bin's windows inside a row of A; bin b writes output rows rowmap[m] + b
   float sb_mul = 1.f;          // fp16 split formats: the split-blocked / fp6-block output holds y * sb_mul, a per-layer power of two that
                                // keeps the activations' low halves normal (|y * sb_mul| ~ 2^4 rms; the reader's per-channel scale
-                               // carries 1 / sb_mul exactly: xvec_api.hip, act_exponent).  The fp32 output Y is never scaled.
+                               // carries 1 / sb_mul exactly: api_weights.hip, act_exponent).  The fp32 output Y is never scaled.
   int f16 = 0;                 // split format of both operands: 0 = bf16 hi/lo (bf16x3), 1 = fp16 hi/lo (f16x3: same layout and
                                // MFMA rate, 11 + 11 significand bits instead of 8 + 8; values beyond +-65504 overflow)
   long long* trace = nullptr;  // debug: per-workgroup phase timestamps (XVEC_TRACE_K), 4 per workgroup
