@@ -12,6 +12,7 @@ transform=
 normalize=true
 plda=
 smoothing=
+target_energy=
 segments=
 rttm_out=
 
@@ -39,6 +40,7 @@ if [ $# != 3 ]; then
   echo "  --normalize <true>"
   echo "  --plda <plda>                       # PLDA instead of cosine"
   echo "  --smoothing <0.0>                   # needs --plda"
+  echo "  --target-energy <E>                 # needs --plda: per-recording PCA as ivector-plda-scoring-dense (Kaldi: 0.1)"
   echo "  --segments <segments>               # with --rttm-out: key recording start end"
   echo "  --rttm-out <rttm>"
   echo ""
@@ -52,6 +54,7 @@ if [ -n "$mean" ]; then opts="$opts --mean $mean"; fi
 if [ -n "$transform" ]; then opts="$opts --transform $transform"; fi
 if [ -n "$plda" ]; then opts="$opts --plda $plda"; fi
 if [ -n "$smoothing" ]; then opts="$opts --smoothing $smoothing"; fi
+if [ -n "$target_energy" ]; then opts="$opts --target-energy $target_energy"; fi
 if [ -n "$segments" ]; then opts="$opts --segments $segments"; fi
 if [ -n "$rttm_out" ]; then opts="$opts --rttm-out $rttm_out"; fi
 

@@ -523,6 +523,52 @@ int xv_ahc(int device, float* s_dev, const int32_t* rows_host, const int32_t* ta
            double threshold, int32_t* labels_dev, int32_t* num_clusters_dev, int32_t* merge_a_dev, int32_t* merge_b_dev,
            double* merge_height_dev, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- per-recording PCA adaptation of a PLDA model on the GPU (csrc/plda_adapt.hip): what Kaldi's diarization recipe does in
+ * front of every recording's score matrix (`ivector-plda-scoring-dense --target-energy`: EstPca, ApplyPca,
+ * Plda::ApplyTransform).  Kaldi is absent from the reference tree, so this is **parity unpinned**; the rule below is the
+ * specification and tests/helpers/ref_plda_adapt.py states it in numpy.  All arithmetic is double (Kaldi's PCA is float).
+ * The global model is (m, A, psi) with A = Plda.transform: within-class covariance A^-1 A^-T, between-class A^-1 diag(psi) A^-T.
+ * One group is one recording with n float32 rows x_1 .. x_n of length d:
+ *   1. mu = (the sum of the rows in double, in row order) / n;  C = (1 / n) sum (x - mu)(x - mu)^T in double, every entry one
+ *      chain of fused multiply-adds in row order and one division: the bound of xv_gram_f64 with c = mu, plus the division.
+ *   2. C = V diag(lambda) V^T, lambda_0 >= lambda_1 >= ... >= lambda_{d-1}.
+ *   3. k = the least k >= 1 with lambda_0 + .. + lambda_{k-1} > target_energy * trace, trace = the sum of all lambda in
+ *      descending order; r = min(k + 1, d) (the published loop keeps one direction more than it needs); no such k: r = d.
+ *   4. P = the first r eigenvectors as rows [r, d].
+ *   5. M = P A^-1, W' = M M^T, B' = M diag(psi) M^T.
+ *   6. W' = L L^T (Cholesky), K = L^-1 B' L^-T = U diag(psi') U^T, psi' descending (and clamped at 0 from below).
+ *   7. A' = U^T L^-1; the adapted affine is T = [A' P | -A' P m], [r, d + 1]: u = T [x; 1] has within-class covariance I and
+ *      between-class covariance diag(psi'), and scoring goes on as with any Plda of dimension r.
+ *   8. Every row of P (before step 5) and every row of T is scaled by +-1 so that its entry of largest magnitude, the lowest
+ *      column among equals, is positive.  Scores do not depend on these signs nor on the basis inside an eigenspace.
+ *   9. Fallback: dim = 0 (the caller scores the group with the global model) when n < 2, when trace is not > 0, when the
+ *      Cholesky meets a pivot that is not > 0, or when an eigen-iteration has not converged after 30 sweeps.
+ *   The outputs of a group are a pure function of its own rows, the model and target_energy: the same bits on every repeat,
+ *   alone or in any batch, in any group order, for every legal ws_bytes.  No floating-point atomics.
+ * Eigen-iteration: two-sided cyclic Jacobi, round-robin pairs, Rutishauser's rotation; a pair is rotated while |a_pq| >
+ *   2^-53 ||A||_F / m (m = the dimension rounded up to even) and the iteration ends with the first sweep that rotates nothing.
+ * Layout: group g owns the rows offsets[g] .. offsets[g + 1]) of x_dev [*, ldx] (the caller sorts the rows by group);
+ *   offsets_host is a host array, consumed before the call returns.  within_factor_dev = A^-1 [d, d], inverted by the caller
+ *   in float64.  dim_dev [G] = r or 0; eigval_dev [G, d] = all of lambda, descending, written whenever n >= 2; pca_dev
+ *   [G, d, d], rows 0..r-1 = P; affine_dev [G, d, d + 1], rows 0..r-1 = T; psi_out_dev [G, d], entries 0..r-1 = psi'.  What lies
+ *   past r, and everything but dim (and eigval) of a fallback group, is unspecified.
+ * Workspace: xv_plda_adapt_workspace(G, d) = 256 ceil((16 G + 8) / 256) + 32 m^2 bytes is the least ws_bytes: the group table
+ *   and one slot.  One workgroup works in one slot; every further xv_plda_adapt_slot_bytes(d) = 32 m^2 bytes lets one more
+ *   group run at a time (up to min(G, 1024); what lies beyond is not used).  On return the int32 pairs at ws_dev + 8 (G + 1) hold, per group, the sweeps the two iterations needed
+ *   (-1: cap met; 0: not run or nothing to rotate).  ws_dev must be 8-byte aligned (XV_ERR_INVALID otherwise).
+ * 1 <= d <= 256, anything else is XV_ERR_UNSUPPORTED (so does xv_plda_adapt_workspace return).  Offsets that decrease or start
+ *   below 0, ldx < d, a target_energy outside (0, 1] or NaN: XV_ERR_INVALID; too little workspace: XV_ERR_WORKSPACE.  Every
+ *   argument check comes before the first HIP call and the outputs are untouched on any error.  num_groups = 0 returns XV_OK
+ *   and touches nothing. */
+int64_t xv_plda_adapt_workspace(int64_t num_groups, int d);
+int64_t xv_plda_adapt_slot_bytes(int d);
+int xv_plda_adapt(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host /* [num_groups + 1] */,
+                  int64_t num_groups, int d, const double* mean_dev /* [d] */, const double* within_factor_dev /* A^-1 [d, d] */,
+                  const double* psi_dev /* [d] */, double target_energy,
+                  int32_t* dim_dev /* [G]: r, or 0 = fall back */, double* eigval_dev /* [G, d], all of lambda, descending */,
+                  double* pca_dev /* [G, d, d], rows 0..r-1 = P */, double* affine_dev /* [G, d, d + 1], rows 0..r-1 = T */,
+                  double* psi_out_dev /* [G, d], entries 0..r-1 = psi' */, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- classifier-head validation loss on the GPU (csrc/loss.hip): what Trainer.valid evaluates per batch
  * (model/trainer.py:756-884), loss_i = logsumexp_c(z_ic) - z_i,label as tf.losses.sparse_softmax_cross_entropy takes it, without
  * ever writing the [n, C] logits.  Products are exact fp32 with fp32 accumulation (the tile arithmetic of the scoring calls);

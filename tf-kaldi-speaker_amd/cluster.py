@@ -5,14 +5,16 @@ tests/helpers/ref_cluster.py restates it in numpy.
 
     python -m tf_kaldi_speaker_amd.cluster [--gpu 0] [--threshold T | --reco2num-spk FILE] [--mean mean.vec]
            [--transform transform.mat] [--normalize true] [--plda plda [--smoothing 0.0] [--normalize-length true]
-           [--simple-length-normalization false]] [--segments FILE --rttm-out FILE]
+           [--simple-length-normalization false] [--target-energy E]] [--segments FILE --rttm-out FILE]
            <utt2reco> <xvector-rspecifier> <labels-out>
 
 <utt2reco> holds lines `key recording`; every key of the x-vector table needs one (a key without a recording is an error).
 The table goes through the front of score_cos (--mean, --transform, --normalize).  Without --plda the score of two rows is their
 cosine; with --plda it is the log likelihood ratio of ivector-plda-scoring with both sides counted as one utterance (the
-model options are score_plda's).  The per-recording PCA and whitening of ivector-plda-scoring-dense is out of scope: the
-scores are those of the global model.  Rows of one recording are merged by average linkage while the best linkage is at
+model options are score_plda's).  With --target-energy E (Kaldi's diarization/score_plda.sh uses 0.1) every recording is
+scored as ivector-plda-scoring-dense scores it: with the model projected onto the leading principal directions of the
+recording's own x-vectors (xv_plda_adapt, csrc/plda_adapt.hip; plda.adapt_groups states the rule); without it the scores are
+those of the global model.  Rows of one recording are merged by average linkage while the best linkage is at
 least --threshold (a score: larger = more similar; default 0.0, Kaldi's default), or, with --reco2num-spk (lines
 `recording N`), down to N clusters; a recording with fewer rows than N gets one cluster per row and a warning.
 <labels-out> ('-': stdout) gets `key label` lines in input order, labels from 1 per recording as agglomerative-cluster writes
@@ -193,31 +195,93 @@ def cosine(x, groups, threshold=None, num_clusters=None, mean=None, transform=No
     return _by_group(n, groups, fill, threshold, num_clusters, device)
 
 
-def plda(model, x, groups, threshold=None, num_clusters=None, mean=None, transform=None, normalize=True, normalize_length=True,
-         simple_length_norm=False, device=0):
-    """cosine() with the PLDA front: the score of rows i and j is the log likelihood ratio of plda.llr_matrix with row i on the
-    enrolment side (plda.prepare_enroll, one utterance) and row j on the test side (plda.prepare_test), written by
-    xv_plda_matrix.  `model` is a plda.Plda (plda.read_plda, plda.smooth); mean / transform / normalize are the front before it.
-    The per-recording PCA and whitening of Kaldi's ivector-plda-scoring-dense is out of scope: every recording is scored with
-    the one global model."""
+def _plda_fill(model, x, names, members, mean, transform, normalize, normalize_length, simple_length_norm, target_energy, device):
+    """The front, the global operands and, with `target_energy`, one xv_plda_adapt over all groups -> fill(g, view), which
+    writes the score matrix of group g into `view` [n, ld] with xv_plda_matrix."""
     from . import plda as plda_mod
-    n, _ = scoring._shape2(x, "x")
     torch = scoring._need_device()
     lib = _lib.load()
     front = mean is not None or transform is not None or normalize
     rows = scoring.prepare(x, mean=mean, transform=transform, normalize=normalize, device=device, as_tensor=True) if front else x
     norm = dict(normalize_length=normalize_length, simple_length_norm=simple_length_norm, device=device)
-    enroll, test = plda_mod.prepare_enroll(model, rows, **norm), plda_mod.prepare_test(model, rows, **norm)
-    k, tau = plda_mod._operands(enroll, test, "cluster.plda")
+    whole = []
 
-    def fill(members, view):
-        idx = torch.from_numpy(members).to(enroll.packed.device)
-        a, rho, b, t = enroll.packed[idx].contiguous(), enroll.bias[idx].contiguous(), test.packed[idx].contiguous(), tau[idx].contiguous()
+    def global_operands():                # the global model over all rows, as without target_energy; made on first use
+        if not whole:
+            enroll, test = plda_mod.prepare_enroll(model, rows, **norm), plda_mod.prepare_test(model, rows, **norm)
+            whole.append((enroll, test) + plda_mod._operands(enroll, test, "cluster.plda"))
+        return whole[0]
+
+    def matrix(a, rho, b, tau, k, count, view):
         stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_plda_matrix(device, _p(a), a.shape[1], len(members), _p(rho), _p(b), b.shape[1], len(members), _p(t), k,
+        _lib.check(lib.xv_plda_matrix(device, _p(a), a.shape[1], count, _p(rho), _p(b), b.shape[1], count, _p(tau), k,
                                       _p(view), view.shape[1], C.c_void_p(stream)))
 
-    return _by_group(n, groups, fill, threshold, num_clusters, device)
+    def fill_global(g, view):
+        enroll, test, k, tau = global_operands()
+        idx = torch.from_numpy(members[g]).to(enroll.packed.device)
+        matrix(enroll.packed[idx].contiguous(), enroll.bias[idx].contiguous(), test.packed[idx].contiguous(), tau[idx].contiguous(),
+               k, len(members[g]), view)
+
+    if target_energy is None:
+        global_operands()
+        return fill_global
+
+    with torch.cuda.device(device):
+        rows = scoring._rows(rows, device, "x")
+        order = np.concatenate(members) if members else np.zeros(0, np.int64)
+        xs = rows[torch.from_numpy(order).to(rows.device)].contiguous()
+    offsets = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.int64)
+    dim, _, _, affine, psi, _ = plda_mod._adapt_raw(model, xs, offsets, target_energy, device, want_pca=False)
+    plda_mod._warn_fallback(dim, "cluster.plda")
+
+    def fill(g, view):
+        r = int(dim[g])
+        if r == 0:
+            return fill_global(g, view)
+        adapted = plda_mod.AdaptedPlda(None, affine[g, :r], psi[g, :r], None)
+        xg = xs[int(offsets[g]):int(offsets[g + 1])]
+        enroll, test = plda_mod.prepare_enroll(adapted, xg, **norm), plda_mod.prepare_test(adapted, xg, **norm)
+        k, tau = plda_mod._operands(enroll, test, "cluster.plda")
+        matrix(enroll.packed, enroll.bias, test.packed, tau, k, len(members[g]), view)
+
+    return fill
+
+
+def plda(model, x, groups, threshold=None, num_clusters=None, mean=None, transform=None, normalize=True, normalize_length=True,
+         simple_length_norm=False, device=0, target_energy=None):
+    """cosine() with the PLDA front: the score of rows i and j is the log likelihood ratio of plda.llr_matrix with row i on the
+    enrolment side (plda.prepare_enroll, one utterance) and row j on the test side (plda.prepare_test), written by
+    xv_plda_matrix.  `model` is a plda.Plda (plda.read_plda, plda.smooth); mean / transform / normalize are the front before it.
+    `target_energy` None scores every recording with the one global model.  A value in (0, 1] is Kaldi's
+    `ivector-plda-scoring-dense --target-energy`: one xv_plda_adapt call over all recordings (plda.adapt_groups has the rule)
+    gives every recording its own PCA-projected model, and its matrix is bit for bit plda.llr_matrix of the recording's rows
+    prepared with that model; a recording that cannot be adapted is scored with the global model, and one warning counts
+    such recordings."""
+    n, _ = scoring._shape2(x, "x")
+    names, members = _group_rows(groups, n)
+    fill = _plda_fill(model, x, names, members, mean, transform, normalize, normalize_length, simple_length_norm, target_energy, device)
+    res = _run([len(m) for m in members], fill, _threshold(threshold), _targets(num_clusters, len(names), names), device)
+    labels = np.zeros(n, np.int32)
+    for m, r in zip(members, res):
+        labels[m] = r.labels
+    return labels, collections.OrderedDict(zip(names, res))
+
+
+def plda_matrices(model, x, groups, mean=None, transform=None, normalize=True, normalize_length=True, simple_length_norm=False,
+                  device=0, target_energy=None):
+    """The score matrices plda() clusters, one [n, n] float32 numpy array per group -> OrderedDict in sorted group order."""
+    n, _ = scoring._shape2(x, "x")
+    torch = scoring._need_device()
+    names, members = _group_rows(groups, n)
+    fill = _plda_fill(model, x, names, members, mean, transform, normalize, normalize_length, simple_length_norm, target_energy, device)
+    out = collections.OrderedDict()
+    with torch.cuda.device(device):
+        for g, (name, m) in enumerate(zip(names, members)):
+            buf = torch.empty((len(m), matrix_ld(len(m))), dtype=torch.float32, device="cuda:%d" % device)
+            fill(g, buf)
+            out[name] = buf[:, :len(m)].cpu().numpy()
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------- host: RTTM
@@ -307,6 +371,9 @@ def parse_args(argv=None):
     ap.add_argument("--normalize-length", type=_bool, default=None, help="ivector-plda-scoring --normalize-length; default true; needs --plda")
     ap.add_argument("--simple-length-normalization", type=_bool, default=None,
                     help="ivector-plda-scoring --simple-length-normalization; default false; needs --plda")
+    ap.add_argument("--target-energy", type=float, default=None,
+                    help="ivector-plda-scoring-dense --target-energy, in (0, 1]: score every recording in the PCA subspace of its own "
+                         "x-vectors that holds this share of their variance; default: the global model; needs --plda")
     ap.add_argument("--segments", default="", help="`key recording start end` lines; with --rttm-out: write the labels as RTTM")
     ap.add_argument("--rttm-out", default="", help="RTTM file to write; needs --segments")
     ap.add_argument("utt2reco")
@@ -321,7 +388,8 @@ def parse_args(argv=None):
         args.threshold = 0.0
     if not args.plda:
         for name, value in (("--smoothing", args.smoothing), ("--normalize-length", args.normalize_length),
-                            ("--simple-length-normalization", args.simple_length_normalization)):
+                            ("--simple-length-normalization", args.simple_length_normalization),
+                            ("--target-energy", args.target_energy)):
             if value is not None:
                 ap.error("%s needs --plda" % name)
     args.smoothing = 0.0 if args.smoothing is None else args.smoothing
@@ -329,6 +397,8 @@ def parse_args(argv=None):
     args.simple_length_normalization = bool(args.simple_length_normalization)
     if not 0.0 <= args.smoothing <= 1.0:
         ap.error("--smoothing must be in [0, 1]")
+    if args.target_energy is not None and not 0.0 < args.target_energy <= 1.0:
+        ap.error("--target-energy must be in (0, 1]")
     if bool(args.segments) != bool(args.rttm_out):
         ap.error("--segments and --rttm-out are given together")
     return args
@@ -369,7 +439,7 @@ def main(argv=None):
             from . import plda as plda_mod
             model = plda_mod.smooth(plda_mod.read_plda(args.plda), args.smoothing)
             labels, per = plda(model, x, recos, normalize_length=args.normalize_length, simple_length_norm=args.simple_length_normalization,
-                               **front)
+                               target_energy=args.target_energy, **front)
         else:
             labels, per = cosine(x, recos, **front)
     except ValueError as e:

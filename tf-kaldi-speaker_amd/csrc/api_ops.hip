@@ -508,4 +508,45 @@ int xv_ahc(int device, float* s_dev, const int32_t* rows_host, const int32_t* ta
   });
 }
 
+int64_t xv_plda_adapt_workspace(int64_t num_groups, int d) {
+  if (d < 1 || d > 256) return XV_ERR_UNSUPPORTED;
+  if (num_groups < 0 || num_groups > INT32_MAX) return XV_ERR_INVALID;
+  return plda_adapt_workspace_bytes(num_groups, d);
+}
+
+int64_t xv_plda_adapt_slot_bytes(int d) {
+  if (d < 1 || d > 256) return XV_ERR_UNSUPPORTED;
+  return plda_adapt_slot_bytes(d);
+}
+
+int xv_plda_adapt(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host, int64_t num_groups, int d,
+                  const double* mean_dev, const double* within_factor_dev, const double* psi_dev, double target_energy,
+                  int32_t* dim_dev, double* eigval_dev, double* pca_dev, double* affine_dev, double* psi_out_dev, void* ws_dev,
+                  int64_t ws_bytes, void* stream) {
+  if (d < 1 || d > 256) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_plda_adapt: 1 <= d <= 256, got %d", d);
+  if (!(target_energy > 0.0 && target_energy <= 1.0))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_adapt: target_energy must be in (0, 1], got %g", target_energy);
+  if (num_groups < 0 || num_groups > INT32_MAX)
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_adapt: bad group count %lld", (long long)num_groups);
+  if (num_groups == 0) return XV_OK;
+  if (!offsets_host || ldx < d) return fail(nullptr, XV_ERR_INVALID, "xv_plda_adapt: bad arguments (offsets, ldx >= d)");
+  if (offsets_host[0] < 0) return fail(nullptr, XV_ERR_INVALID, "xv_plda_adapt: the first offset is negative");
+  for (int64_t g = 0; g < num_groups; ++g)
+    if (offsets_host[g + 1] < offsets_host[g])
+      return fail(nullptr, XV_ERR_INVALID, "xv_plda_adapt: the offsets decrease at group %lld", (long long)g);
+  if (!mean_dev || !within_factor_dev || !psi_dev || !dim_dev || !eigval_dev || !pca_dev || !affine_dev || !psi_out_dev ||
+      (offsets_host[num_groups] > 0 && !x_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_adapt: null pointer");
+  const int64_t need = plda_adapt_workspace_bytes(num_groups, d);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_plda_adapt: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7)
+    return fail(nullptr, XV_ERR_INVALID, "xv_plda_adapt: the workspace must be 8-byte aligned (it holds offsets and doubles)");
+  return with_device(device, "xv_plda_adapt", [&] {
+    return launch_plda_adapt(x_dev, ldx, offsets_host, num_groups, d, mean_dev, within_factor_dev, psi_dev, target_energy, dim_dev,
+                             eigval_dev, pca_dev, affine_dev, psi_out_dev, ws_dev, ws_bytes, to_stream(stream));
+  });
+}
+
 }  // extern "C"

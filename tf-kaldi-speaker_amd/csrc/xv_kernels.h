@@ -289,6 +289,16 @@ int64_t ahc_workspace_bytes(int64_t num_groups);
 hipError_t launch_ahc(float* s, const int32_t* rows, const int32_t* target, int64_t num_groups, double threshold, int32_t* labels,
                       int32_t* num_clusters, int32_t* merge_a, int32_t* merge_b, double* merge_height, void* ws, hipStream_t stream);
 
+// Per-recording PCA adaptation of a PLDA model (csrc/plda_adapt.hip): one workgroup per group, from the rows to the adapted
+// affine.  offsets is a host array [num_groups + 1]; ws holds at least plda_adapt_workspace_bytes(num_groups, d) bytes (the
+// offsets table and one slot; every further slot lets one more group run at a time).  The caller has checked every argument;
+// num_groups >= 1.
+int64_t plda_adapt_slot_bytes(int d);
+int64_t plda_adapt_workspace_bytes(int64_t num_groups, int d);
+hipError_t launch_plda_adapt(const float* x, int64_t ldx, const int64_t* offsets, int64_t num_groups, int d, const double* mean,
+                             const double* within_factor, const double* psi, double target_energy, int32_t* dim, double* eigval,
+                             double* pca, double* affine, double* psi_out, void* ws, int64_t ws_bytes, hipStream_t stream);
+
 // classifier-head validation loss (csrc/loss.hip): model/loss.py:9-48,80-384 without the logit matrix
 // kernel [E, ldk] -> class rows [C, ldr], columns normalised (tf.nn.l2_normalize) when `normalize`
 hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,

@@ -55,6 +55,32 @@ class Plda(object):
         return self.psi.shape[0]
 
 
+class AdaptedPlda(object):
+    """A Plda adapted to one recording (adapt_groups): `pca` [r, D] (the kept principal directions as rows), `affine`
+    [r, D + 1] (u = affine [x; 1] has within-class covariance I and between-class covariance diag(psi)), `psi` [r],
+    `eigenvalues` [D] (all of the recording's PCA spectrum, descending), float64; `dim` = r, `in_dim` = D.  prepare_enroll /
+    prepare_test take it in place of a Plda, with rows of length in_dim."""
+
+    def __init__(self, pca, affine, psi, eigenvalues):
+        self.pca = None if pca is None else np.ascontiguousarray(pca, dtype=np.float64)
+        self.affine = np.ascontiguousarray(affine, dtype=np.float64)
+        self.psi = np.ascontiguousarray(psi, dtype=np.float64)
+        self.eigenvalues = None if eigenvalues is None else np.ascontiguousarray(eigenvalues, dtype=np.float64)
+        if self.affine.ndim != 2 or self.psi.shape != (self.affine.shape[0],) or self.affine.shape[0] < 1 or self.affine.shape[1] < 2:
+            raise ValueError("AdaptedPlda: affine of shape %s, psi of shape %s" % (self.affine.shape, self.psi.shape))
+        if self.pca is not None and self.pca.shape != (self.affine.shape[0], self.affine.shape[1] - 1):
+            raise ValueError("AdaptedPlda: pca of shape %s for an affine of shape %s" % (self.pca.shape, self.affine.shape))
+        self._device = {}
+
+    @property
+    def dim(self):
+        return self.psi.shape[0]
+
+    @property
+    def in_dim(self):
+        return self.affine.shape[1] - 1
+
+
 # ----------------------------------------------------------------------------- model file
 def _text_tokens(data):
     """Whitespace-separated tokens of a text-mode object; a line end is the token '\\n' (it separates matrix rows)."""
@@ -186,10 +212,14 @@ def _norm_mode(normalize_length, simple_length_norm):
 
 
 def _affine(model, device, torch):
-    """[transform | -transform mean] as float32 on the device (the offset in float64 first), cached on the model."""
+    """[transform | -transform mean] as float32 on the device (the offset in float64 first; the affine of an AdaptedPlda,
+    rounded once), cached on the model."""
     key = ("affine", device)
     if key not in model._device:
-        t = np.concatenate([model.transform, -(model.transform @ model.mean)[:, None]], axis=1).astype(np.float32)
+        if isinstance(model, AdaptedPlda):
+            t = model.affine.astype(np.float32)
+        else:
+            t = np.concatenate([model.transform, -(model.transform @ model.mean)[:, None]], axis=1).astype(np.float32)
         model._device[key] = torch.from_numpy(np.ascontiguousarray(t)).to("cuda:%d" % device)
     return model._device[key]
 
@@ -246,8 +276,9 @@ class PldaRows(object):
 def _prepare(model, x, side, num_utts, normalize_length, simple_length_norm, device):
     n, d_in = scoring._shape2(x, "x")
     d = model.dim
-    if d_in != d:
-        raise ValueError("x: rows of dimension %d for a Plda of dimension %d" % (d_in, d))
+    d_model = model.in_dim if isinstance(model, AdaptedPlda) else d
+    if d_in != d_model:
+        raise ValueError("x: rows of dimension %d for a Plda of dimension %d" % (d_in, d_model))
     if d > 2048:
         raise ValueError("Plda of dimension %d: at most 2048" % d)
     if side == "enroll":
@@ -285,7 +316,7 @@ def _prepare(model, x, side, num_utts, normalize_length, simple_length_norm, dev
         bias = torch.empty((n,), dtype=torch.float32, device=xd.device) if side == "enroll" else None
         if n:
             stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.xv_plda_prepare(device, scoring._p(xd), d, n, d, scoring._p(aff), d + 1, d,
+            _lib.check(lib.xv_plda_prepare(device, scoring._p(xd), d_in, n, d_in, scoring._p(aff), d_in + 1, d,
                                            _norm_mode(normalize_length, simple_length_norm), 0 if side == "enroll" else 1,
                                            int(mixed), scoring._p(tabd), None if logd is None else scoring._p(logd), tab.shape[0],
                                            None if idx is None else scoring._p(idx), scoring._p(rows), d, scoring._p(packed), ldp,
@@ -306,12 +337,19 @@ def prepare_test(model, x, normalize_length=True, simple_length_norm=False, devi
     return _prepare(model, x, "test", None, normalize_length, simple_length_norm, device)
 
 
+def _same_model(a, b):
+    """Two models by their arrays: a Plda by psi, transform and mean, an AdaptedPlda by psi and affine."""
+    if isinstance(a, AdaptedPlda) != isinstance(b, AdaptedPlda):
+        return False
+    if isinstance(a, AdaptedPlda):
+        return np.array_equal(a.psi, b.psi) and np.array_equal(a.affine, b.affine)
+    return np.array_equal(a.psi, b.psi) and np.array_equal(a.transform, b.transform) and np.array_equal(a.mean, b.mean)
+
+
 def _operands(enroll, test, who):
     if not isinstance(enroll, PldaRows) or not isinstance(test, PldaRows) or enroll.side != "enroll" or test.side != "test":
         raise ValueError("%s: expected prepare_enroll(...) and prepare_test(...) results, in this order" % who)
-    if enroll.model is not test.model and not (np.array_equal(enroll.model.psi, test.model.psi)
-                                                and np.array_equal(enroll.model.transform, test.model.transform)
-                                                and np.array_equal(enroll.model.mean, test.model.mean)):
+    if enroll.model is not test.model and not _same_model(enroll.model, test.model):
         raise ValueError("%s: the two sides were prepared with different models" % who)
     if enroll.device != test.device:
         raise ValueError("%s: the two sides live on different devices (%d, %d)" % (who, enroll.device, test.device))
@@ -407,3 +445,124 @@ def llr_histograms(enroll, labels_e, test, labels_t, lo, hi, nbins=8192):
                                          C.c_void_p(hist.data_ptr()), C.c_void_p(hist.data_ptr() + 8 * nbins), C.c_void_p(stream)))
         h = hist.cpu().numpy().view(np.uint64)
     return h[0].copy(), h[1].copy()
+
+
+# ----------------------------------------------------------------------------- per-recording adaptation (csrc/plda_adapt.hip)
+ADAPT_MAX_DIM = 256
+ADAPT_BUDGET_BYTES = 1 << 30            # what the outputs and the workspace of one xv_plda_adapt call may take together
+
+
+def _check_target_energy(target_energy):
+    te = float(target_energy)
+    if not 0.0 < te <= 1.0:             # also refuses NaN
+        raise ValueError("target_energy must be in (0, 1], got %r" % (target_energy,))
+    return te
+
+
+def _adapt_device(model, device, torch):
+    """mean, transform^-1 (inverted once, float64, on the host) and psi as doubles on the device, cached on the model."""
+    key = ("adapt", device)
+    if key not in model._device:
+        dev = "cuda:%d" % device
+        model._device[key] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+                                   for a in (model.mean, np.linalg.inv(model.transform), model.psi))
+    return model._device[key]
+
+
+def _adapt_raw(model, xs, offsets, target_energy, device=0, want_pca=True, budget=None, ws_bytes=None):
+    """xv_plda_adapt over the groups of `xs` (a [N, D] float32 device tensor whose rows are sorted by group; group g owns
+    the rows offsets[g] .. offsets[g + 1]) -> (dim [G] int32, eigval [G, D], pca [G, D, D] or None, affine [G, D, D + 1],
+    psi [G, D], sweeps [G, 2] int32), numpy.  The groups go in runs whose outputs fit `budget` bytes (a run holds at least one
+    group), each with a workspace of one slot per group (xv_plda_adapt_slot_bytes) inside the same budget, or of exactly `ws_bytes`; by
+    the rule the result does not depend on either.  One device-to-host copy per run and output."""
+    te = _check_target_energy(target_energy)
+    d = model.dim
+    if not 1 <= d <= ADAPT_MAX_DIM:
+        raise ValueError("a Plda of dimension %d cannot be adapted: at most %d" % (d, ADAPT_MAX_DIM))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    groups = offsets.shape[0] - 1
+    if int(xs.shape[1]) != d:
+        raise ValueError("x: rows of dimension %d for a Plda of dimension %d" % (int(xs.shape[1]), d))
+    torch = scoring._need_device()
+    lib = _lib.load()
+    budget = ADAPT_BUDGET_BYTES if budget is None else int(budget)
+    per_group = 8 * (d * d + d * (d + 1) + 2 * d) + 4
+    slot = int(lib.xv_plda_adapt_slot_bytes(d))
+    run = max(1, (budget // 2) // per_group)
+    dims, eig, pcas, affs, psis, sweeps = [], [], [], [], [], []
+    with torch.cuda.device(device):
+        dev = torch.device("cuda:%d" % device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        mean, ainv, psi = _adapt_device(model, device, torch)
+        for g0 in range(0, groups, run):
+            g1 = min(groups, g0 + run)
+            cnt = g1 - g0
+            off = np.ascontiguousarray(offsets[g0:g1 + 1])
+            dim = torch.empty((cnt,), dtype=torch.int32, device=dev)
+            eigval = torch.zeros((cnt, d), dtype=torch.float64, device=dev)
+            pca = torch.zeros((cnt, d, d), dtype=torch.float64, device=dev)
+            affine = torch.zeros((cnt, d, d + 1), dtype=torch.float64, device=dev)
+            psi_out = torch.zeros((cnt, d), dtype=torch.float64, device=dev)
+            least = int(lib.xv_plda_adapt_workspace(cnt, d))
+            if least < 0:
+                raise _lib.XvError(least, "xv_plda_adapt_workspace: bad arguments")
+            if ws_bytes is None:
+                slots = max(1, min(cnt, (budget // 2) // slot))
+                size = least + (slots - 1) * slot
+            else:
+                size = int(ws_bytes)
+            ws = torch.empty((max(size, 8),), dtype=torch.uint8, device=dev)
+            _lib.check(lib.xv_plda_adapt(device, scoring._p(xs), d, off.ctypes.data_as(C.c_void_p), cnt, d, scoring._p(mean),
+                                         scoring._p(ainv), scoring._p(psi), te, scoring._p(dim), scoring._p(eigval), scoring._p(pca),
+                                         scoring._p(affine), scoring._p(psi_out), scoring._p(ws), size, C.c_void_p(stream)))
+            dims.append(dim.cpu().numpy())
+            eig.append(eigval.cpu().numpy())
+            if want_pca:
+                pcas.append(pca.cpu().numpy())
+            affs.append(affine.cpu().numpy())
+            psis.append(psi_out.cpu().numpy())
+            sweeps.append(ws[8 * (cnt + 1):16 * cnt + 8].cpu().numpy().view(np.int32).reshape(cnt, 2).copy())
+    if not groups:
+        return (np.zeros(0, np.int32), np.zeros((0, d)), np.zeros((0, d, d)) if want_pca else None, np.zeros((0, d, d + 1)),
+                np.zeros((0, d)), np.zeros((0, 2), np.int32))
+    return (np.concatenate(dims), np.concatenate(eig), np.concatenate(pcas) if want_pca else None, np.concatenate(affs),
+            np.concatenate(psis), np.concatenate(sweeps))
+
+
+def _warn_fallback(dims, who):
+    bad = int(np.sum(np.asarray(dims) == 0))
+    if bad:
+        import warnings
+        warnings.warn("%s: %d of %d groups could not be adapted (fewer than 2 rows, no variance, or an iteration that did not "
+                      "converge) and are scored with the global model" % (who, bad, len(dims)), RuntimeWarning, stacklevel=3)
+
+
+def adapt_groups(model, x, groups, target_energy, device=0):
+    """Kaldi's `ivector-plda-scoring-dense --target-energy` adaptation for every group (recording) of the rows x [N, D]
+    (the rows behind the mean / transform / normalize front, numpy or a device tensor): the PCA of the group's own rows keeps
+    the leading directions that hold `target_energy` of the variance plus one, the global model is projected there and
+    diagonalised again (include/xvec_hip.h, xv_plda_adapt, states the rule).  -> OrderedDict group -> AdaptedPlda in sorted
+    group order, None for a group that falls back to the global model (fewer than 2 rows, no variance, a projected
+    within-class covariance that is not positive definite, an iteration that did not converge); one warning per call counts
+    them.  `groups` [N] holds one id per row (anything np.unique sorts)."""
+    import collections
+    n, _ = scoring._shape2(x, "x")
+    ids = np.asarray(groups).reshape(-1)
+    if ids.shape[0] != n:
+        raise ValueError("groups: %d ids for %d rows" % (ids.shape[0], n))
+    _check_target_energy(target_energy)
+    names, inverse = np.unique(ids, return_inverse=True)
+    order = np.argsort(inverse, kind="stable")
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(inverse, minlength=len(names)))]).astype(np.int64)
+    torch = scoring._need_device()
+    with torch.cuda.device(device):
+        xd = scoring._rows(x, device, "x")
+        xs = xd[torch.from_numpy(order).to(xd.device)].contiguous()
+    dim, eigval, pca, affine, psi, _ = _adapt_raw(model, xs, offsets, target_energy, device)
+    _warn_fallback(dim, "adapt_groups")
+    out = collections.OrderedDict()
+    for g, name in enumerate(names):
+        r = int(dim[g])
+        key = name.item() if hasattr(name, "item") else name
+        out[key] = AdaptedPlda(pca[g, :r], affine[g, :r], psi[g, :r], eigval[g]) if r else None
+    return out

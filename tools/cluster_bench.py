@@ -9,6 +9,12 @@
            --subset smallest recordings of the batch, and that is stated in the output.  With scipy the largest difference of
            the merge heights over the first --subset recordings is reported as well (tie-free data: the logs are comparable)
 
+  --target-energy E   instead of the above: the per-recording PLDA adaptation (xv_plda_adapt, csrc/plda_adapt.hip) of the same
+           batch plus the single recording in one call, at every --adapt-dims dimension (128 and 200): the time of xv_plda_adapt
+           alone, of the whole cluster.plda call with and without the option (wall clock around a synchronised call), the sweeps
+           the two Jacobi iterations needed, and the same adaptation by the float64 numpy oracle
+           (tests/helpers/ref_plda_adapt.adapt, numpy.linalg.eigh) on the host, one recording after the other
+
 Device times are hipEvent times around one call sequence, after a warm-up run of the same shapes; the working matrix is refilled
 before every clustering run because xv_ahc consumes it.  --repeats runs each (3), all reported, the median quoted.  Prints one
 JSON line; profiles/clustering.md keeps the numbers."""
@@ -33,6 +39,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--subset", type=int, default=10, help="recordings compared in detail (and timed with ref_cluster without scipy)")
     ap.add_argument("--no-host", action="store_true", help="skip the host comparison")
+    ap.add_argument("--target-energy", type=float, default=None, help="time the per-recording PLDA adaptation instead")
+    ap.add_argument("--adapt-dims", type=int, nargs="+", default=[128, 200])
     args = ap.parse_args()
     import torch
     import __graft_entry__ as g
@@ -49,6 +57,74 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
     out = {"device": torch.cuda.get_device_name(0), "dim": d, "repeats": args.repeats}
+
+    def adapt_leg(dim, sizes):
+        """xv_plda_adapt over recordings drawn from a random PLDA model of dimension `dim` (2..8 speakers each)."""
+        sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+        import ref_plda
+        import ref_plda_adapt
+        from tf_kaldi_speaker_amd import cluster, plda
+        te = args.target_energy
+        mean, transform, psi = ref_plda.random_model(rng, dim)
+        model = plda.Plda(mean, transform, psi)
+        recs = []
+        for n in sizes:
+            k = int(rng.integers(2, 9))
+            x, _ = ref_plda.draw(rng, mean, transform, psi, k, (n + k - 1) // k)
+            recs.append(np.ascontiguousarray(x[rng.permutation(len(x))[:n]], dtype=np.float32))
+        x = np.concatenate(recs)
+        groups = np.repeat(np.arange(len(sizes)), sizes)
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        xs = torch.from_numpy(x).to(dev)
+        plda._adapt_raw(model, xs, offsets, te, want_pca=False)             # warm-up, same shapes
+        times = []
+        for _ in range(args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dim_out, _, _, _, _, sweeps = plda._adapt_raw(model, xs, offsets, te, want_pca=False)
+            times.append(1e3 * (time.perf_counter() - t0))                   # the call and its copies back; synchronised by them
+        # the kernel alone: hipEvents around one xv_plda_adapt with preallocated outputs
+        cnt = len(sizes)
+        bufs = [torch.empty(s, dtype=torch.float64, device=dev) for s in ((cnt, dim), (cnt, dim, dim), (cnt, dim, dim + 1), (cnt, dim))]
+        dims_dev = torch.empty((cnt,), dtype=torch.int32, device=dev)
+        mean_d, ainv_d, psi_d = plda._adapt_device(model, 0, torch)
+        size = int(lib.xv_plda_adapt_workspace(cnt, dim)) + (cnt - 1) * int(lib.xv_plda_adapt_slot_bytes(dim))
+        ws = torch.empty((size,), dtype=torch.uint8, device=dev)
+        kernel = []
+        for _ in range(args.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _lib.check(lib.xv_plda_adapt(0, P(xs), dim, offsets.ctypes.data_as(C.c_void_p), cnt, dim, P(mean_d), P(ainv_d), P(psi_d), te,
+                                         P(dims_dev), P(bufs[0]), P(bufs[1]), P(bufs[2]), P(bufs[3]), P(ws), size, stream))
+            e1.record()
+            e1.synchronize()
+            kernel.append(e0.elapsed_time(e1))
+        res = {"dim": dim, "groups": cnt, "rows_total": int(sum(sizes)), "rows_max": int(max(sizes)), "target_energy": te,
+               "workspace_mbytes": 1e-6 * size, "adapt_kernel_ms": float(np.median(kernel)), "adapt_kernel_all_ms": kernel,
+               "adapt_call_ms": float(np.median(times)), "adapt_call_all_ms": times,
+               "kept_dims_min_median_max": [int(dim_out.min()), float(np.median(dim_out)), int(dim_out.max())],
+               "fallbacks": int(np.sum(dim_out == 0)),
+               "sweeps_pca_min_median_max": [int(sweeps[:, 0].min()), float(np.median(sweeps[:, 0])), int(sweeps[:, 0].max())],
+               "sweeps_model_min_median_max": [int(sweeps[:, 1].min()), float(np.median(sweeps[:, 1])), int(sweeps[:, 1].max())]}
+        for name, kw in (("cluster_plda_global_ms", {}), ("cluster_plda_adapted_ms", {"target_energy": te})):
+            cluster.plda(model, xs, groups, threshold=0.0, normalize=False, **kw)          # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cluster.plda(model, xs, groups, threshold=0.0, normalize=False, **kw)
+            res[name] = 1e3 * (time.perf_counter() - t0)
+        if not args.no_host:
+            t0 = time.perf_counter()
+            kept = [ref_plda_adapt.adapt(mean, transform, psi, r, te).dim for r in recs]
+            res["host_numpy_ms"] = 1e3 * (time.perf_counter() - t0)
+            res["host_what"] = "tests/helpers/ref_plda_adapt.adapt (numpy float64: covariance, eigh, cholesky, eigh), one recording after the other"
+            res["kept_dims_equal_to_host"] = int(np.sum(np.asarray(kept) == dim_out))
+        return res
+
+    if args.target_energy is not None:
+        sizes = [int(v) for v in rng.integers(200, 1001, args.groups)] + [args.single]
+        out["adapt"] = [adapt_leg(dim, sizes) for dim in args.adapt_dims]
+        print(json.dumps(out))
+        return
 
     def rows_of(n):
         """n prepared rows: 2..8 speaker centroids + noise, like the sub-segments of a conversation."""
