@@ -597,6 +597,57 @@ int xv_loss_classifier(int device, const float* x_dev, int64_t ldx, int64_t n, i
                        double fa, float* loss_dev, float* target_dev, float* lse_dev, int32_t* top1_dev, void* ws_dev,
                        int64_t ws_bytes, void* stream);
 
+/* ---- metric-learning loss heads on the GPU (csrc/metric_loss.hip): what validation needs for a checkpoint trained with
+ * `semihard_triplet_loss` (model/loss.py:387-527) or `angular_triplet_loss` (:530-663; validated with `e2e_valid_loss`,
+ * :666-734, model/trainer.py:424-427).  Pinned to the reference's float64 numpy twins (model/test_utils.py:21-86, 118-154,
+ * 694-857) through tests/golden/metric_*.npz.  Everything is double, from float32 rows.
+ * A group is one batch: rows x_1 .. x_B of length d, labels l_1 .. l_B (any int32 values).
+ *   u_i = x_i s_i, s_i = 1 / sqrt(max(sum_t x_it^2, 1e-12)) (l2_scaling, model/common.py:45-58); G(a, b) = sum_t a_t b_t,
+ *   a pure function of the VALUES of the two rows (not of their position, tile or group).
+ * XV_METRIC_SEMIHARD: v = u with `normalize`, else x.  n_i = G(v_i, v_i), D2(i, j) = max(n_i - 2 G(v_i, v_j) + n_j, 0),
+ *   d = D2 with `squared`, else sqrt(D2); d(i, i) = 0.  For every ordered pair (i, j), j != i, l_j == l_i, over the negatives k
+ *   (l_k != l_i): z = the least d(i, k) > d(i, j) (strict), or the largest d(i, k) if there is none; the term is
+ *   max(margin + d(i, j) - z, 0).  loss = sum / max(pairs, 1e-16).  An anchor without a negative contributes nothing.
+ * XV_METRIC_ANGULAR_ALL / _HARD: c(i, j) = clip(G(u_i, u_j), -1, 1); pos(c) by pos_head: XV_LOSS_ASOFTMAX margin = m: c
+ *   (m = 1), 2 sign(c) c^2 - 1 (m = 2), s3 (8 c^4 - 8 c^2 + 1) + s4 with s0 = sign(c), s3 = sign(2 c^2 - 1) s0,
+ *   s4 = 2 s0 + s3 - 3 (m = 4; sign(0) = 0; any other m is XV_ERR_UNSUPPORTED); XV_LOSS_AMSOFTMAX: c - margin;
+ *   XV_LOSS_ARCSOFTMAX: t = c cos(margin) - sqrt(1 - c^2) sin(margin), -t - 2 when c <= cos(pi - margin), else t.
+ *   ALL: over anchors i, positives j != i and negatives k, t = c(i, k) - pos(c(i, j)); S = sum max(t, 0), A = #{t > 1e-12},
+ *   V = the number of triplets; loss = S / (A + 1e-16).  HARD: hp_i = min of pos(c(i, j)) over l_j == l_i (j = i included),
+ *   hn_i = max of c(i, k) over the negatives, row = max(hn_i - hp_i, 0), 0 without a negative; loss = the mean over the B rows.
+ * XV_METRIC_GE2E_SOFTMAX / _CONTRASTIVE: classes = the distinct labels in order of first appearance; s_c = the sum of u_i over
+ *   the class in row order; chat_c = unit(s_c), e_i = unit(s_c(i) - u_i) (unit = the scaling above: a class of one row has
+ *   e_i = 0); sim(i, c) = G(u_i, chat_c), sim(i, c(i)) = G(u_i, e_i); z = w sim + b.  SOFTMAX: row = lse(z_i) - z_i,c(i)
+ *   (max-shifted), top1_i = the label of the arg-max class, the earliest class among equals.  CONTRASTIVE: row =
+ *   1 - sigma(z_i,c(i)) + max(0, max_{c != c(i)} sigma(z_ic)), sigma from exp(-|z|).  loss = the mean over the rows.
+ *   e2e_valid_loss is SOFTMAX with w = 20, b = 0.
+ * Layout: group g owns the rows offsets[g] .. offsets[g + 1]) of x_dev [*, ldx]; labels_dev and the three row outputs are
+ *   indexed by the same row numbers (total = offsets[G]); offsets_host is a host array, consumed before the call returns.
+ *   row_loss_dev = the anchor's un-normalised sum (the row's loss for HARD and GE2E); row_count_dev = the anchor's positive
+ *   pairs (SEMIHARD), its active triplets (ALL), 1 otherwise; row_top1_dev (GE2E; may be NULL).  group_loss_dev [G] = the
+ *   sequential double sum of the group's row_loss in row order, normalised as above; group_count_dev [G, 2] = (pairs, 0),
+ *   (A, V), (B, 0), (B, rows whose top1 is their own label).
+ *   A group's outputs are a pure function of its own rows, labels and the options: the same bits on every repeat, alone or in
+ *   any batch, in any group order, for every legal ws_bytes.  No floating-point atomics.
+ * Workspace: xv_metric_loss_workspace is the least ws_bytes (tables, three doubles per row and, for groups over 1024 rows or
+ *   the GE2E kinds, one slot of 128 (B | 1) resp. 8 B (d + B) bytes rounded up to 256, B = the largest group); every further slot lets
+ *   one more workgroup run at a time (up to 1024); xv_metric_loss_slot_bytes is the size of one (0: the kind needs none for
+ *   groups of max_rows rows).  Both return XV_ERR_INVALID for arguments xv_metric_loss refuses.
+ *   ws_dev must be 8-byte aligned.
+ * 1 <= d <= 4096, 1 .. 4096 rows per group, ascending offsets from >= 0, ldx >= d, a known kind (and pos_head for the angular
+ *   kinds), finite margin, w, b: XV_ERR_INVALID otherwise; too little workspace: XV_ERR_WORKSPACE.  Every argument check comes
+ *   before the first HIP call and the outputs are untouched on any error.  num_groups = 0 returns XV_OK and touches nothing. */
+enum { XV_METRIC_SEMIHARD = 0, XV_METRIC_ANGULAR_ALL = 1, XV_METRIC_ANGULAR_HARD = 2, XV_METRIC_GE2E_SOFTMAX = 3,
+       XV_METRIC_GE2E_CONTRASTIVE = 4 };
+int64_t xv_metric_loss_workspace(int64_t num_groups, const int64_t* offsets_host /* [num_groups + 1] */, int d, int kind);
+int64_t xv_metric_loss_slot_bytes(int max_rows, int d, int kind);
+int xv_metric_loss(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host /* [num_groups + 1] */,
+                   int64_t num_groups, int d, const int32_t* labels_dev, int kind,
+                   int pos_head /* XV_LOSS_ASOFTMAX | _AMSOFTMAX | _ARCSOFTMAX, angular kinds */, double margin, int squared,
+                   int normalize, double w, double b, double* row_loss_dev /* [total] */, int64_t* row_count_dev /* [total] */,
+                   int32_t* row_top1_dev /* [total] or NULL */, double* group_loss_dev /* [G] */,
+                   int64_t* group_count_dev /* [G, 2] */, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- back-end training statistics on the GPU (csrc/backend.hip): the sums behind `ivector-mean`, `ivector-compute-lda` and
  * `ivector-compute-plda` (egs/voxceleb/v1/run.sh:384-400, egs/sre/v1/run.sh:399-411); the d x d linear algebra behind them is
  * host float64 (tf_kaldi_speaker_amd.backend).  Kaldi is absent from the reference tree: **parity unpinned**.

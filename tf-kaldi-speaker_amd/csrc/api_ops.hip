@@ -1,5 +1,5 @@
-// C ABI of libxvec_hip.so, the stateless ops: front-end, scoring, PLDA, back-end statistics, loss heads, clustering and
-// calibration.  Every wrapper validates its arguments and hands one launch (or a short chain) to with_device().
+// C ABI of libxvec_hip.so, the stateless ops: front-end, scoring, PLDA, back-end statistics, loss heads (classifier and metric), clustering
+// and calibration.  Every wrapper validates its arguments and hands one launch (or a short chain) to with_device().
 #include "xv_model.h"
 
 using namespace xv;
@@ -546,6 +546,62 @@ int xv_plda_adapt(int device, const float* x_dev, int64_t ldx, const int64_t* of
   return with_device(device, "xv_plda_adapt", [&] {
     return launch_plda_adapt(x_dev, ldx, offsets_host, num_groups, d, mean_dev, within_factor_dev, psi_dev, target_energy, dim_dev,
                              eigval_dev, pca_dev, affine_dev, psi_out_dev, ws_dev, ws_bytes, to_stream(stream));
+  });
+}
+
+// shared argument check of the two metric-loss entry points
+static int metric_groups(const char* who, int64_t num_groups, const int64_t* offsets_host, int d, int kind) {
+  if (kind < XV_METRIC_SEMIHARD || kind > XV_METRIC_GE2E_CONTRASTIVE) return fail(nullptr, XV_ERR_INVALID, "%s: unknown kind %d", who, kind);
+  if (d < 1 || d > 4096) return fail(nullptr, XV_ERR_INVALID, "%s: 1 <= d <= 4096, got %d", who, d);
+  if (num_groups < 0 || num_groups > INT32_MAX) return fail(nullptr, XV_ERR_INVALID, "%s: bad group count %lld", who, (long long)num_groups);
+  if (num_groups == 0) return XV_OK;
+  if (!offsets_host) return fail(nullptr, XV_ERR_INVALID, "%s: null pointer", who);
+  if (offsets_host[0] < 0) return fail(nullptr, XV_ERR_INVALID, "%s: the first offset is negative", who);
+  for (int64_t g = 0; g < num_groups; ++g) {
+    const int64_t rows = offsets_host[g + 1] - offsets_host[g];
+    if (rows < 1 || rows > 4096)
+      return fail(nullptr, XV_ERR_INVALID, "%s: group %lld has %lld rows (1 .. 4096; the offsets ascend)", who, (long long)g, (long long)rows);
+  }
+  return XV_OK;
+}
+
+int64_t xv_metric_loss_workspace(int64_t num_groups, const int64_t* offsets_host, int d, int kind) {
+  if (const int rc = metric_groups("xv_metric_loss_workspace", num_groups, offsets_host, d, kind)) return rc;
+  if (num_groups == 0) return 0;
+  return metric_loss_workspace_bytes(num_groups, offsets_host, d, kind);
+}
+
+int64_t xv_metric_loss_slot_bytes(int max_rows, int d, int kind) {
+  const int64_t offsets[2] = {0, max_rows};
+  if (const int rc = metric_groups("xv_metric_loss_slot_bytes", 1, offsets, d, kind)) return rc;
+  return metric_loss_slot_bytes(max_rows, d, kind);
+}
+
+int xv_metric_loss(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host, int64_t num_groups, int d,
+                   const int32_t* labels_dev, int kind, int pos_head, double margin, int squared, int normalize, double w, double b,
+                   double* row_loss_dev, int64_t* row_count_dev, int32_t* row_top1_dev, double* group_loss_dev,
+                   int64_t* group_count_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = metric_groups("xv_metric_loss", num_groups, offsets_host, d, kind)) return rc;
+  if (num_groups == 0) return XV_OK;
+  if (!x_dev || !labels_dev || !row_loss_dev || !row_count_dev || !group_loss_dev || !group_count_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss: null pointer");
+  if (ldx < d) return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss: ldx = %lld < d = %d", (long long)ldx, d);
+  if (!std::isfinite(margin) || !std::isfinite(w) || !std::isfinite(b)) return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss: margin, w and b must be finite");
+  if (kind == XV_METRIC_ANGULAR_ALL || kind == XV_METRIC_ANGULAR_HARD) {
+    if (pos_head < XV_LOSS_ASOFTMAX || pos_head > XV_LOSS_ARCSOFTMAX) return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss: unknown pos_head %d", pos_head);
+    if (pos_head == XV_LOSS_ASOFTMAX && margin != 1.0 && margin != 2.0 && margin != 4.0)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_metric_loss: m=%g is not supported (asoftmax: 1, 2 or 4)", margin);   // loss.py:168
+  }
+  const int64_t need = metric_loss_workspace_bytes(num_groups, offsets_host, d, kind);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_metric_loss: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7)
+    return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss: the workspace must be 8-byte aligned (it holds offsets and doubles)");
+  return with_device(device, "xv_metric_loss", [&] {
+    return launch_metric_loss(x_dev, ldx, offsets_host, num_groups, d, labels_dev, kind, pos_head, margin, squared ? 1 : 0,
+                              normalize ? 1 : 0, w, b, row_loss_dev, row_count_dev, row_top1_dev, group_loss_dev, group_count_dev,
+                              ws_dev, ws_bytes, to_stream(stream));
   });
 }
 

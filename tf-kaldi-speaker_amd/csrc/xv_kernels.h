@@ -299,6 +299,16 @@ hipError_t launch_plda_adapt(const float* x, int64_t ldx, const int64_t* offsets
                              const double* within_factor, const double* psi, double target_energy, int32_t* dim, double* eigval,
                              double* pca, double* affine, double* psi_out, void* ws, int64_t ws_bytes, hipStream_t stream);
 
+// Metric-learning loss heads (csrc/metric_loss.hip): semi-hard triplet, angular triplet (all / hard), ge2e (softmax /
+// contrastive), per group of rows.  offsets is a host array [num_groups + 1]; ws holds at least metric_loss_workspace_bytes
+// bytes.  The caller has checked every argument (ascending offsets, 1 .. 4096 rows per group); num_groups >= 1.
+int64_t metric_loss_slot_bytes(int max_rows, int d, int kind);
+int64_t metric_loss_workspace_bytes(int64_t num_groups, const int64_t* offsets, int d, int kind);
+hipError_t launch_metric_loss(const float* x, int64_t ldx, const int64_t* offsets, int64_t num_groups, int d, const int32_t* labels,
+                              int kind, int pos_head, double margin, int squared, int normalize, double w, double b,
+                              double* row_loss, int64_t* row_count, int32_t* row_top1, double* group_loss, int64_t* group_count,
+                              void* ws, int64_t ws_bytes, hipStream_t stream);
+
 // classifier-head validation loss (csrc/loss.hip): model/loss.py:9-48,80-384 without the logit matrix
 // kernel [E, ldk] -> class rows [C, ldr], columns normalised (tf.nn.l2_normalize) when `normalize`
 hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,

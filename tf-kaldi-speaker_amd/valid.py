@@ -5,8 +5,10 @@
     python -m tf_kaldi_speaker_amd.valid [--gpu N] [--checkpoint NAME] [--precision P] [--no-eer] [--append]
                                          model_dir valid_dir valid_spklist
 
-prints one line `step <step> loss <loss> acc <top-1 accuracy> eer <eer>`.  The batch plan (plan_batches, read_batch) is pure
-host code; the forward pass, the loss heads (losses.py) and the pairwise EER (scoring.py) run on the GPU and have no CPU path."""
+prints one line `step <step> loss <loss> acc <top-1 accuracy> eer <eer>`.  The batch plan (plan_batches, plan_end2end_batches,
+read_batch) is pure host code; the forward pass, the loss heads (losses.py, metric_losses.py) and the pairwise EER (scoring.py)
+run on the GPU and have no CPU path.  A checkpoint trained with `semihard_triplet_loss` or `angular_triplet_loss` goes through
+metric_valid instead of Trainer.valid (model/trainer.py:407-436: the angular triplet loss is validated with e2e_valid_loss)."""
 import argparse
 import collections
 import os
@@ -107,6 +109,87 @@ def plan_for_params(data, spklist, params):
                         (int(p["min_segment_len"]) + int(p["max_segment_len"])) // 2, p.get("valid_max_iterations"))
 
 
+def plan_end2end_batches(data, spklist, num_speakers, num_segments, target_len, max_iterations=None):
+    """Batches of N speakers x M segments, what KaldiDataRandomQueue (dataset/data_loader.py:289-356) feeds the end-to-end
+    losses, made deterministic where the reference draws from os.urandom -> [Batch(keys, rxfiles, labels, length)]:
+
+      1. an utterance is eligible when utt2num_frames > target_len (strict, :334); the speakers are those with an eligible
+         utterance, in ascending index, S of them.  S < N is a ValueError (the reference would draw a speaker twice there and
+         make two classes of one voice);
+      2. `max_iterations` batches (valid_max_iterations: the reference's queue never ends), ceil(S / N) without it;
+      3. batch b takes the speakers (b N + i) mod S, i = 0 .. N - 1; the t-th appearance of a speaker (t from 0) takes its
+         eligible utterances (t M + j) mod E, j = 0 .. M - 1, in feats.scp order (the wrap is the list duplication of :345-346);
+      4. every segment is the frames [0, target_len); rows are speaker-major and the label is the speaker index."""
+    n, m, target_len = int(num_speakers), int(num_segments), int(target_len)
+    if n < 1 or m < 1 or target_len < 1:
+        raise ValueError("speakers, segments and segment length must be positive, got %d, %d and %d" % (n, m, target_len))
+    spk2features, _ = read_speaker_info(data, spklist)
+    frames = read_utt2num_frames(data)
+    eligible = {}
+    for spk in sorted(spk2features):
+        utts = [(key, rx) for key, rx in spk2features[spk] if frames[key] > target_len]
+        if utts:
+            eligible[spk] = utts
+    speakers = sorted(eligible)
+    if len(speakers) < n:
+        raise ValueError("%d speakers have an utterance of more than %d frames, a batch needs %d" % (len(speakers), target_len, n))
+    num_batches = -(-len(speakers) // n) if max_iterations is None else int(max_iterations)
+    seen = dict.fromkeys(speakers, 0)
+    out = []
+    for b in range(num_batches):
+        keys, rxfiles, labels = [], [], []
+        for i in range(n):
+            spk = speakers[(b * n + i) % len(speakers)]
+            utts = eligible[spk]
+            for j in range(m):
+                key, rx = utts[(seen[spk] * m + j) % len(utts)]
+                keys.append(key)
+                rxfiles.append(rx)
+                labels.append(spk)
+            seen[spk] += 1
+        out.append(Batch(keys, rxfiles, np.array(labels, dtype=np.int32), target_len))
+    return out
+
+
+METRIC_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss")      # validated by metric_valid, not by Trainer.valid
+
+
+def metric_valid(trainer, data, spklist, batch_type="softmax", output_embeddings=False):
+    """Trainer.valid for a checkpoint trained with a metric-learning loss -> (loss, embeddings or None, labels or None).
+    The network runs to the `output` endpoint exactly as Trainer.valid runs it; the batches are those of plan_for_params
+    (batch_type "softmax") or of plan_end2end_batches with num_valid_speakers_per_batch x num_valid_segments_per_speaker
+    ("end2end", model/trainer.py:839-853); all of them go to the head metric_losses.from_params names in ONE call, and the
+    loss is the mean of the batch losses.  trainer.valid_accuracy holds the top-1 accuracy of the ge2e head, nan otherwise."""
+    from . import metric_losses
+    assert batch_type == "softmax" or batch_type == "end2end", "The batch_type can only be softmax or end2end"
+    params = trainer.params
+    head = metric_losses.from_params(params, validation=True, device=trainer._device_index)
+    p = params.dict
+    if batch_type == "end2end":
+        assert "num_valid_speakers_per_batch" in p and "num_valid_segments_per_speaker" in p, \
+            "Valid parameters should be set if E2E loss is selected"                  # trainer.py:843-844
+        plan = plan_end2end_batches(data, spklist, p["num_valid_speakers_per_batch"], p["num_valid_segments_per_speaker"],
+                                    (int(p["min_segment_len"]) + int(p["max_segment_len"])) // 2, p.get("valid_max_iterations"))
+    else:
+        plan = plan_for_params(data, spklist, params)
+    if not plan:
+        raise ValueError("no validation batch in %s" % data)
+    trainer.build("predict")
+    trainer.embeddings = "output"                                                     # valid_setup, trainer.py:460
+    embs, labs, cache = [], [], {}
+    for batch in plan:
+        embs.append(trainer.predict(read_batch(batch, trainer.dim, cache)))
+        labs.append(batch.labels)
+    offsets = np.concatenate([[0], np.cumsum([len(l) for l in labs])]).astype(np.int64)
+    emb, labels = np.concatenate(embs, axis=0), np.concatenate(labs, axis=0)
+    res = head(emb, labels, offsets)
+    trainer.valid_num_batches = len(plan)
+    trainer.valid_accuracy = float(np.mean(res.top1 == labels)) if res.top1 is not None else float("nan")
+    if output_embeddings:
+        return res.loss, emb, labels
+    return res.loss, None, None
+
+
 def read_batch(batch, dim, cache=None):
     """-> float32 [B, length, dim]: the first `length` frames of every utterance; columns beyond `dim` are dropped
     (model/trainer.py:865-866), fewer than `dim` is a ValueError.  `cache` ({rxfile: matrix}) spares re-reading wrapped rows."""
@@ -167,14 +250,16 @@ def main(argv=None):
     from .trainer import Trainer
     trainer = Trainer(params, args.model_dir, dim, single_cpu=True, device=args.gpu if args.gpu >= 0 else None,
                       precision=args.precision or None)
-    trainer.build("valid")
+    metric = params.dict.get("loss_func") in METRIC_LOSSES
+    trainer.build("predict" if metric else "valid")
     if args.checkpoint:
         weights, step = model_io.load_weights(nnet_dir, name=args.checkpoint)
         if weights is None:
             sys.exit("Cannot find checkpoint %s in %s" % (args.checkpoint, nnet_dir))
         trainer.load_weights(weights, step)
-    loss, emb, labels = trainer.valid(args.valid_dir, args.valid_spklist, batch_type=params.dict.get("batch_type", "softmax"),
-                                      output_embeddings=not args.no_eer)
+    run = (lambda *a, **k: metric_valid(trainer, *a, **k)) if metric else trainer.valid
+    loss, emb, labels = run(args.valid_dir, args.valid_spklist, batch_type=params.dict.get("batch_type", "softmax"),
+                            output_embeddings=not args.no_eer)
     eer = None
     if not args.no_eer:
         eer = scoring.pairwise_eer(emb, labels, device=trainer._device_index)[0]
