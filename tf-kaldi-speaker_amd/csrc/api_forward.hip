@@ -167,10 +167,19 @@ int launch_first_layer(const Run& r, const PlanStep& st, const Layer& L, GemmArg
   if (st.scratch_off < 0) return fail(h, XV_ERR_STATE, "im2col layer has no scratch");
   a.Xsb = r.raw(st.scratch_off);
   a.Wsb = L.wsb.p; a.Wfr = L.wfr.p;
+  bool guarded = false;               // the staging pass has taken the per-utterance maxima itself
   if (L.cin_pad) {
     // the 30-dim feature rows become SB rows of one 32-channel block (9.8 MB for 256 x 300 frames instead of the
     // 48 MB of materialised 5-frame rows); the layer is then an ordinary 5-tap convolution over them
-    XV_HIP(h, launch_im2col_sb(r.feats, r.feat_ld, L.cin, 1, st.rows_in, r.raw(st.scratch_off), L.cin_pad, r.f16, r.ovf(), r.s));
+    const std::vector<int32_t>& ho = r.p->lvl_offsets[0];
+    guarded = feat_stage_sb_ok(L.cin_pad, r.B) && (int)ho.size() == r.B + 1 && ho[r.B] == st.rows_in;
+    if (guarded) {                    // staging and the per-utterance guard in one pass (csrc/pool.hip)
+      int max_len = 0;
+      for (int b = 0; b < r.B; ++b) max_len = std::max(max_len, ho[b + 1] - ho[b]);
+      XV_HIP(h, launch_feat_stage_sb(r.feats, r.feat_ld, L.cin, r.off, r.B, max_len, r.raw(st.scratch_off), L.cin_pad, r.f16, r.ovf(), r.s));
+    } else {
+      XV_HIP(h, launch_im2col_sb(r.feats, r.feat_ld, L.cin, 1, st.rows_in, r.raw(st.scratch_off), L.cin_pad, r.f16, r.ovf(), r.s));
+    }
     a.ldsbx = L.cin_pad;
     a.cin = L.cin_pad;
     a.K = L.w * L.cin_pad;
@@ -181,7 +190,7 @@ int launch_first_layer(const Run& r, const PlanStep& st, const Layer& L, GemmArg
     a.ldsbx = L.Kpad;
     a.cin = a.K;
   }
-  if (r.f16) XV_HIP(h, launch_feat_utt_guard(r.feats, r.feat_ld, L.cin, r.off, r.B, r.ovf(), r.s));
+  if (r.f16 && !guarded) XV_HIP(h, launch_feat_utt_guard(r.feats, r.feat_ld, L.cin, r.off, r.B, r.ovf(), r.s));
   XV_HIP(h, launch_gemm_bf16x3(a, r.s));
   return XV_OK;
 }

@@ -403,8 +403,8 @@ int xv_finalize(xv_handle* h) {
       XV_HIP(h, hipMemcpy(h->post_vec.p, vec.data(), vec.size() * sizeof(float), hipMemcpyHostToDevice));
     }
   }
-  XV_HIP(h, h->ovf_flag.alloc((kFlagWords + kFeatMaxSlots) * sizeof(int)));
-  XV_HIP(h, hipMemset(h->ovf_flag.p, 0, (kFlagWords + kFeatMaxSlots) * sizeof(int)));
+  XV_HIP(h, h->ovf_flag.alloc(kFlagBufWords * sizeof(int)));
+  XV_HIP(h, hipMemset(h->ovf_flag.p, 0, kFlagBufWords * sizeof(int)));
   XV_HIP(h, hipDeviceSynchronize());
   for (auto& kv : h->tensors) { kv.second.data.clear(); kv.second.data.shrink_to_fit(); }
   h->finalized = true;

@@ -21,6 +21,7 @@
 //    exactly like the A tile and needs no bounds checks.
 //  * XCD-aware block order: consecutive ids on one XCD (id % 8) walk the N tiles of the same M
 //    tile, so the A panel is fetched once per XCD L2.
+//  * Segment-level layers (M <= 512, dense) have a kernel of their own: gemm_f32_seg_kernel below.
 #include <mutex>
 
 #include "xv_epilogue.h"
@@ -167,6 +168,122 @@ __global__ void splitk_reduce_kernel(GemmArgs p) {
   }
 }
 
+// ------------------------------------------------------------------------------ segment-level layers
+// M <= 512 rows (one per utterance: tdnn6 / tdnn7, the extended TDNN's tdnn12, the ResNet's dense1/2, the attention post
+// layers), dense, fp32 out.  The 128 x 128 kernel above gives such a layer 8 tiles, so it was run split-K over the chip with the
+// partial sums going through HBM and a second launch adding them.  Here one launch does it: a workgroup owns a 32 x 16 output
+// tile (256 x 512 -> 256 workgroups, one per CU), its eight waves take the 32-wide K steps round robin (step s -> wave s % 8)
+// and the eight partial tiles are added in wave order through LDS before scale / shift / activation.  Deterministic: a fixed
+// summation order.
+//  * v_mfma_f32_16x16x4_f32 (same FLOP per clock as the 32x32x2 shape, exact products); weights = A operand, activations =
+//    B operand, so a lane ends up with four consecutive channels of one row, as in xv_epilogue.h.
+//  * No LDS in the K loop: lane (i, g) loads the eight consecutive k = 32 s + 8 g .. + 7 of row i straight from global
+//    memory (two 16-byte loads per operand tile per eight MFMAs, a wave instruction pair = whole 128-byte lines of 16 rows; the K
+//    index of an MFMA is only a summation label, so both operands use the same permuted order) and the loads run SG_PF steps
+//    ahead of the MFMAs in a register ring.
+//  * Consecutive workgroup ids walk the N tiles of one M tile: the ids congruent mod 8 (one XCD) then touch one eighth of the
+//    weights each, and every XCD reads the activations once.
+//  * 256 x 3000 x 512 takes it about 22 us, against 31 us for the pair it replaces (profiles/small_launches.md).  A ring half as
+//    deep with 64-byte pieces per row took the same time and the MFMAs are 5 us of the whole chip, so the likely limit (inferred:
+//    no fetch counters were taken) is the bytes a CU pulls through its L1 -- (32 + 16) rows x K x 4 = 577 KB per workgroup,
+//    148 MB over the chip.  A 32 x 32 tile would move 98 MB on half the CUs; that form was not measured.
+constexpr int SG_TM = 32, SG_TN = 16, SG_WAVES = 8, SG_KS = 32, SG_PF = 4;
+
+__global__ __launch_bounds__(SG_WAVES * 64) void gemm_f32_seg_kernel(GemmArgs p, int nNt, int vec_out) {
+  __shared__ __attribute__((aligned(16))) float red[SG_WAVES][SG_TM * SG_TN];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int i16 = lane & 15, g = lane >> 4;
+  const int mt = blockIdx.x / nNt, nt = blockIdx.x - mt * nNt;
+  const int m0 = mt * SG_TM, n0 = nt * SG_TN;
+  const int nks = p.Kpad / SG_KS;
+
+  // rows past M are computed on a copy of row M - 1 and never stored; the weights are zero padded to [Npad][Kpad]
+  const float* wrow = p.Wt + (int64_t)(n0 + i16) * p.Kpad + 8 * g;
+  const float* xrow0 = p.X + (int64_t)min(m0 + i16, p.M - 1) * p.ldx;
+  const float* xrow1 = p.X + (int64_t)min(m0 + 16 + i16, p.M - 1) * p.ldx;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  // Every load is unconditional -- a step past the end re-reads the last one, a quad behind K (K % 4 == 0: it is inside the row
+  // or behind it) the row's last quad -- and what must not count is zeroed when it is used: with the loads under a condition the
+  // compiler put them behind branches and drained the whole ring (vmcnt(0)) once per trip, one memory latency per SG_PF steps.
+  f32x4 rw[SG_PF][2], rx0[SG_PF][2], rx1[SG_PF][2];
+  auto load_step = [&](int s, int i) {
+    const int k = min(s, nks - 1) * SG_KS;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int kx = min(k + 8 * g + 4 * c, p.K - 4);
+      rw[i][c] = *reinterpret_cast<const f32x4*>(wrow + k + 4 * c);
+      rx0[i][c] = *reinterpret_cast<const f32x4*>(xrow0 + kx);
+      rx1[i][c] = *reinterpret_cast<const f32x4*>(xrow1 + kx);
+    }
+  };
+  // Compiler order only (no instruction): without it the loads of the ring are folded through the loop's phi nodes into one load
+  // per slot at the top of the body, right in front of its use ...
+  auto keep_here = [] {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);       // ... and the scheduler moved every load of a trip behind the trip's last MFMA
+  };
+
+  f32x4 acc0 = z, acc1 = z;
+#pragma unroll
+  for (int i = 0; i < SG_PF; ++i) load_step(wave + i * SG_WAVES, i);
+  keep_here();
+  for (int s = wave; s < nks; s += SG_PF * SG_WAVES) {
+#pragma unroll
+    for (int i = 0; i < SG_PF; ++i) {
+      const int si = s + i * SG_WAVES;
+      const bool in = si < nks;
+      f32x4 w[2], x0[2], x1[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const bool inx = in && si * SG_KS + 8 * g + 4 * c < p.K;
+        w[c] = in ? rw[i][c] : z;                    // (steps past the end add exact zeros)
+        x0[c] = inx ? rx0[i][c] : z;
+        x1[c] = inx ? rx1[i][c] : z;
+      }
+      load_step(si + SG_PF * SG_WAVES, i);
+      keep_here();
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][j], x0[c][j], acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][j], x1[c][j], acc1, 0, 0, 0);
+        }
+    }
+  }
+
+  // D[n][m]: lane (i16, g) holds channels 4 g .. 4 g + 3 of rows i16 and 16 + i16
+  *reinterpret_cast<f32x4*>(&red[wave][i16 * SG_TN + 4 * g]) = acc0;
+  *reinterpret_cast<f32x4*>(&red[wave][(16 + i16) * SG_TN + 4 * g]) = acc1;
+  __syncthreads();
+  if (tid >= SG_TM * SG_TN / 4) return;
+  const int ml = tid >> 2, q = tid & 3;
+  f32x4 acc = *reinterpret_cast<const f32x4*>(&red[0][ml * SG_TN + 4 * q]);
+#pragma unroll
+  for (int w = 1; w < SG_WAVES; ++w) acc += *reinterpret_cast<const f32x4*>(&red[w][ml * SG_TN + 4 * q]);
+  const int m = m0 + ml, n = n0 + 4 * q;
+  if (m >= p.M || n >= p.N) return;
+  float* y = p.Y + (int64_t)m * p.ldy + n;
+  if (vec_out) {                                   // N % 4 == 0: the whole quad is inside the row
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(p.scale + n), sh = *reinterpret_cast<const f32x4*>(p.shift + n);
+    const f32x4 al = p.alpha ? *reinterpret_cast<const f32x4*>(p.alpha + n) : z;
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = apply_act(fmaf(acc[e], sc[e], sh[e]), p.act, al[e]);
+    *reinterpret_cast<f32x4*>(y) = v;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (n + e < p.N) y[e] = apply_act(fmaf(acc[e], p.scale[n + e], p.shift[n + e]), p.act, p.alpha ? p.alpha[n + e] : 0.f);
+  }
+}
+
+// true when gemm_f32_seg_kernel runs this launch
+static bool seg_form(const GemmArgs& a, bool aligned) {
+  return aligned && !a.a_pitch && a.M <= 512 && a.Y && !a.rowmap && !a.R && !a.Ysb && !a.pool_part && !a.att_part && !a.raw;
+}
+
 int gemm_f32_ksplit(int M, int Kpad, int Npad) {
   if (M > 512) return 1;                       // frame-level layers fill the chip on their own
   const int tiles = ((M + BM - 1) / BM) * (Npad / BN), nk = Kpad / BK;
@@ -177,6 +294,16 @@ int gemm_f32_ksplit(int M, int Kpad, int Npad) {
 
 hipError_t launch_gemm_f32(const GemmArgs& a, bool aligned, hipStream_t s) {
   if (a.M <= 0) return hipSuccess;
+  if (seg_form(a, aligned)) {
+    // (The planner still reserves the split-K partials of such a layer -- a.partial, a.ksplit: the reservation is part of the
+    // recorded plans -- but nothing is written there any more.)
+    const int nMt = (a.M + SG_TM - 1) / SG_TM, nNt = (a.N + SG_TN - 1) / SG_TN;
+    const int vec_out = (a.N & 3) == 0 && (a.ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(a.Y) & 15) == 0 &&
+                        (reinterpret_cast<uintptr_t>(a.scale) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.shift) & 15) == 0 &&
+                        (reinterpret_cast<uintptr_t>(a.alpha) & 15) == 0;
+    hipLaunchKernelGGL(gemm_f32_seg_kernel, dim3(nMt * nNt), dim3(SG_WAVES * 64), 0, s, a, nNt, vec_out);
+    return hipGetLastError();
+  }
   const int nMt = (a.M + BM - 1) / BM, nNt = a.Npad / BN;
   const int ks = (a.ksplit > 1 && a.partial && !a.Ysb && !a.pool_part) ? a.ksplit : 1;
   const int nk_all = a.Kpad / BK;

@@ -449,6 +449,134 @@ hipError_t launch_im2col_sb(const float* x, int64_t ldx, int cin, int w, int64_t
   return hipGetLastError();
 }
 
+// The cin_pad form of the first layer (one tap: a feature row becomes one SB row, zero padded to ldsb channels) and the per-utterance
+// lower-range guard of the fp16 formats in ONE pass over the features.  The workgroup knows its utterance; a lane takes 8 channels
+// of a row: 8-byte loads where the row stride and the pointer allow (a 30-dim row is only 8-byte aligned), the split of
+// xv_epilogue.h, then the hi and the lo halves as one 16-byte store each.  No division inside the loop.  Two grids:
+//  * no utterance longer than kStageSingleRows: grid (1, utterance), 1024 threads.  The workgroup sees the whole utterance and
+//    decides by itself, as feat_utt_guard_kernel does: plain stores, nothing to combine.
+//  * else grid (chunks of kStageRows rows, utterance), 256 threads, so that a long utterance is spread over as many workgroups
+//    as it has chunks.  The largest magnitude of a workgroup's rows goes into the utterance's word behind the per-wave words
+//    with ONE vector atomic max per workgroup on the bit pattern (non-negative floats order like ints) -- ceil(L / kStageRows)
+//    atomics per address, not the one per thread whose cost the comment in im2col_sb_kernel records -- and feat_utt_fold_kernel,
+//    launched right behind in the same step, decides for THIS forward and clears the words.
+// Range guard (fp16 formats only), as before: a pair beyond +-65504 (or NaN) raises flag word 0; an utterance that is non-zero
+// but entirely below 2^-8 sets the sticky flag word kUttSmallWord; the largest finite magnitude goes where the read-outs take the
+// batch maximum from (single grid: the workgroup's word among the per-wave words; else flag word 1).  The read-outs
+// (flags_snapshot_kernel, xv_check_overflow) never see the per-utterance words.
+constexpr int kStageRows = 128, kStageSingleRows = 512;
+
+template <bool VEC2>
+__global__ __launch_bounds__(1024) void feat_stage_sb_kernel(const float* __restrict__ x, int64_t ldx, int cin,
+                                                             const int32_t* __restrict__ offs, char* __restrict__ out,
+                                                             int ldsb, int f16, int* __restrict__ flags, int single) {
+  __shared__ float wmax[16];
+  const int b = blockIdx.y;
+  const int64_t r0 = offs[b];
+  const int len = (int)(offs[b + 1] - r0);
+  const int row_begin = single ? 0 : blockIdx.x * kStageRows;
+  if (row_begin >= len) return;                      // (uniform over the workgroup)
+  const int row_end = single ? len : min(len, row_begin + kStageRows);
+  const int lpr = ldsb >> 3, rpp = blockDim.x / lpr; // lanes per row, rows per pass (launch_feat_stage_sb: lpr <= 256)
+  const int rs = threadIdx.x / lpr, c8 = threadIdx.x - rs * lpr;
+  const int k0 = 8 * c8;
+  float mx = 0.f;
+  bool bad = false;
+  if (rs < rpp) {
+    const float* src = x + (r0 + row_begin + rs) * ldx + k0;
+    char* dst = out + (r0 + row_begin + rs) * (int64_t)ldsb * 4 + (c8 >> 2) * 128 + (c8 & 3) * 16;
+    for (int row = row_begin + rs; row < row_end; row += rpp, src += (int64_t)rpp * ldx, dst += (int64_t)rpp * ldsb * 4) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) {
+        if (VEC2 && k0 + e + 1 < cin) {
+          const float2 t = *reinterpret_cast<const float2*>(src + e);
+          v[e] = t.x;
+          v[e + 1] = t.y;
+        } else {
+          v[e] = k0 + e < cin ? src[e] : 0.f;
+          v[e + 1] = k0 + e + 1 < cin ? src[e + 1] : 0.f;
+        }
+      }
+      uint32_t hi[4], lo[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        split2(v[2 * e], v[2 * e + 1], hi[e], lo[e], f16);          // hi/lo split in the format the GEMM consumes (xv_epilogue.h)
+        const float m2 = fmaxf(fabsf(v[2 * e]), fabsf(v[2 * e + 1]));
+        bad |= !(m2 <= kF16Max);                                    // a feature beyond the fp16 range
+        mx = fmaxf(mx, m2);
+      }
+      *reinterpret_cast<uint4*>(dst) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+      *reinterpret_cast<uint4*>(dst + 64) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    }
+  }
+  if (!f16 || !flags) return;
+  if (bad) flags[0] = 1;                             // every reporter writes the same value
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) mx = fmaxf(mx, wmax[i]);
+    if (single) {                                    // the whole utterance: decided here
+      reinterpret_cast<float*>(flags + kFlagWords)[b] = (mx <= 3.0e38f) ? mx : 0.f;
+      if (mx > 0.f && mx < 0.00390625f) flags[kUttSmallWord] = __float_as_int(mx);     // 2^-8; any such value will do
+    } else if (mx > 0.f) {
+      atomicMax(flags + kFlagWords + kFeatMaxSlots + b, __float_as_int(mx));
+    }
+  }
+}
+
+// One workgroup behind the chunked grid of feat_stage_sb_kernel: the per-utterance maxima of this forward -> sticky flag words,
+// then cleared.
+__global__ __launch_bounds__(1024) void feat_utt_fold_kernel(int* __restrict__ flags, int batch) {
+  __shared__ float wmax[16], wsmall[16];
+  int* utt = flags + kFlagWords + kFeatMaxSlots;
+  float mx = 0.f, small = 0.f;
+  for (int i = threadIdx.x; i < batch; i += 1024) {
+    const float v = __int_as_float(utt[i]);
+    utt[i] = 0;
+    if (v > 0.f && v < 0.00390625f) small = fmaxf(small, v);         // non-zero but entirely below 2^-8
+    mx = fmaxf(mx, v <= 3.0e38f ? v : 0.f);                          // (an infinity raised flag word 0 already)
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    small = fmaxf(small, __shfl_xor(small, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    wmax[threadIdx.x >> 6] = mx;
+    wsmall[threadIdx.x >> 6] = small;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 16; ++i) {
+      mx = fmaxf(mx, wmax[i]);
+      small = fmaxf(small, wsmall[i]);
+    }
+    if (small > 0.f) flags[kUttSmallWord] = __float_as_int(small);   // any such value will do (feat_utt_guard_kernel)
+    if (mx > 0.f) atomicMax(flags + 1, __float_as_int(mx));          // (no value returned: nothing to wait for)
+  }
+}
+
+bool feat_stage_sb_ok(int ldsb, int batch) { return ldsb % 32 == 0 && ldsb <= 2048 && batch <= kUttMaxSlots && batch <= kFeatMaxSlots; }
+
+hipError_t launch_feat_stage_sb(const float* x, int64_t ldx, int cin, const int32_t* offsets_dev, int batch, int max_len,
+                                void* out_sb, int ldsb, int f16, int* flags, hipStream_t s) {
+  if (batch <= 0 || max_len <= 0) return hipSuccess;
+  if (!feat_stage_sb_ok(ldsb, batch)) return hipErrorInvalidValue;
+  const int single = max_len <= kStageSingleRows;
+  const dim3 grid(single ? 1 : (max_len + kStageRows - 1) / kStageRows, batch), block(single ? 1024 : 256);
+  if (ldx % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0)
+    hipLaunchKernelGGL(feat_stage_sb_kernel<true>, grid, block, 0, s, x, ldx, cin, offsets_dev, static_cast<char*>(out_sb), ldsb, f16, flags, single);
+  else
+    hipLaunchKernelGGL(feat_stage_sb_kernel<false>, grid, block, 0, s, x, ldx, cin, offsets_dev, static_cast<char*>(out_sb), ldsb, f16, flags, single);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !f16 || !flags || single) return e;
+  hipLaunchKernelGGL(feat_utt_fold_kernel, dim3(1), dim3(1024), 0, s, flags, batch);
+  return hipGetLastError();
+}
+
 // --------------------------------------------------------------------- small elementwise
 __global__ void affine_act_kernel(const float* __restrict__ x, int64_t ldx, int64_t rows, int C,
                                   const float* __restrict__ scale, const float* __restrict__ shift,
@@ -526,7 +654,8 @@ __global__ void flags_snapshot_kernel(int* __restrict__ dev, int* __restrict__ h
 // The staging kernel's per-wave maxima guard the batch as a whole; an utterance whose features all sit far below the others' would
 // pass that test and run with flushed low halves (~2^-11 relative error on its frame-level outputs).  One workgroup per utterance
 // takes its largest |feature| (the features were just staged: the re-read comes from the caches) and reports one that is non-zero
-// and below 2^-8 with a plain store into the flag word (any such value will do).
+// and below 2^-8 with a plain store into the flag word (any such value will do).  Only behind im2col_sb_kernel (the materialising
+// first layer): feat_stage_sb_kernel takes the same maximum while it stages.
 __global__ void feat_utt_guard_kernel(const float* __restrict__ x, int64_t ldx, int cin, const int32_t* __restrict__ offs,
                                       int* __restrict__ flags) {
   __shared__ float wmax[16];

@@ -16,8 +16,12 @@ enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_LRELU = 2, ACT_PRELU = 3, ACT_T
 constexpr float kLreluAlpha = 0.2f;       // tf.nn.leaky_relu default (model/tdnn.py:33)
 // fp16 range guard buffer of a handle: kFlagWords ints ([0] overflow flag, [1] bits of a feature maximum carried over, [2..3] scratch
 // of xv_flags_async, [kUttSmallWord] bits of the largest |feature| of an utterance that stayed below 2^-8, 0 = none), then
-// kFeatMaxSlots floats: the largest feature magnitude each wave of the feature staging kernel saw since the last read-out
+// kFeatMaxSlots floats: the largest feature magnitude each wave of the feature staging kernel saw since the last read-out, then
+// kUttMaxSlots words: the bits of the largest |feature| of utterance b of the forward being staged (feat_stage_sb_kernel; folded into
+// the flag words and cleared again by feat_utt_fold_kernel inside the same step: zero between forwards, never read out)
 constexpr int kFlagWords = 8, kUttSmallWord = 4, kFeatMaxSlots = 32768;      // 8192 workgroups x 4 waves
+constexpr int kUttMaxSlots = 32768;
+constexpr int kFlagBufWords = kFlagWords + kFeatMaxSlots + kUttMaxSlots;
 constexpr float kVarFloor = 1e-12f;       // VAR2STD_EPSILON (model/pooling.py:6)
 
 // One "overlapping-row" GEMM:  Y[rowmap[m], n] = act((sum_k A[m,k] * Wt[n,k]) * scale[n] + shift[n])
@@ -63,7 +67,7 @@ struct GemmArgs {
   int f16 = 0;                 // split format of both operands: 0 = bf16 hi/lo (bf16x3), 1 = fp16 hi/lo (f16x3: same layout and
                                // MFMA rate, 11 + 11 significand bits instead of 8 + 8; values beyond +-65504 overflow)
   long long* trace = nullptr;  // debug: per-workgroup phase timestamps (XVEC_TRACE_K), 4 per workgroup
-  // split-K (fp32 kernel, small-M segment layers): slice s of `ksplit` accumulates K tiles
+  // split-K (fp32 kernel, small-M layers that gemm_f32_seg_kernel does not take): slice s of `ksplit` accumulates K tiles
   // [s*kper, (s+1)*kper) and writes RAW accumulators to partial[s][M][Npad]; a reduce kernel
   // sums the slices in order (deterministic) and applies the epilogue.
   int ksplit;             // 0/1 = off
@@ -135,6 +139,12 @@ int64_t gemm_bf16x3_tail_plan(int M, int Kpad, int Npad, int w, int* tail_mt, in
 //   out row m, k < w*cin: x[(m + k / cin) * ldx + k % cin]; zero padded to ldsb columns.
 hipError_t launch_im2col_sb(const float* x, int64_t ldx, int cin, int w, int64_t rows, void* out_sb, int ldsb, int f16,
                             int* ovf, hipStream_t s);
+
+// The one-tap form of the same (rows of ldsb >= cin channels, one per feature row) fused with the per-utterance lower-range guard of
+// the fp16 formats: one pass over the features.  max_len = the longest utterance (frames); feat_stage_sb_ok: the shapes it takes.
+bool feat_stage_sb_ok(int ldsb, int batch);
+hipError_t launch_feat_stage_sb(const float* x, int64_t ldx, int cin, const int32_t* offsets_dev, int batch, int max_len,
+                                void* out_sb, int ldsb, int f16, int* flags, hipStream_t s);
 
 // bf16x3 / f16x3 split path (3x v_mfma_f32_16x16x32_{bf16,f16} per product tile).
 hipError_t launch_gemm_bf16x3(const GemmArgs& a, hipStream_t s);

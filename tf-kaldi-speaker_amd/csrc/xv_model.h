@@ -161,8 +161,9 @@ struct xv_handle {
   std::vector<xv::api::Node> nodes;
   // attention extras
   xv::api::DevBuf query;        // [H, dk_h]
-  xv::api::DevBuf ovf_flag;     // fp16 split formats, 4 ints: [0] set by any kernel that converted a value beyond the fp16 range;
-                                // [1] bits of the largest feature magnitude staged since the last reset (underflow guard)
+  xv::api::DevBuf ovf_flag;     // fp16 split formats, kFlagBufWords ints (xv_kernels.h): [0] set by any kernel that converted a value beyond
+                                // the fp16 range; [1] bits of the largest feature magnitude staged since the last reset (underflow guard);
+                                // then the staging kernels' per-wave and per-utterance maxima
   xv::api::DevBuf query_eff;    // [H, Npad of the last key layer]: the query of head h over the padded key width, zero
                                 // outside the head's slice (fused score epilogue)
   int key_npad = 0;
