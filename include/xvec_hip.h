@@ -711,6 +711,72 @@ int xv_logreg_stats(int device, const float* scores_dev, int64_t lds, int64_t n,
 int xv_score_fuse(int device, const float* scores_dev, int64_t lds, int64_t n, int k, const double* theta_host, float* out_dev,
                   void* stream);
 
+/* ---- reverberation and additive noise (csrc/reverb.hip) ------------------------------------------------------------
+ * What Kaldi's wav-reverberate does to one utterance, on a packed batch: the stage-2 augmentation of egs/sre/v1/run.sh and
+ * egs/voxceleb/v2/run_aug.sh, whose wav.scp lines are `wav-reverberate ... |` pipelines.  Kaldi is not in the reference tree:
+ * **parity unpinned**; the rule restates wav-reverberate.cc as published and is the specification
+ * (tests/helpers/ref_reverb.py states it in float64 numpy).
+ *
+ * An utterance has int16 samples x[0..N), N >= 1, at sample rate fs; optionally an impulse response h[0..L) = int16 / 32768
+ * (exact in float32), 1 <= L <= 65536; J >= 0 additive signals v_j[0..M_j) with snr_j in dB, a start time t_j in seconds and
+ * an extended length M'_j >= 1 (M'_j = M_j unless the signal came from a nested --duration pipe).  All rates are equal.
+ *   1. P_before = (sum x^2) / N.
+ *   2. With an RIR: y[n] = sum_k h[k] x[n - k] for n in [0, N + L - 1).  p = the lowest index of the largest *signed* h
+ *      (Vector::Max).  b = trunc(0.001 fs), a = trunc(0.05 fs); the early window is [s, e) = [max(0, p - b), min(L, p + a));
+ *      E = sum_n e[n]^2 / (N + (e - s) - 1), e = the same convolution restricted to the taps in [s, e).
+ *      Without an RIR: y = x, E = P_before, p = 0.  Y = len(y).
+ *   3. For j in order: P_j = sum_{i < M'_j} v_j[i mod M_j]^2 / M'_j, g_j = sqrt(10^(-snr_j / 10) E / P_j),
+ *      o_j = trunc(t_j fs); for 0 <= i < min(M'_j, Y - o_j): y[o_j + i] += g_j v_j[i mod M_j].  P_j = 0 is an error of that
+ *      utterance (status 1); no inf is ever written.
+ *   4. P_after = sum y^2 / Y.
+ *   5. scale = volume if volume > 0; else sqrt(P_before / P_after) if normalize_output (P_after = 0: status 2); else 1.
+ *   6. shift = p if there is an RIR and shift_output, else 0.  n_out = trunc(duration fs) if duration > 0, else N if
+ *      shift_output, else Y.  out[i] = scale y[(i + shift) mod Y] for i < n_out: the plain range when n_out <= N, the full
+ *      tail when shift_output = false, and the repetition that fills a --duration longer than the signal.
+ *   7. int16 output: trunc toward zero, then saturation to [-32768, 32767]; the saturated samples are counted per utterance.
+ *   8. Sums of squares and every scalar (E, P_*, g_j, scale) are double; partial sums are added in a fixed order, one per
+ *      workgroup, then a second fixed-order pass; no floating-point atomics.  y is float32.  An utterance's outputs are a
+ *      pure function of its own inputs: the same bits on every repeat, alone or in any batch, and for every workspace of at
+ *      least xv_reverb_workspace bytes.
+ * The float32 output stays within scale eps[n] + |ref| delta of the rule in exact arithmetic; csrc/reverb.hip derives
+ * eps and delta.
+ *
+ * Tables are host arrays.  waves_dev / rirs_dev / noises_dev are packed int16 device buffers of wave_samples / rir_samples /
+ * noise_samples samples; several utterances may name the same impulse response or additive signal.  Utterance i reads
+ * waves[wave_off .. + wave_len) and writes out[out_off .. + out_len), out_len = n_out of rule 6; both sets of offsets rise
+ * without overlap.  rir_len = 0: no RIR.  Its additive signals are the rows [noise_begin, + noise_count) of the noise table
+ * (rising).  out_i16_dev or out_f32_dev may be NULL, not both; an utterance whose status_dev is not 0 gets zeros.
+ * peak_dev[i] = p, clipped_dev[i] = the saturated samples of the int16 output (0 without one).  xv_reverb validates every
+ * table before the first HIP call (XV_ERR_INVALID: offsets that do not rise or leave a buffer, a length outside [1, 2^31),
+ * N + L - 1 or n_out at or above 2^31, out_len other than n_out, fs outside [100, 1e6], snr outside [-200, 200] dB, a negative
+ * start time, volume above 1e6; XV_ERR_UNSUPPORTED: L > 65536; XV_ERR_WORKSPACE: ws_bytes below xv_reverb_workspace) and only
+ * enqueues on `stream`.  xv_reverb_workspace makes the same checks and returns the bytes or the negative code.
+ * xv_reverb_tile: the convolution's tile of outputs per workgroup and chunk of taps per LDS pass (tests size shapes by them). */
+#define XV_REVERB_TILE 2048
+#define XV_REVERB_CHUNK 256
+#define XV_REVERB_MAX_TAPS 65536
+typedef struct {
+  int64_t wave_off, wave_len;         /* N */
+  int64_t rir_off, rir_len;           /* L; 0: none */
+  int64_t noise_begin, noise_count;   /* J rows of the noise table */
+  int64_t out_off, out_len;           /* n_out */
+  double sample_rate, duration, volume;
+  int32_t shift_output, normalize_output;
+} xv_reverb_utt;
+typedef struct {
+  int64_t off, len, ext_len;          /* M, M' */
+  double snr_db, start_time;
+} xv_reverb_noise;
+int xv_reverb_tile(int* tile, int* chunk);
+int64_t xv_reverb_workspace(const xv_reverb_utt* utts_host, int64_t num_utts, const xv_reverb_noise* noises_host,
+                            int64_t num_noises, int64_t wave_samples, int64_t rir_samples, int64_t noise_samples,
+                            int64_t out_samples);
+int xv_reverb(int device, const int16_t* waves_dev, int64_t wave_samples, const int16_t* rirs_dev, int64_t rir_samples,
+              const int16_t* noises_dev, int64_t noise_samples, const xv_reverb_utt* utts_host, int64_t num_utts,
+              const xv_reverb_noise* noises_host, int64_t num_noises, int16_t* out_i16_dev, float* out_f32_dev,
+              int64_t out_samples, int32_t* status_dev, int32_t* peak_dev, int32_t* clipped_dev, void* ws_dev, int64_t ws_bytes,
+              void* stream);
+
 /* ---- host-side ark I/O (csrc/ark_io.cpp; no HIP calls, usable without a GPU) ---------------------
  * Batch counterpart of dataset/kaldi_io.py read_mat_ark (:974-994, records per _read_mat_binary
  * :1014-1031 / _read_compressed_mat :1071-1115) and write_vec_flt (:915-946): the extraction driver

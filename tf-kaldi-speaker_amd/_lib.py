@@ -43,6 +43,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_loss_prepare_classes", "xv_loss_workspace", "xv_loss_classifier", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
            "xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse",
+           "xv_reverb_tile", "xv_reverb_workspace", "xv_reverb",
            "xv_ark_open", "xv_ark_open_scp", "xv_ark_scp_count", "xv_ark_scp_shapes", "xv_ark_next_batch", "xv_ark_pending_shape", "xv_ark_skipped", "xv_ark_set_copy_threads", "xv_ark_error", "xv_ark_close", "xv_ark_format_vectors", "xv_crc32c", "xv_pack_rows"]
 
 
@@ -84,6 +85,19 @@ class FbankOpts(C.Structure):
         ("energy_floor", C.c_float), ("raw_energy", C.c_int32), ("htk_compat", C.c_int32), ("use_log_fbank", C.c_int32),
         ("use_power", C.c_int32),
     ]
+
+
+class ReverbUtt(C.Structure):
+    _fields_ = [
+        ("wave_off", C.c_int64), ("wave_len", C.c_int64), ("rir_off", C.c_int64), ("rir_len", C.c_int64),
+        ("noise_begin", C.c_int64), ("noise_count", C.c_int64), ("out_off", C.c_int64), ("out_len", C.c_int64),
+        ("sample_rate", C.c_double), ("duration", C.c_double), ("volume", C.c_double),
+        ("shift_output", C.c_int32), ("normalize_output", C.c_int32),
+    ]
+
+
+class ReverbNoise(C.Structure):
+    _fields_ = [("off", C.c_int64), ("len", C.c_int64), ("ext_len", C.c_int64), ("snr_db", C.c_double), ("start_time", C.c_double)]
 
 
 class PlanInfo(C.Structure):
@@ -199,6 +213,10 @@ def load():
     lib.xv_logreg_workspace.restype = i64
     lib.xv_logreg_stats.argtypes = [i32, vp, i64, i64, i32, vp, vp, C.c_double, C.c_double, C.c_double, vp, i32, vp, vp, vp, i64, vp]
     lib.xv_score_fuse.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp]
+    lib.xv_reverb_tile.argtypes = [C.POINTER(i32), C.POINTER(i32)]
+    lib.xv_reverb_workspace.argtypes = [vp, i64, vp, i64, i64, i64, i64, i64]
+    lib.xv_reverb_workspace.restype = i64
+    lib.xv_reverb.argtypes = [i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     lib.xv_ark_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
     lib.xv_ark_open_scp.argtypes = [C.c_char_p, C.POINTER(vp)]
     lib.xv_ark_scp_count.argtypes = [vp]
@@ -222,7 +240,7 @@ def load():
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
                      "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
+                     "xv_loss_workspace", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

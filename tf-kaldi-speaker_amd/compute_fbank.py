@@ -13,9 +13,9 @@ import argparse
 import logging
 import sys
 
-from .compute_mfcc import TableWriter
+from .compute_mfcc import TableWriter, device_batches
 from .fbank import FbankOptions
-from .mfcc import VadOptions, read_wav_scp, vad_packed, wav_batches
+from .mfcc import VadOptions, vad_packed
 
 log = logging.getLogger("xvec.compute_fbank")
 
@@ -29,6 +29,8 @@ def build_parser():
     parser.add_argument("--vad-wspecifier", type=str, default="", help="Also write the energy VAD decisions: ark:vad.ark or ark,scp:vad.ark,vad.scp")
     parser.add_argument("--vad-config", type=str, default="", help="Kaldi conf/vad.conf for --vad-wspecifier (default: Kaldi's defaults)")
     parser.add_argument("--batch-samples", type=int, default=32 << 20, help="Samples packed into one device batch (extension)")
+    parser.add_argument("--native-reverberate", action="store_true",
+                        help="Resolve `wav-reverberate ... |` lines on the GPU (tf_kaldi_speaker_amd.augment) instead of running Kaldi")
     FbankOptions.add_arguments(parser)
     parser.add_argument("wav_rspecifier", type=str, help="scp:wav.scp")
     parser.add_argument("feats_wspecifier", type=str, help="ark:feats.ark or ark,scp:feats.ark,feats.scp")
@@ -65,13 +67,13 @@ def main(argv=None):
         log.warning("[WARNING] %s: %s" % (key, e))
 
     with torch.cuda.device(args.gpu):
-        for keys, samples, offsets in wav_batches(read_wav_scp(args.wav_rspecifier), opts, args.batch_samples, args.channel, on_error):
+        for keys, samples, offsets in device_batches(args, opts, dev, on_error):
             vad = None
             if vad_writer:
-                feats, foff, energy = fbank.compute(torch.from_numpy(samples).to(dev), offsets, energy=True)
+                feats, foff, energy = fbank.compute(samples, offsets, energy=True)
                 vad = vad_packed(energy.view(-1, 1), foff, vopts).cpu().numpy()
             else:
-                feats, foff = fbank.compute(torch.from_numpy(samples).to(dev), offsets)
+                feats, foff = fbank.compute(samples, offsets)
             feats = feats.cpu().numpy()
             for i, key in enumerate(keys):
                 if foff[i + 1] == foff[i]:

@@ -62,6 +62,18 @@ class TableWriter(object):
             self.scp.close()
 
 
+def device_batches(args, opts, dev, on_error):
+    """(keys, int16 CUDA tensor, sample offsets) per batch of the wav.scp: read on the host and copied, or, with
+    --native-reverberate, wav-reverberate pipelines resolved on the device (other lines go through read_wav as before)."""
+    import torch
+    items = read_wav_scp(args.wav_rspecifier)
+    if args.native_reverberate:
+        from .augment import native_batches
+        return native_batches(items, opts, args.batch_samples, args.channel, on_error, dev)
+    return ((keys, torch.from_numpy(samples).to(dev), offsets)
+            for keys, samples, offsets in wav_batches(items, opts, args.batch_samples, args.channel, on_error))
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument("-g", "--gpu", type=int, default=0, help="The GPU id.")
@@ -69,6 +81,8 @@ def build_parser():
     parser.add_argument("--channel", type=int, default=-1, help="Channel to extract (-1: the wav must be mono)")
     parser.add_argument("--write-utt2num-frames", type=str, default="", help="Write `key frames` lines to this file")
     parser.add_argument("--batch-samples", type=int, default=32 << 20, help="Samples packed into one device batch (extension)")
+    parser.add_argument("--native-reverberate", action="store_true",
+                        help="Resolve `wav-reverberate ... |` lines on the GPU (tf_kaldi_speaker_amd.augment) instead of running Kaldi")
     MfccOptions.add_arguments(parser)
     parser.add_argument("wav_rspecifier", type=str, help="scp:wav.scp")
     parser.add_argument("feats_wspecifier", type=str, help="ark:feats.ark or ark,scp:feats.ark,feats.scp")
@@ -101,8 +115,8 @@ def main(argv=None):
         log.warning("[WARNING] %s: %s" % (key, e))
 
     with torch.cuda.device(args.gpu):
-        for keys, samples, offsets in wav_batches(read_wav_scp(args.wav_rspecifier), opts, args.batch_samples, args.channel, on_error):
-            feats, foff = mfcc.compute(torch.from_numpy(samples).to(dev), offsets)
+        for keys, samples, offsets in device_batches(args, opts, dev, on_error):
+            feats, foff = mfcc.compute(samples, offsets)
             feats = feats.cpu().numpy()
             for i, key in enumerate(keys):
                 if foff[i + 1] == foff[i]:

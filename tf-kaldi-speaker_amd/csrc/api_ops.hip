@@ -175,6 +175,45 @@ int xv_class_mean_f64(int device, const float* x_dev, int64_t ldx, int64_t n, in
   });
 }
 
+int xv_reverb_tile(int* tile, int* chunk) {
+  if (!tile || !chunk) return fail(nullptr, XV_ERR_INVALID, "xv_reverb_tile: null pointer");
+  *tile = XV_REVERB_TILE;
+  *chunk = XV_REVERB_CHUNK;
+  return XV_OK;
+}
+
+int64_t xv_reverb_workspace(const xv_reverb_utt* utts_host, int64_t num_utts, const xv_reverb_noise* noises_host,
+                            int64_t num_noises, int64_t wave_samples, int64_t rir_samples, int64_t noise_samples,
+                            int64_t out_samples) {
+  std::string err;
+  const int rc = reverb_validate(utts_host, num_utts, noises_host, num_noises, wave_samples, rir_samples, noise_samples,
+                                 out_samples, &err);
+  if (rc != XV_OK) return fail(nullptr, rc, "xv_reverb_workspace: %s", err.c_str());
+  return reverb_workspace_bytes(utts_host, num_utts, num_noises);
+}
+
+int xv_reverb(int device, const int16_t* waves_dev, int64_t wave_samples, const int16_t* rirs_dev, int64_t rir_samples,
+              const int16_t* noises_dev, int64_t noise_samples, const xv_reverb_utt* utts_host, int64_t num_utts,
+              const xv_reverb_noise* noises_host, int64_t num_noises, int16_t* out_i16_dev, float* out_f32_dev,
+              int64_t out_samples, int32_t* status_dev, int32_t* peak_dev, int32_t* clipped_dev, void* ws_dev, int64_t ws_bytes,
+              void* stream) {
+  std::string err;
+  const int rc = reverb_validate(utts_host, num_utts, noises_host, num_noises, wave_samples, rir_samples, noise_samples,
+                                 out_samples, &err);
+  if (rc != XV_OK) return fail(nullptr, rc, "xv_reverb: %s", err.c_str());
+  if (!waves_dev || !status_dev || !peak_dev || !clipped_dev || (!out_i16_dev && !out_f32_dev) || (rir_samples > 0 && !rirs_dev) ||
+      (noise_samples > 0 && !noises_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_reverb: null pointer");
+  const int64_t need = reverb_workspace_bytes(utts_host, num_utts, num_noises);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_reverb: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0), (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 15) return fail(nullptr, XV_ERR_INVALID, "xv_reverb: the workspace must be 16-byte aligned");
+  return with_device(device, "reverb", [&] {
+    return launch_reverb(waves_dev, rirs_dev, noises_dev, utts_host, num_utts, noises_host, num_noises, out_i16_dev, out_f32_dev,
+                         status_dev, peak_dev, clipped_dev, ws_dev, to_stream(stream));
+  });
+}
+
 int64_t xv_logreg_workspace(int64_t n, int k) {
   if (k < 1 || k > XV_LOGREG_MAX_SYSTEMS) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_logreg_workspace: 1 <= k <= 8, got %d", k);
   if (n < 0 || n >= ((int64_t)1 << 40)) return fail(nullptr, XV_ERR_INVALID, "xv_logreg_workspace: n outside [0, 2^40)");

@@ -354,6 +354,17 @@ hipError_t launch_logreg_stats(const float* scores, int64_t lds, int64_t n, int 
                                int64_t* counts, void* ws, hipStream_t s);
 hipError_t launch_score_fuse(const float* scores, int64_t lds, int64_t n, int k, const double* theta, float* out, hipStream_t s);
 
+// reverberation and additive noise (csrc/reverb.hip): the rule of include/xvec_hip.h on a packed batch.  utts / noises are host
+// tables; reverb_validate checks them (XV_OK or an xv_status, message in *err) and nothing launches on a bad table; ws holds
+// reverb_workspace_bytes bytes.  launch_reverb expects validated tables.
+int64_t reverb_out_len(const xv_reverb_utt& u);
+int reverb_validate(const xv_reverb_utt* utts, int64_t nu, const xv_reverb_noise* noises, int64_t nn, int64_t wave_samples,
+                    int64_t rir_samples, int64_t noise_samples, int64_t out_samples, std::string* err);
+int64_t reverb_workspace_bytes(const xv_reverb_utt* utts, int64_t nu, int64_t nn);
+hipError_t launch_reverb(const int16_t* waves, const int16_t* rirs, const int16_t* sig, const xv_reverb_utt* utts, int64_t nu,
+                         const xv_reverb_noise* noises, int64_t nn, int16_t* out16, float* out32, int32_t* status, int32_t* peak,
+                         int32_t* clipped, void* ws, hipStream_t stream);
+
 // attention scores (model/pooling.py:189-194): score[r, h] = scale * sum_d key[r, h*dk_h + d] * q[h, d]
 // (split_key) or sum_d key[r, d] * q[h, d] (no split; dk_h == dk).
 hipError_t launch_att_scores(const float* key, int64_t ldk, int64_t rows, const float* query, int H,

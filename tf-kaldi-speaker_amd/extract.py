@@ -68,6 +68,8 @@ def build_parser():
     parser.add_argument("--vad-config", type=str, default="", help="Kaldi conf/vad.conf for --wav-input (default: Kaldi's defaults).")
     parser.add_argument("--channel", type=int, default=-1, help="Channel of the wav files for --wav-input (-1: they must be mono).")
     parser.add_argument("--batch-samples", type=int, default=32 << 20, help="Samples packed into one device batch with --wav-input.")
+    parser.add_argument("--native-reverberate", action="store_true",
+                        help="With --wav-input: resolve `wav-reverberate ... |` lines on the GPU instead of running Kaldi.")
     parser.add_argument("model_dir", type=str, help="The model directory.")
     parser.add_argument("rspecifier", type=str, help="Kaldi feature rspecifier (or ark file).")
     parser.add_argument("wspecifier", type=str, help="Kaldi output wspecifier (or ark file).")
@@ -434,12 +436,14 @@ def run_native(trainer, rspecifier, writer, min_chunk_size, chunk_size, normaliz
 
 
 def run_wav(trainer, rspecifier, writer, mopts, vopts, min_chunk_size, chunk_size, normalize, batch_frames, cmn_window=0,
-            channel=-1, batch_samples=32 << 20, fopts=None, config_names=("--mfcc-config", "--fbank-config")):
+            channel=-1, batch_samples=32 << 20, fopts=None, config_names=("--mfcc-config", "--fbank-config"),
+            native_reverberate=False):
     """--wav-input: wav.scp -> MFCC -> energy VAD -> sliding CMN + voiced-frame selection -> network, one device batch of about
     batch_samples samples at a time; the features never leave the device.  Utterances without frames, and those left with fewer
     than min_chunk_size voiced frames, are skipped as on the feature-file route.
     With fopts (FbankOptions) the features are fbank; the VAD is decided on the frame log energy of that pass, or, when mopts is
-    given too, on column 0 of an MFCC pass over the same samples (config_names: the two files, for the error message)."""
+    given too, on column 0 of an MFCC pass over the same samples (config_names: the two files, for the error message).
+    With native_reverberate the `wav-reverberate ... |` lines are resolved on the device (tf_kaldi_speaker_amd.augment)."""
     import torch
     from .frontend import cmn_select_packed
     from .mfcc import Mfcc, read_wav_scp, vad_packed, wav_batches
@@ -457,9 +461,14 @@ def run_wav(trainer, rspecifier, writer, mopts, vopts, min_chunk_size, chunk_siz
         skipped += 1
         log.warning("[WARNING] %s: %s" % (key, e))
 
-    for keys, samples, soff in wav_batches(read_wav_scp(rspecifier), fopts or mopts, batch_samples, channel, on_error):
+    if native_reverberate:
+        from .augment import native_batches
+        batches = native_batches(read_wav_scp(rspecifier), fopts or mopts, batch_samples, channel, on_error, devname)
+    else:
+        batches = wav_batches(read_wav_scp(rspecifier), fopts or mopts, batch_samples, channel, on_error)
+    for keys, samples, soff in batches:
         with torch.cuda.device(dev_index):
-            wave_dev = torch.from_numpy(samples).to(devname)
+            wave_dev = samples if native_reverberate else torch.from_numpy(samples).to(devname)
             if fbank is None:
                 raw, foff = mfcc.compute(wave_dev, soff)
                 vad = vad_packed(raw, foff, vopts).cpu().numpy()
@@ -549,8 +558,8 @@ def main(argv=None):
                                                                                      mopts.sample_frequency, args.mfcc_config))
         elif mopts.num_ceps < dim:
             sys.exit("--wav-input: the model expects %d features, %s gives %d" % (dim, args.mfcc_config, mopts.num_ceps))
-    elif args.mfcc_config or args.fbank_config or args.vad_config:
-        sys.exit("--mfcc-config / --fbank-config / --vad-config go with --wav-input")
+    elif args.mfcc_config or args.fbank_config or args.vad_config or args.native_reverberate:
+        sys.exit("--mfcc-config / --fbank-config / --vad-config / --native-reverberate go with --wav-input")
     elif spec.rsplit(".", 1)[-1] == "scp" and not (args.scp_input and spec.startswith(("scp:", "scp,"))):   # extract.py:59-61
         sys.exit("The rspecifier must be ark or input pipe")
 
@@ -577,7 +586,7 @@ def main(argv=None):
     if args.wav_input:
         done, skipped = run_wav(trainer, args.rspecifier, writer, mopts, vopts, args.min_chunk_size, args.chunk_size,
                                 args.normalize, args.batch_frames, args.cmn_window, args.channel, args.batch_samples,
-                                fopts, (args.mfcc_config, args.fbank_config))
+                                fopts, (args.mfcc_config, args.fbank_config), args.native_reverberate)
     elif native:
         done, skipped = run_native(trainer, args.rspecifier, writer, args.min_chunk_size, args.chunk_size,
                                    args.normalize, args.batch_frames, args.cmn_window, args.vad_rspecifier)
