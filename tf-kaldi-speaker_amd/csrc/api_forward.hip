@@ -119,7 +119,9 @@ GemmArgs gemm_args(const Run& r, const PlanStep& st, const Op& op, const Layer& 
 
 // The border of a grid output must be zero.  Covered outputs: the layer's own zero-writing rows do it, except for the
 // first utterance's top border row and first left border (S + 1 positions no GEMM row maps to); otherwise the whole value
-// is zeroed first.
+// is zeroed first.  In the full enumeration (no compact rows, no time-row map) the 2 S + 2 slack positions behind the value
+// are zeroed as well, see below: up to four memsets there (head or whole value, and slack; f32 and f16 copy each), one
+// border kernel and no memset on the default path.
 int gemm_clear_border(const Run& r, const PlanStep& st, const Layer& L, const Value& vo) {
   xv_handle* h = r.h;
   const size_t head = (size_t)vo.grid_S + 1;
@@ -129,9 +131,23 @@ int gemm_clear_border(const Run& r, const PlanStep& st, const Layer& L, const Va
   if (st.compact() || st.trows()) {     // border positions only
     XV_HIP(h, launch_grid_zero_border(r.p->dev_offsets(st.lvl_out), r.B, st.frames_out, vo.grid_F, vo.grid_S, L.cout / 4,
                                       sb_ld(L.cout) / 4, r.f32(st.out_off), r.raw(st.out_sb_off), r.s));
-  } else if (rows0 > 0) {
-    if (st.out_off >= 0) XV_HIP(h, hipMemsetAsync(r.raw(st.out_off), 0, rows0 * L.cout * 4, r.s));
-    if (st.out_sb_off >= 0) XV_HIP(h, hipMemsetAsync(r.raw(st.out_sb_off), 0, rows0 * sb_ld(L.cout) * 4, r.s));
+  } else {
+    if (rows0 > 0) {
+      if (st.out_off >= 0) XV_HIP(h, hipMemsetAsync(r.raw(st.out_off), 0, rows0 * L.cout * 4, r.s));
+      if (st.out_sb_off >= 0) XV_HIP(h, hipMemsetAsync(r.raw(st.out_sb_off), 0, rows0 * sb_ld(L.cout) * 4, r.s));
+    }
+    // Full enumeration (xv_set_option "grid_compact" 0): a consumer's GEMM rows cover every position of this value, the bottom
+    // border row of the last utterance included, and the 3x3 windows of those rows end two time rows and two positions behind
+    // the value, in its slack (kSlackRows).  Their results are zeros or dropped, but the fp16 range guard of the epilogue sees
+    // them before the row map does: over bytes that nobody wrote it raised the overflow flag of a forward whose every stored
+    // value was in range.  No GEMM row of the producer maps there (its zero-writing rows end at position (L + 3, 0)), so the
+    // 2 S + 2 positions behind the value are cleared here.
+    const size_t tail = 2 * (size_t)vo.grid_S + 2;
+    if (tail > (size_t)kSlackRows) return fail(h, XV_ERR_STATE, "grid pitch %d: the window overreach does not fit the slack", vo.grid_S);
+    if (st.out_off >= 0) XV_HIP(h, hipMemsetAsync(r.f32(st.out_off) + (size_t)st.rows_out * L.cout, 0, tail * L.cout * 4, r.s));
+    if (st.out_sb_off >= 0)
+      XV_HIP(h, hipMemsetAsync(static_cast<char*>(r.raw(st.out_sb_off)) + (size_t)st.rows_out * sb_ld(L.cout) * 4, 0,
+                               tail * sb_ld(L.cout) * 4, r.s));
   }
   return XV_OK;
 }
@@ -358,7 +374,12 @@ int run_step(const Run& r, const PlanStep& st) {
     case OP_GRID_MAXPOOL: {
       const Value& vo = h->values[op.out];
       float* y = r.f32(st.out_off);
-      XV_HIP(h, launch_grid_maxpool3x3(r.in(st.in0_off), off, B, vo.grid_F, vo.grid_S, vo.cols, st.rows_out, y,
+      // 2 S + 2 positions more than the value has: the kernel writes zeros there (they lie below the last utterance's bottom
+      // border, in the slack), which is what the windows of a fully enumerating consumer's last GEMM rows read (see
+      // gemm_clear_border) -- written by the producer, no memset
+      const int64_t tail = 2 * (int64_t)vo.grid_S + 2;
+      if (tail > kSlackRows) return fail(h, XV_ERR_STATE, "grid pitch %d: the window overreach does not fit the slack", vo.grid_S);
+      XV_HIP(h, launch_grid_maxpool3x3(r.in(st.in0_off), off, B, vo.grid_F, vo.grid_S, vo.cols, st.rows_out + tail, y,
                                        r.raw(st.out_sb_off), sb_ld(vo.cols), r.f16, r.ovf(), std::ldexp(1.f, vo.sb_exp), s));
       if (st.unpad_to_out)
         XV_HIP(h, launch_grid_unpad_n(y, off_out, B, vo.grid_F, vo.grid_S, vo.cols, st.frames_out, r.out, s));
