@@ -731,6 +731,12 @@ __device__ __forceinline__ void store_wave_tile_n32_impl(const GemmArgs& p, cons
   }
 }
 
+// 1 / (weight sum of a slot segment) for the slot mean s1 / s0 of the weighted moments below.  Peaked attention leaves slots whose
+// weights are all subnormal (softmax scores 88 .. 103 below the utterance's maximum): below 2^-128 the reciprocal overflows, the
+// slot mean becomes inf (or 0 x inf) and the utterance's variance a NaN.  Such a slot carries less than 2^-126 of the weight: its
+// moments are taken about zero instead (the merge in att_pool_finalize_kernel adds s0 (s1 / s0 - mean)^2 with a true division).
+__device__ __forceinline__ float slot_inverse(float s0) { return s0 >= 1.17549435e-38f ? 1.0f / s0 : 0.f; }
+
 // Attention epilogue of the 128-frame x 32-channel wave tile (kernel instantiations with EPI = 1; dense layers only:
 // no rowmap).  Two forms, see GemmArgs:
 //  * att_part: the tile is the last key layer's output and only its dot products with the query are wanted
@@ -834,7 +840,7 @@ __device__ __forceinline__ void store_wave_tile_n32_att_impl(const GemmArgs& p, 
 #pragma unroll 4
         for (int k = 0; k < 8; ++k) s1 += row4(k * 8 + rrow) * wt[k];
         s1 = groups_sum(s1);
-        const f32x4 mu = s1 * (s0 > 0.f ? 1.0f / s0 : 0.f);
+        const f32x4 mu = s1 * slot_inverse(s0);
         f32x4 m2 = z;
 #pragma unroll 4
         for (int k = 0; k < 8; ++k) {                   // second sweep of the LDS copy (registers are scarce here)
@@ -864,7 +870,7 @@ __device__ __forceinline__ void store_wave_tile_n32_att_impl(const GemmArgs& p, 
               if (t >= r && t < re) s1 += row4(t) * wt;
             }
             s1 = groups_sum(s1);
-            const f32x4 mu = s1 * (s0 > 0.f ? 1.0f / s0 : 0.f);
+            const f32x4 mu = s1 * slot_inverse(s0);
             f32x4 m2 = z;
             for (int t0 = r & ~7; t0 < re; t0 += 8) {
               const int t = t0 + rrow;
