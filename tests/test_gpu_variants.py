@@ -3,7 +3,7 @@
 * randomised ragged batches (seeded) through the default kernels: lengths from the network's minimum context to
   several M tiles, batch sizes that leave partial tiles, both poolings, embedding and frame-level nodes;
 * the K-split tail form and the fused / unfused statistics pooling, switched with xv_set_option in-process (the two
-  earlier GEMM kernels are lab-only code now, -DXV_LAB, and not part of the shipped library);
+  earlier GEMM kernels and their -DXV_LAB switches were removed; d876abd is the last commit that contains them);
 * the hardware property the default kernel's hand-counted s_waitcnt rely on (LDS-DMA and register loads retire in
   issue order under one vmcnt counter): tools/vmcnt_order_test.hip compiled and run here.
 Tolerance as in test_gpu_parity.py (BASELINE.json north_star: relative L2 <= 1e-4)."""

@@ -26,7 +26,8 @@ __device__ __forceinline__ float apply_act(float v, int act, float alpha) {
   }
 }
 
-// debug (tools/gemm_trace.py, -DXV_GEMM_TRACE builds only): phase stamps 4..7 of the workgroup's first thread
+// debug (tools/gemm_trace.py, -DXV_GEMM_TRACE builds only): phase stamps of the workgroup's first thread (0..3: the tile
+// functions of gemm_bf16x3.hip, 4..7: the epilogues here)
 #ifdef XV_GEMM_TRACE
 #define XV_EPI_STAMP(p, i)                                                                                          \
   do {                                                                                                              \
