@@ -569,6 +569,57 @@ int xv_plda_adapt(int device, const float* x_dev, int64_t ldx, const int64_t* of
                   double* pca_dev /* [G, d, d], rows 0..r-1 = P */, double* affine_dev /* [G, d, d + 1], rows 0..r-1 = T */,
                   double* psi_out_dev /* [G, d], entries 0..r-1 = psi' */, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- VB-HMM resegmentation of clustered x-vectors on the GPU (csrc/vbx.hip): the Bayesian HMM over the x-vector sequence of
+ * a recording that diarization recipes run after the first clustering ("VBx": Landini et al., "Bayesian HMM clustering of
+ * x-vector sequences", 2022; the function VBx of the published VB_diarization.py).  Neither the reference tree nor Kaldi's
+ * x-vector recipe has the step, so this is **parity unpinned**; the rule below is the specification and
+ * tests/helpers/ref_vbx.py states it in numpy.  All arithmetic is double.
+ * One group is one recording with T >= 1 float32 rows x_0 .. x_{T-1} of length d, in time order, S initial speakers, the affine
+ * A [r, d + 1] and psi [r] of the model (for a Plda [transform | -transform mean] and psi; for an adapted model its affine and
+ * psi; the first k rows / entries keep k dimensions).  No length normalisation happens inside.
+ *   1. u_t = A [x_t; 1];  rho_t = u_t * sqrt(psi);  G_t = -1/2 (sum_k u_tk^2 + r log(2 pi)).
+ *   2. Start values: gamma [T, S] with rows >= 0 and pi [S] >= 0 with a positive sum (the caller's duty; not checked).
+ *   3. Iteration i = 0, 1, ..:
+ *        N_s = sum_t gamma_ts;  invL_sk = 1 / (1 + Fa/Fb N_s psi_k);  alpha_sk = Fa/Fb invL_sk sum_t gamma_ts rho_tk;
+ *        logp_ts = Fa (rho_t . alpha_s - 1/2 sum_k (invL_sk + alpha_sk^2) psi_k + G_t);
+ *        tr_ij = loop_prob [i = j] + (1 - loop_prob) pi_j;
+ *        forward:  lfw_0 = logp_0 + log pi,  lfw_t,j = logp_tj + log sum_i exp(lfw_{t-1},i) tr_ij;
+ *        backward: lbw_{T-1} = 0,  lbw_t,i = log sum_j tr_ij exp(logp_{t+1},j + lbw_{t+1},j);
+ *        tll = logsumexp_j lfw_{T-1},j;  gamma = exp(lfw + lbw - tll);
+ *        ELBO_i = tll + Fb/2 sum_sk (log invL_sk - invL_sk - alpha_sk^2 + 1);
+ *        pi_j <- gamma_0j + (1 - loop_prob) pi_j sum_{t>=1} exp(logsumexp_i lfw_{t-1},i + logp_tj + lbw_tj - tll), then
+ *        pi <- pi / sum pi (T = 1: the sum over t is empty);
+ *        stop after this iteration if i > 0 and ELBO_i - ELBO_{i-1} < epsilon, or if i = max_iters - 1.
+ *      epsilon = -inf means "run all max_iters".
+ *   4. Outputs: the last gamma and the updated pi; ELBO_0 .. ELBO_{n-1} and n, the rest of the ELBO row NaN; label_t = the
+ *      lowest s with the largest gamma_ts.
+ *   5. Log-domain sums take their maximum out first (0 when every term is -inf, so that no NaN comes out of finite input);
+ *      a speaker with pi_j = 0 has gamma_.j = 0 exactly and stays dead; -inf is a legal log value.
+ *   6. tr is a diagonal plus a rank-one matrix and the kernel uses that: with m = max_i lfw_{t-1},i, e_i = exp(lfw_{t-1},i - m)
+ *      and E = sum_i e_i the forward step is lfw_t,j = logp_tj + m + log(loop_prob e_j + (1 - loop_prob) pi_j E), the backward
+ *      step alike: O(S) per frame, the same sum in another order.
+ *   7. The outputs of a group are a pure function of its own rows, start values, model and options: the same bits on every
+ *      repeat, alone or in any batch, in any group order, for every legal ws_bytes and whatever the workspace held before.  No
+ *      floating-point atomics.
+ * Layout: group g owns the rows offsets[g] .. offsets[g + 1]) of x_dev [*, ldx] and the same entries of labels_dev;
+ *   offsets_host [G + 1] and num_spk_host [G] are host arrays, consumed before the call returns.  gamma_dev (in and out) holds
+ *   the groups back to back, group g [T_g, S_g] at the double offset sum_{h<g} T_h S_h; pi_dev (in and out) group g at the
+ *   offset sum_{h<g} S_h.  elbo_dev [G, max_iters], iters_dev [G].  A group with T = 0 writes only iters = 0.
+ * Workspace: xv_vbx_workspace(G, offsets, num_spk, r) = 256 ceil(32 G / 256) + 8 (N (r + 2) + 3 sum_g T_g S_g) bytes, N the
+ *   number of rows of the call (the group table; rho, G_t and the per-frame logsumexp; logp, lfw, lbw), is the least ws_bytes,
+ *   or the code xv_vbx returns for the same groups and r; what lies beyond is not used.  ws_dev must be 8-byte aligned.
+ * 1 <= S <= 64, 1 <= r <= 256, 1 <= d <= 2048, T <= 8192, anything else is XV_ERR_UNSUPPORTED.  Offsets that decrease or start
+ *   below 0, ldx < d, Fa or Fb not positive (or not finite), loop_prob outside [0, 1], max_iters < 1, a NaN option, a
+ *   misaligned workspace: XV_ERR_INVALID; too little workspace: XV_ERR_WORKSPACE.  Every argument check comes before the first
+ *   HIP call and the outputs are untouched on any error.  num_groups = 0 returns XV_OK and touches nothing. */
+int64_t xv_vbx_workspace(int64_t num_groups, const int64_t* offsets_host /* [num_groups + 1] */,
+                         const int32_t* num_spk_host /* [num_groups] */, int r);
+int xv_vbx(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host /* [num_groups + 1] */,
+           const int32_t* num_spk_host /* [num_groups] */, int64_t num_groups, int d, const double* affine_dev /* [r, d + 1] */,
+           const double* psi_dev /* [r] */, int r, double* gamma_dev /* in, out */, double* pi_dev /* in, out */, double fa,
+           double fb, double loop_prob, int max_iters, double epsilon, int32_t* labels_dev /* indexed as the rows of x_dev */,
+           double* elbo_dev /* [G, max_iters] */, int32_t* iters_dev /* [G] */, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- classifier-head validation loss on the GPU (csrc/loss.hip): what Trainer.valid evaluates per batch
  * (model/trainer.py:756-884), loss_i = logsumexp_c(z_ic) - z_i,label as tf.losses.sparse_softmax_cross_entropy takes it, without
  * ever writing the [n, C] logits.  Products are exact fp32 with fp32 accumulation (the tile arithmetic of the scoring calls);

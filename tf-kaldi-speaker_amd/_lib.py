@@ -40,6 +40,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_plda_prepare", "xv_plda_matrix", "xv_plda_pairs", "xv_plda_histogram",
            "xv_cohort_stats_workspace", "xv_cohort_stats", "xv_score_topk_workspace", "xv_score_topk",
            "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_ahc", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_plda_adapt",
+           "xv_vbx_workspace", "xv_vbx",
            "xv_loss_prepare_classes", "xv_loss_workspace", "xv_loss_classifier", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
            "xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse",
@@ -195,7 +196,11 @@ def load():
     lib.xv_plda_adapt_slot_bytes.argtypes = [i32]
     lib.xv_plda_adapt_slot_bytes.restype = i64
     lib.xv_plda_adapt.argtypes = [i32, vp, i64, vp, i64, i32, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.xv_loss_prepare_classes.argtypes = [i32, vp, i64, i32, i64, i32, vp, i64, vp]
+    lib.xv_vbx_workspace.argtypes = [i64, vp, vp, i32]
+    lib.xv_vbx_workspace.restype = i64
+    lib.xv_vbx.argtypes = [i32, vp, i64, vp, vp, i64, i32, vp, vp, i32, vp, vp, C.c_double, C.c_double, C.c_double, i32, C.c_double,
+                           vp, vp, vp, vp, i64, vp]
+    lib.xv_loss_prepare_classes.argtypes =[i32, vp, i64, i32, i64, i32, vp, i64, vp]
     lib.xv_loss_workspace.argtypes = [i64, i64]
     lib.xv_loss_workspace.restype = i64
     lib.xv_loss_classifier.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, i64, vp, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, i64, vp]
@@ -240,7 +245,7 @@ def load():
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
                      "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
+                     "xv_loss_workspace", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_vbx_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

@@ -1,5 +1,7 @@
 // C ABI of libxvec_hip.so, the stateless ops: front-end, scoring, PLDA, back-end statistics, loss heads (classifier and metric), clustering
 // and calibration.  Every wrapper validates its arguments and hands one launch (or a short chain) to with_device().
+#include <cfloat>
+
 #include "xv_model.h"
 
 using namespace xv;
@@ -585,6 +587,57 @@ int xv_plda_adapt(int device, const float* x_dev, int64_t ldx, const int64_t* of
   return with_device(device, "xv_plda_adapt", [&] {
     return launch_plda_adapt(x_dev, ldx, offsets_host, num_groups, d, mean_dev, within_factor_dev, psi_dev, target_energy, dim_dev,
                              eigval_dev, pca_dev, affine_dev, psi_out_dev, ws_dev, ws_bytes, to_stream(stream));
+  });
+}
+
+// shared argument check of the two VB-HMM entry points: the group table
+static int vbx_groups(const char* who, int64_t num_groups, const int64_t* offsets_host, const int32_t* num_spk_host, int r) {
+  if (r < 1 || r > 256) return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= r <= 256, got %d", who, r);
+  if (num_groups < 0 || num_groups > INT32_MAX) return fail(nullptr, XV_ERR_INVALID, "%s: bad group count %lld", who, (long long)num_groups);
+  if (num_groups == 0) return XV_OK;
+  if (!offsets_host || !num_spk_host) return fail(nullptr, XV_ERR_INVALID, "%s: null pointer", who);
+  if (offsets_host[0] < 0) return fail(nullptr, XV_ERR_INVALID, "%s: the first offset is negative", who);
+  for (int64_t g = 0; g < num_groups; ++g) {
+    if (offsets_host[g + 1] < offsets_host[g]) return fail(nullptr, XV_ERR_INVALID, "%s: the offsets decrease at group %lld", who, (long long)g);
+    if (offsets_host[g + 1] - offsets_host[g] > 8192)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: group %lld has %lld rows, at most 8192", who, (long long)g,
+                  (long long)(offsets_host[g + 1] - offsets_host[g]));
+    if (num_spk_host[g] < 1 || num_spk_host[g] > 64)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: group %lld has %d speakers, 1 .. 64", who, (long long)g, num_spk_host[g]);
+  }
+  return XV_OK;
+}
+
+int64_t xv_vbx_workspace(int64_t num_groups, const int64_t* offsets_host, const int32_t* num_spk_host, int r) {
+  if (const int rc = vbx_groups("xv_vbx_workspace", num_groups, offsets_host, num_spk_host, r)) return rc;
+  if (num_groups == 0) return 0;
+  return vbx_workspace_bytes(num_groups, offsets_host, num_spk_host, r);
+}
+
+int xv_vbx(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host, const int32_t* num_spk_host, int64_t num_groups,
+           int d, const double* affine_dev, const double* psi_dev, int r, double* gamma_dev, double* pi_dev, double fa, double fb,
+           double loop_prob, int max_iters, double epsilon, int32_t* labels_dev, double* elbo_dev, int32_t* iters_dev, void* ws_dev,
+           int64_t ws_bytes, void* stream) {
+  if (d < 1 || d > 2048) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_vbx: 1 <= d <= 2048, got %d", d);
+  if (const int rc = vbx_groups("xv_vbx", num_groups, offsets_host, num_spk_host, r)) return rc;
+  if (!(fa > 0.0) || !(fb > 0.0) || fa > DBL_MAX || fb > DBL_MAX)
+    return fail(nullptr, XV_ERR_INVALID, "xv_vbx: Fa and Fb must be positive and finite, got %g, %g", fa, fb);
+  if (!(loop_prob >= 0.0 && loop_prob <= 1.0)) return fail(nullptr, XV_ERR_INVALID, "xv_vbx: loop_prob must be in [0, 1], got %g", loop_prob);
+  if (max_iters < 1) return fail(nullptr, XV_ERR_INVALID, "xv_vbx: max_iters must be >= 1, got %d", max_iters);
+  if (epsilon != epsilon) return fail(nullptr, XV_ERR_INVALID, "xv_vbx: epsilon is NaN (-inf means: run max_iters iterations)");
+  if (num_groups == 0) return XV_OK;
+  if (ldx < d) return fail(nullptr, XV_ERR_INVALID, "xv_vbx: ldx = %lld for d = %d", (long long)ldx, d);
+  if (!affine_dev || !psi_dev || !iters_dev ||
+      (offsets_host[num_groups] > offsets_host[0] && (!x_dev || !gamma_dev || !pi_dev || !labels_dev || !elbo_dev)))
+    return fail(nullptr, XV_ERR_INVALID, "xv_vbx: null pointer");
+  const int64_t need = vbx_workspace_bytes(num_groups, offsets_host, num_spk_host, r);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_vbx: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0), (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7)
+    return fail(nullptr, XV_ERR_INVALID, "xv_vbx: the workspace must be 8-byte aligned (it holds the group table and doubles)");
+  return with_device(device, "xv_vbx", [&] {
+    return launch_vbx(x_dev, ldx, offsets_host, num_spk_host, num_groups, d, affine_dev, psi_dev, r, gamma_dev, pi_dev, fa, fb, loop_prob,
+                      max_iters, epsilon, labels_dev, elbo_dev, iters_dev, ws_dev, to_stream(stream));
   });
 }
 

@@ -309,6 +309,16 @@ hipError_t launch_plda_adapt(const float* x, int64_t ldx, const int64_t* offsets
                              const double* within_factor, const double* psi, double target_energy, int32_t* dim, double* eigval,
                              double* pca, double* affine, double* psi_out, void* ws, int64_t ws_bytes, hipStream_t stream);
 
+// VB-HMM resegmentation of x-vector sequences (csrc/vbx.hip): one projection launch over all rows, then one workgroup per
+// group for all iterations.  offsets [num_groups + 1] and num_spk [num_groups] are host arrays; ws holds
+// vbx_workspace_bytes(...) bytes and receives the group table, stream-ordered.  The caller has checked every argument;
+// num_groups >= 1.
+int64_t vbx_workspace_bytes(int64_t num_groups, const int64_t* offsets, const int32_t* num_spk, int r);
+hipError_t launch_vbx(const float* x, int64_t ldx, const int64_t* offsets, const int32_t* num_spk, int64_t num_groups, int d,
+                      const double* affine, const double* psi, int r, double* gamma, double* pi, double fa, double fb,
+                      double loop_prob, int max_iters, double epsilon, int32_t* labels, double* elbo, int32_t* iters, void* ws,
+                      hipStream_t stream);
+
 // Metric-learning loss heads (csrc/metric_loss.hip): semi-hard triplet, angular triplet (all / hard), ge2e (softmax /
 // contrastive), per group of rows.  offsets is a host array [num_groups + 1]; ws holds at least metric_loss_workspace_bytes
 // bytes.  The caller has checked every argument (ascending offsets, 1 .. 4096 rows per group); num_groups >= 1.
