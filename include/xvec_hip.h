@@ -648,6 +648,69 @@ int xv_loss_classifier(int device, const float* x_dev, int64_t ldx, int64_t n, i
                        double fa, float* loss_dev, float* target_dev, float* lse_dev, int32_t* top1_dev, void* ws_dev,
                        int64_t ws_bytes, void* stream);
 
+/* ---- loss and gradients of the classifier heads (csrc/loss_grad.hip): training a new softmax layer on a frozen encoder
+ * (egs/voxceleb/v1/nnet/lib/finetune.py:6-7).  One call gives the four per-row outputs of xv_loss_classifier, bit for bit, and
+ * the gradients of sum_i s loss_i with s = grad_scale (1 / n for the mean; the call never divides by n, so n = 0 is legal:
+ * XV_OK, nothing touched) with respect to x, the RAW kernel and the bias.  rows_dev [num_classes, ldc] is the transpose of
+ * `softmax/output/kernel`, not normalised: what xv_loss_prepare_classes(normalize = 0) writes.
+ * The rule, with l the label of row i and w^_c the normalised class row (the raw row for XV_LOSS_SOFTMAX):
+ *   forward  z_ic = x_i . w^_c (+ b_c), N_i = max(||x_i||, 1e-12), c_raw = z_il / N_i, c = clip(c_raw, +-(1 - 1e-12)),
+ *            t_i = fs z_il + fa phi(c) N_i (fs = 1 - fa), u_ic = z_ic except u_il = t_i, p_ic = exp(u_ic - lse_i).
+ *   backward sign() and the branch selectors are constants and the clip passes no derivative outside its range, as
+ *            TensorFlow differentiates tf.sign, tf.where, tf.clip_by_value and tf.maximum:
+ *            d_i = s (p_il - 1); G_ic = s p_ic for c != l;
+ *            phi': asoftmax m = 2: 4 |c|; m = 4: sign(2 c^2 - 1) sign(c) (32 c^3 - 16 c); additive margin: 1; additive angle:
+ *            sn = sqrt(max(1 - c^2, 1e-12)), dsn = -c / sn if 1 - c^2 > 1e-12 else 0, phi' = +-(cos m - dsn sin m), + while
+ *            c > cos(pi - m); phi' is multiplied by [c_raw inside the clip range];
+ *            G_il = d_i (fs + fa phi'), r_i = d_i fa (phi - phi' c_raw); softmax and asoftmax m = 1: G_il = d_i, r_i = 0;
+ *            grad_x_i = sum_c G_ic w^_c + r_i x_i / ||x_i|| (the last term 0 when ||x_i|| <= 1e-12);
+ *            gw_c = sum_i G_ic x_i; grad_bias_c = sum_i s (p_ic - [c = l_i]);
+ *            softmax: grad_rows = gw.  Angular heads, q_c = sum_e w_ce^2: grad_rows_c = (gw_c - w^_c (w^_c . gw_c)) / sqrt(q_c)
+ *            if q_c > 1e-12, else gw_c / 1e-6 (the floor of tf.nn.l2_normalize).
+ * Outputs: loss, target, lse, top1 [n]; grad_x_dev [n, ldgx] or NULL; grad_rows_dev [num_classes, ldc] (the columns beyond
+ * embed_dim are left alone); grad_bias_dev [num_classes], required when bias_dev is given.
+ * Properties (tests/test_gpu_loss_grad.py): no floating-point atomics; every output is bit-identical on every repeat, for
+ * every legal ws_bytes (a smaller workspace means smaller row panels; the sums over the rows run in row order whatever the
+ * panel) and whatever the workspace and the outputs held before; grad_x_i and the per-row outputs do not depend on the batch
+ * around row i.  The per-element error bound is derived in the header of csrc/loss_grad.hip.
+ * Checks mirror xv_loss_classifier: 1 <= embed_dim <= 2048 (XV_ERR_UNSUPPORTED); a label outside [0, num_classes) gives
+ * XV_ERR_INVALID after the first kernel with every output untouched (one wait: unfit for hipGraph capture).
+ * Workspace, 16-byte aligned: any ws_bytes >= xv_loss_grad_workspace_min(n, C, E) is legal (XV_ERR_WORKSPACE below it):
+ *   the forward workspace + C (4 round4(E) + 520) for the normalised rows, q and the bias sums + 4 E round4(C) for their
+ *   transpose + 16 n + a panel of P rows of 4 (round4(C) + C + E) bytes each, P = 32.  xv_loss_grad_workspace is the size at
+ *   which P reaches min(round32(n), 1024) and nothing more is used. */
+int64_t xv_loss_grad_workspace(int64_t n, int64_t num_classes, int embed_dim);
+int64_t xv_loss_grad_workspace_min(int64_t n, int64_t num_classes, int embed_dim);
+int xv_loss_classifier_grad(int device, const float* x_dev, int64_t ldx, int64_t n, int embed_dim, const int32_t* labels_dev,
+                            const float* rows_dev, int64_t ldc, int64_t num_classes, const float* bias_dev, int head, double margin,
+                            double fa, double grad_scale, float* loss_dev, float* target_dev, float* lse_dev, int32_t* top1_dev,
+                            float* grad_x_dev, int64_t ldgx, float* grad_rows_dev, float* grad_bias_dev, void* ws_dev,
+                            int64_t ws_bytes, void* stream);
+
+/* ---- one optimizer step on one float32 parameter tensor of `count` elements, in place (csrc/opt_step.hip): TensorFlow 1.x's
+ * rules as the reference uses them (model/trainer.py:225-246, 529-533, model/loss.py:26-33), in this order, every product,
+ * sum, division and square root rounded to float32 on its own (no fused multiply-add), so that numpy float32 written in the
+ * same order gives the same bits (tests/helpers/ref_loss_grad.py).  l2, clip_norm, momentum and learning_rate are rounded to
+ * float32 once on entry.
+ *   1. g <- g + l2 * w                                  (skipped when l2 = 0; pass 0 for a bias)
+ *   2. clip_norm > 0: g <- (g * clip_norm) / max(||g||, clip_norm)          (tf.clip_by_norm of this tensor alone)
+ *      ||g|| = float32(sqrt(sum g^2)) with the sum in double in a fixed order, no atomics: workgroup b owns the elements
+ *      [4096 b, 4096 b + 4096), thread t adds j = 4096 b + 256 i + t for i = 0 .. 15, the 64 lanes of a wave by a shuffle tree
+ *      (offsets 32 .. 1), the four waves in order; then lane l adds the partials l, l + 64, ... and the same tree.
+ *   3. XV_OPT_SGD:       w <- w - lr * g
+ *      XV_OPT_MOMENTUM:  a <- (m * a) + g;  w <- w - lr * a;  with use_nesterov  w <- w - lr * (g + m * a)      (a: slot0)
+ *      XV_OPT_ADAM:      m <- (0.9 * m) + (0.1' * g);  v <- (0.999 * v) + (0.001' * (g * g));                    (slot0, slot1)
+ *                        w <- w - (lr_t * m) / (sqrt(v) + 1e-8),  lr_t = float32(lr sqrt(1 - 0.999^step) / (1 - 0.9^step)) from
+ *                        double on the host, 0.1' = float32(1.0 - 0.9), 0.001' = float32(1.0 - 0.999), step counted from 1.
+ * grad_dev is not written.  Unused slots may be NULL.  A non-finite or negative learning_rate, a negative l2 or clip_norm or
+ * an unknown kind gives XV_ERR_INVALID before any launch.  ws_dev (8-byte aligned, xv_opt_workspace(count) bytes) is needed
+ * with clip_norm > 0 only. */
+enum { XV_OPT_SGD = 0, XV_OPT_MOMENTUM = 1, XV_OPT_ADAM = 2 };
+int64_t xv_opt_workspace(int64_t count);
+int xv_opt_step(int device, int kind, int use_nesterov, float* w_dev, const float* grad_dev, float* slot0_dev, float* slot1_dev,
+                int64_t count, double learning_rate, double l2, double clip_norm, double momentum, int64_t step, void* ws_dev,
+                int64_t ws_bytes, void* stream);
+
 /* ---- metric-learning loss heads on the GPU (csrc/metric_loss.hip): what validation needs for a checkpoint trained with
  * `semihard_triplet_loss` (model/loss.py:387-527) or `angular_triplet_loss` (:530-663; validated with `e2e_valid_loss`,
  * :666-734, model/trainer.py:424-427).  Pinned to the reference's float64 numpy twins (model/test_utils.py:21-86, 118-154,

@@ -376,6 +376,90 @@ int xv_loss_classifier(int device, const float* x_dev, int64_t ldx, int64_t n, i
   return XV_OK;
 }
 
+int64_t xv_loss_grad_workspace(int64_t n, int64_t num_classes, int embed_dim) {
+  return loss_grad_workspace_bytes(n, num_classes, embed_dim, 0);
+}
+
+int64_t xv_loss_grad_workspace_min(int64_t n, int64_t num_classes, int embed_dim) {
+  return loss_grad_workspace_bytes(n, num_classes, embed_dim, 1);
+}
+
+// xv_loss_classifier and TensorFlow's gradients of it with respect to x, the raw kernel and the bias (include/xvec_hip.h)
+int xv_loss_classifier_grad(int device, const float* x_dev, int64_t ldx, int64_t n, int embed_dim, const int32_t* labels_dev,
+                            const float* rows_dev, int64_t ldc, int64_t num_classes, const float* bias_dev, int head, double margin,
+                            double fa, double grad_scale, float* loss_dev, float* target_dev, float* lse_dev, int32_t* top1_dev,
+                            float* grad_x_dev, int64_t ldgx, float* grad_rows_dev, float* grad_bias_dev, void* ws_dev,
+                            int64_t ws_bytes, void* stream) {
+  if (!x_dev || !labels_dev || !rows_dev || !loss_dev || !target_dev || !lse_dev || !top1_dev || !grad_rows_dev || !ws_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: null pointer");
+  if (embed_dim < 1 || embed_dim > 2048)
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_classifier_grad: 1 <= embed_dim <= 2048, got %d", embed_dim);
+  if (n < 0 || n > INT32_MAX || num_classes < 1 || num_classes > INT32_MAX || ldx < embed_dim || ldc < embed_dim ||
+      (grad_x_dev && ldgx < embed_dim))
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: bad dimensions");
+  if (head < XV_LOSS_SOFTMAX || head > XV_LOSS_ARCSOFTMAX) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: unknown head %d", head);
+  if (bias_dev && head != XV_LOSS_SOFTMAX) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: only the softmax head has a bias");
+  if (bias_dev && !grad_bias_dev) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: a bias needs grad_bias_dev");
+  int m = 0;
+  if (head == XV_LOSS_ASOFTMAX) {
+    if (margin != 1.0 && margin != 2.0 && margin != 4.0)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_loss_classifier_grad: m=%g is not supported (asoftmax: 1, 2 or 4)", margin);   // loss.py:168
+    m = (int)margin;
+  }
+  if (!(fa >= 0.0 && fa <= 1.0) || !std::isfinite(margin) || !std::isfinite(grad_scale))
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: bad margin, fa or grad_scale");
+  if ((reinterpret_cast<uintptr_t>(ws_dev) & 15) != 0)
+    return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: the workspace must be 16-byte aligned");
+  const int64_t need = loss_grad_workspace_bytes(n, num_classes, embed_dim, 1);
+  if (ws_bytes < need)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_loss_classifier_grad: workspace of %lld bytes, at least %lld needed", (long long)ws_bytes,
+                (long long)need);
+  if (n == 0) return XV_OK;
+  DeviceGuard g(device);
+  if (!g.ok) return fail(nullptr, XV_ERR_HIP, "cannot select HIP device %d", device);
+  hipStream_t s = to_stream(stream);
+  hipError_t e = launch_loss_grad_forward_rows(x_dev, ldx, n, embed_dim, labels_dev, rows_dev, ldc, num_classes, bias_dev, head, m,
+                                               margin, fa, ws_dev, s);
+  int bad = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, ws_dev, sizeof(int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "loss_grad rows failed: %s", hipGetErrorString(e));
+  if (bad) return fail(nullptr, XV_ERR_INVALID, "xv_loss_classifier_grad: a label lies outside [0, %lld)", (long long)num_classes);
+  e = launch_loss_grad_rest(x_dev, ldx, (int)n, embed_dim, labels_dev, rows_dev, ldc, (int)num_classes, bias_dev, head, m, margin, fa,
+                            grad_scale, loss_dev, target_dev, lse_dev, top1_dev, grad_x_dev, ldgx, grad_rows_dev,
+                            bias_dev ? grad_bias_dev : nullptr, ws_dev, ws_bytes, s);
+  if (e != hipSuccess) return fail(nullptr, XV_ERR_HIP, "loss_grad launch failed: %s", hipGetErrorString(e));
+  return XV_OK;
+}
+
+int64_t xv_opt_workspace(int64_t count) { return opt_workspace_bytes(count); }
+
+// model/trainer.py:225-246, 529-533 and model/loss.py:26-33: l2, tf.clip_by_norm, then sgd / momentum / adam
+int xv_opt_step(int device, int kind, int use_nesterov, float* w_dev, const float* grad_dev, float* slot0_dev, float* slot1_dev,
+                int64_t count, double learning_rate, double l2, double clip_norm, double momentum, int64_t step, void* ws_dev,
+                int64_t ws_bytes, void* stream) {
+  if (kind < XV_OPT_SGD || kind > XV_OPT_ADAM) return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: unknown kind %d", kind);
+  if (count < 0) return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: count = %lld", (long long)count);
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: learning_rate must be finite and >= 0");
+  if (!(l2 >= 0.0) || !std::isfinite(l2) || !(clip_norm >= 0.0) || !std::isfinite(clip_norm))
+    return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: l2 and clip_norm must be finite and >= 0");
+  if (kind == XV_OPT_MOMENTUM && (!std::isfinite(momentum) || momentum < 0.0)) return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: bad momentum");
+  if (kind == XV_OPT_ADAM && step < 1) return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: adam counts its steps from 1, got %lld", (long long)step);
+  if (count == 0) return XV_OK;
+  if (!w_dev || !grad_dev || (kind != XV_OPT_SGD && !slot0_dev) || (kind == XV_OPT_ADAM && !slot1_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: null pointer");
+  if ((float)clip_norm > 0.f) {
+    if (!ws_dev || ws_bytes < opt_workspace_bytes(count))
+      return fail(nullptr, XV_ERR_WORKSPACE, "xv_opt_step: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                  (long long)opt_workspace_bytes(count));
+    if ((reinterpret_cast<uintptr_t>(ws_dev) & 7) != 0) return fail(nullptr, XV_ERR_INVALID, "xv_opt_step: the workspace must be 8-byte aligned");
+  }
+  return with_device(device, "xv_opt_step", [&] {
+    return launch_opt_step(kind, use_nesterov ? 1 : 0, w_dev, grad_dev, slot0_dev, slot1_dev, count, learning_rate, l2, clip_norm,
+                           momentum, step, ws_dev, to_stream(stream));
+  });
+}
+
 int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
                     int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
                     int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,

@@ -1,0 +1,559 @@
+// Loss AND gradients of the four classifier heads in one call: what training a new softmax layer on a frozen encoder needs
+// (egs/voxceleb/v1/nnet/lib/finetune.py:6-7).  The rule is stated in include/xvec_hip.h (xv_loss_classifier_grad) and restated
+// in float64 numpy in tests/helpers/ref_loss_grad.py; TensorFlow's autodiff of model/loss.py:9-48, 80-198, 201-286, 289-384
+// followed by tf.losses.sparse_softmax_cross_entropy gives the same numbers (tests/test_loss_grad_host.py).
+//
+// Stages, all stream-ordered, no floating-point atomics anywhere:
+//  * grad_normalize_kernel: raw class rows [C, ldc] -> normalised rows w^ in the workspace and q_c = sum_e w_ce^2 in double.
+//    The sum runs in the order of loss_classes_kernel (csrc/loss.hip: four fma chains over e = k mod 4, then (p0 + p1) +
+//    (p2 + p3)), so w^ has the bits xv_loss_prepare_classes writes.  Softmax skips this and uses the raw rows.
+//  * the three forward kernels of csrc/loss.hip, unchanged, on those rows: loss, target logit, lse and top1 are the bits of
+//    xv_loss_classifier.  The target goes to the workspace first and is copied out after the label check, so that a bad label
+//    leaves every output untouched.
+//  * grad_label_kernel, one wave per row: the label's entry G_il and the coefficient r_i / ||x_i|| in double from the stored
+//    rows, as loss_rows_kernel evaluates the target: the margin multiplies an error of the cosine by |phi'|, so this one entry
+//    does not come from the fp32 tile.
+//  * per PANEL of P rows (P a multiple of 32, at most 1024, as many as the workspace holds), in ascending row order:
+//      - nt_gemm_kernel<EPI_G>: z = x . w^T again with v_mfma_f32_32x32x2_f32 (the tile skeleton of loss_tile_kernel: K in
+//        steps of 32, [row][32 + 4] floats in LDS, register-staged double buffering, zero-filled edges), G_ic = s expf(z_ic -
+//        lse_i), the entry at column l_i swapped for G_il by the tile that owns it; written as G [P, C] and G^T [C, P];
+//      - grad_bias: one wave per class, lane l adds the rows i = l (mod 64) of the batch in ascending order to a double that
+//        lives in the workspace between the panels; a fixed butterfly over the 64 lanes after the last panel;
+//      - nt_gemm_kernel<EPI_X>: grad_x_panel = G . (w^T)^T, K = C over a transposed copy of the rows, 64 x 64 tiles (a
+//        512 x 512 result is 64 tiles, not 16); the epilogue adds r_i x_i / ||x_i|| in double and rounds once;
+//      - nt_gemm_kernel<EPI_ACC>: gw += G^T . (x_panel^T)^T, K = P.  The accumulators START from the value the earlier panels
+//        left in grad_rows, so the sum over the rows is ONE fmaf chain in ascending row index whatever P is: P is a multiple
+//        of the K step, every K step takes its rows in the same fixed order, and rows beyond n are zero-filled (adding
+//        0 * 0 changes nothing but the sign of a zero, and it is added iff n is no multiple of 32, whatever P).  The first
+//        panel starts from zero, not from what grad_rows held.
+//  * grad_finish_kernel (angular heads), one wave per class: grad_rows_c = (gw_c - w^_c (w^_c . gw_c)) / sqrt(q_c) with w^ =
+//    w / sqrt(q) and the product in double, or gw_c / 1e-6 where q_c <= 1e-12 (the floor of tf.nn.l2_normalize), in place.
+// Every element of every output is a function of the inputs alone: a fixed order by row index (gw, grad_bias) or by class index
+// (grad_x), one writer per element, no value read from memory this call did not write.  grad_x_i and the per-row outputs use
+// row i and the class rows only, so they do not depend on the batch around row i.
+//
+// Error bound (u = 2^-24; checked per element in tests/test_gpu_loss_grad.py, restated in ref_loss_grad.bounds).  With B_i the
+// logit bound and bl_i the lse bound of csrc/loss.hip, L_i = max(1, fs + fa |phi'|) with the phi' of the backward pass (0 where
+// c_raw lies outside the clip range: there the target is fs z + const):
+//   p_ic, c != l:   z and lse are off by at most B_i and bl_i, the subtraction z - lse rounds by u (|z| + |lse|), expf is 2 ulp
+//                   = 4 u, s is rounded to float (u) and multiplied (u):  |dG_ic| <= e_i G_ic,
+//                   e_i = 1.01 (B_i + bl_i + u (||x_i|| max||w|| + |lse_i|)) + 6 u      (1.01: exp(d) - 1 <= 1.01 d for d <= 0.01)
+//   label entry:    p_il = exp(t_i - lse_i) in double with t_i off by L_i B_i: |dd_i| <= s p_il 1.01 (L_i B_i + bl_i).  The
+//                   stored w^ moves the cosine by at most u, phi' by phi'' u and phi by |phi'| u (phi'' = 4, |96 c^2 - 16|, 0,
+//                   sin m / sn^3 for asoftmax 2, 4, the additive margin and the additive angle):
+//                   |dG_il| <= |dd_i| (fs + fa |phi'|) + |d_i| fa phi'' u + u |G_il|            (rounded once)
+//                   |dr_i|  <= |dd_i| fa |phi - phi' c| + |d_i| fa (2 |phi'| + |c| phi'') u
+//   grad_x_ie:      sum_c |dG_ic| |w^_ce|  +  (C + 2) u sum_c |G_ic w^_ce|   (fmaf chain of length C, the rounding of w^)
+//                   + |dr_i| |x_ie| / ||x_i||  +  2 u |grad_x_ie|           (the r term and the last rounding)
+//   gw_ce:          a_ce = sum_i |dG_ic| |x_ie| + (n + 32) u sum_i |G_ic x_ie|       (fmaf chain of length n, padded to 32)
+//   grad_bias_c:    sum_i |dG_ic| + u |grad_bias_c|                                 (double sum, rounded once)
+//   grad_rows_ce:   softmax: a_ce + u |grad_rows_ce|.  Angular: with D = sum_e |w^_ce| a_ce the error of w^_c . gw_c,
+//                   (a_ce + |w^_ce| D) / sqrt(q_c) + 2 u |grad_rows_ce|; below the floor a_ce / 1e-6 + u |grad_rows_ce|.
+#include <mutex>
+
+#include "xv_kernels.h"
+
+namespace xv {
+
+typedef float gf32x16 __attribute__((ext_vector_type(16)));
+typedef float gf32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int GBK = 32;
+constexpr int GLDT = GBK + 4;                 // padded LDS row (floats), as csrc/loss.hip
+constexpr int kMaxPanel = 1024;
+constexpr int kPanelStep = 32;                // a panel is a whole number of K steps of the gw product
+
+__host__ __device__ constexpr int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+__device__ __forceinline__ double gwave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------- normalised rows
+// 16 classes per wave, 4 lanes per class: lane k of a class sums e = k, k + 4, ... (the order of loss_classes_kernel)
+__global__ __launch_bounds__(256) void grad_normalize_kernel(const float* __restrict__ rows, int64_t ldc, int E, int64_t C,
+                                                             float* __restrict__ what, int64_t ldh, double* __restrict__ q) {
+  const int k = threadIdx.x & 3;
+  const int64_t c = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
+  const bool ok = c < C;
+  const float* r = rows + (ok ? c : 0) * ldc;
+  double ss = 0.0;
+  if (ok)
+    for (int e = k; e < E; e += 4) {
+      const double v = (double)r[e];
+      ss = fma(v, v, ss);
+    }
+  const double p1 = __shfl_xor(ss, 1, 64);              // k ^ 1
+  const double a = (k & 1) ? p1 + ss : ss + p1;         // p0 + p1 (k < 2) or p2 + p3, the lower index first
+  const double b = __shfl_xor(a, 2, 64);
+  const double s = (k & 2) ? b + a : a + b;             // (p0 + p1) + (p2 + p3)
+  if (!ok) return;
+  const double inv = 1.0 / sqrt(s > 1e-12 ? s : 1e-12);
+  for (int e = k; e < E; e += 4) what[c * ldh + e] = (float)((double)r[e] * inv);
+  if (k == 0) q[c] = s;
+}
+
+// dst [cols, ldd] = src [rows, lds]^T, 64 x 64 through LDS; grid (ceil(rows / 64), ceil(cols / 64)), cols <= 2048 here
+__global__ __launch_bounds__(256) void grad_transpose_kernel(const float* __restrict__ src, int64_t lds, int64_t rows, int64_t cols,
+                                                             float* __restrict__ dst, int64_t ldd) {
+  __shared__ float tile[64][65];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t r0 = (int64_t)blockIdx.x * 64, c0 = (int64_t)blockIdx.y * 64;      // rows (classes) on x: no 65535 limit
+  for (int rl = wave; rl < 64; rl += 4)
+    tile[rl][lane] = (r0 + rl < rows && c0 + lane < cols) ? src[(r0 + rl) * lds + c0 + lane] : 0.f;
+  __syncthreads();
+  for (int cl = wave; cl < 64; cl += 4)
+    if (c0 + cl < cols && r0 + lane < rows) dst[(c0 + cl) * ldd + r0 + lane] = tile[lane][cl];
+}
+
+// ---------------------------------------------------------------------------------------------- the label's entry
+struct GradHead {
+  int head, m;
+  double margin, cos_m, sin_m, cos_pi_m, fa;    // fa = 0 switches the margin off (softmax, asoftmax m = 1)
+  double s;                                     // grad_scale
+};
+
+__global__ __launch_bounds__(256) void grad_label_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int E,
+                                                         const int32_t* __restrict__ labels, const float* __restrict__ rows,
+                                                         int64_t ldr, const float* __restrict__ bias, GradHead hp,
+                                                         const float* __restrict__ lse, float* __restrict__ gl,
+                                                         double* __restrict__ coef) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  const int32_t lab = labels[r];                  // checked by the forward before this launch
+  const float* xr = x + r * ldx;
+  const float* wr = rows + (int64_t)lab * ldr;
+  float mx = 0.f;
+  double dot = 0.0;
+  for (int c = lane; c < E; c += 64) {
+    mx = fmaxf(mx, fabsf(xr[c]));
+    dot = fma((double)xr[c], (double)wr[c], dot);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  dot = gwave_sum_f64(dot);
+  const double l = (double)lse[r];
+  double g, rc = 0.0;
+  if (hp.fa == 0.0) {
+    const double t = dot + ((hp.head == XV_LOSS_SOFTMAX && bias) ? (double)bias[lab] : 0.0);
+    g = hp.s * (exp(t - l) - 1.0);
+  } else {
+    double xn = 0.0;
+    if (mx > 0.f && mx <= 3.4028234e38f) {
+      const int e = ilogbf(mx);
+      double ss = 0.0;
+      for (int c = lane; c < E; c += 64) {
+        const double v = (double)ldexpf(xr[c], -e);
+        ss = fma(v, v, ss);
+      }
+      xn = ldexp(sqrt(gwave_sum_f64(ss)), e);
+    } else if (mx != 0.f) {
+      xn = (double)mx;
+    }
+    const double fn = xn > 1e-12 ? xn : 1e-12;
+    const double craw = dot / fn;
+    const double lo = -1.0 + 1e-12, hi = 1.0 - 1e-12;
+    const double inside = (craw >= lo && craw <= hi) ? 1.0 : 0.0;      // tf.clip_by_value passes the gradient inside [lo, hi]
+    const double c = craw < lo ? lo : (craw > hi ? hi : craw);
+    double phi = c, dphi = 1.0;
+    if (hp.head == XV_LOSS_ASOFTMAX) {
+      const double s0 = c > 0.0 ? 1.0 : (c < 0.0 ? -1.0 : 0.0);
+      const double c2 = c * c;
+      if (hp.m == 2) {
+        phi = 2.0 * s0 * c2 - 1.0;
+        dphi = 4.0 * fabs(c);
+      } else if (hp.m == 4) {
+        const double qq = 2.0 * c2 - 1.0;
+        const double s3 = (qq > 0.0 ? 1.0 : (qq < 0.0 ? -1.0 : 0.0)) * s0;
+        const double s4 = 2.0 * s0 + s3 - 3.0;
+        phi = s3 * (8.0 * c2 * c2 - 8.0 * c2 + 1.0) + s4;
+        dphi = s3 * (32.0 * c2 * c - 16.0 * c);
+      }
+    } else if (hp.head == XV_LOSS_AMSOFTMAX) {
+      phi = c - hp.margin;
+    } else {
+      const double s2 = 1.0 - c * c;
+      const double sn = sqrt(s2 > 1e-12 ? s2 : 1e-12);
+      const double dsn = s2 > 1e-12 ? -c / sn : 0.0;
+      const double cpm = c * hp.cos_m - sn * hp.sin_m;
+      const double dcpm = hp.cos_m - dsn * hp.sin_m;
+      const bool first = c > hp.cos_pi_m;
+      phi = first ? cpm : -cpm - 2.0;
+      dphi = first ? dcpm : -dcpm;
+    }
+    dphi *= inside;
+    const double t = (1.0 - hp.fa) * dot + hp.fa * (phi * fn);
+    const double d = hp.s * (exp(t - l) - 1.0);
+    g = d * ((1.0 - hp.fa) + hp.fa * dphi);
+    const double rr = d * hp.fa * (phi - dphi * craw);
+    rc = xn > 1e-12 ? rr / xn : 0.0;
+  }
+  if (lane == 0) {
+    gl[r] = (float)g;
+    coef[r] = rc;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- C = A . B^T, exact fp32
+enum { EPI_G = 0, EPI_X = 1, EPI_ACC = 2 };
+
+struct NtArgs {
+  const float* A; int64_t lda; int M;         // [M, K]
+  const float* B; int64_t ldb; int N;         // [N, K]
+  int K;
+  int nMt, nNt;
+  // EPI_G: rows are the panel's rows (row pointers already offset by the panel's first row)
+  const float* bias; const int32_t* labels; const float* lse; const float* gl; float sf;
+  float* G; int64_t ldg; float* GT; int64_t ldgt;
+  // EPI_X: out = acc + coef_i x_ie
+  const double* coef; const float* x; int64_t ldx;
+  // EPI_X, EPI_ACC
+  float* out; int64_t ldo; int first;
+};
+
+template <int BM, int BN, bool VEC, int EPI>
+__global__ __launch_bounds__(256, 2) void nt_gemm_kernel(NtArgs p) {
+  constexpr int TA = BM * GLDT, TB = BN * GLDT;      // floats per operand tile
+  constexpr int WM = BM / 2, WN = BN / 2;            // per wave
+  constexpr int AI = WM / 32, BI = WN / 32;
+  constexpr int RA = BM / 32, RB = BN / 32;          // staging passes
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* As = smem;                    // [2][BM][GLDT]
+  float* Bs = smem + 2 * TA;           // [2][BN][GLDT]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r32 = lane & 31, h = lane >> 5;
+  const int c4 = tid & 7, lr = tid >> 3;
+  const int nk = (p.K + GBK - 1) / GBK;
+  const int mt = (int)(blockIdx.x % (unsigned)p.nMt), nt = (int)(blockIdx.x / (unsigned)p.nMt);
+  const int m0 = mt * BM, n0 = nt * BN;
+
+  gf32x4 ra[RA], rb[RB];
+  auto load_rows = [&](const float* base, int64_t ld, int row0, int nrows, int kt, gf32x4* r, int passes) {
+    const int k = kt * GBK + c4 * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (i >= passes) break;
+      const int row = row0 + lr + 32 * i;
+      gf32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (row < nrows && k < p.K) {
+        const float* src = base + (int64_t)row * ld + k;
+        if (VEC && k + 4 <= p.K) {
+          v = *reinterpret_cast<const gf32x4*>(src);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (k + e < p.K) v[e] = src[e];
+        }
+      }
+      r[i] = v;
+    }
+  };
+  auto load_tiles = [&](int kt) {
+    load_rows(p.A, p.lda, m0, p.M, kt, ra, RA);
+    load_rows(p.B, p.ldb, n0, p.N, kt, rb, RB);
+  };
+  auto store_tiles = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < RA; ++i) *reinterpret_cast<gf32x4*>(As + buf * TA + (lr + 32 * i) * GLDT + c4 * 4) = ra[i];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) *reinterpret_cast<gf32x4*>(Bs + buf * TB + (lr + 32 * i) * GLDT + c4 * 4) = rb[i];
+  };
+
+  // accumulator layout: element e of lane (r32, h) is D[8 * (e / 4) + 4 * h + e % 4][r32] (A row, B row)
+  gf32x16 acc[AI][BI];
+#pragma unroll
+  for (int ai = 0; ai < AI; ++ai)
+#pragma unroll
+    for (int bi = 0; bi < BI; ++bi)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        float v = 0.f;
+        if (EPI == EPI_ACC && !p.first) {       // the chain over the rows goes on from where the last panel left it
+          const int gi = m0 + wm * WM + ai * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
+          const int gj = n0 + wn * WN + bi * 32 + r32;
+          if (gi < p.M && gj < p.N) v = p.out[(int64_t)gi * p.ldo + gj];
+        }
+        acc[ai][bi][e] = v;
+      }
+
+  load_tiles(0);
+  store_tiles(0);
+  __syncthreads();
+
+  const float* a_base = As + (wm * WM + r32) * GLDT + 4 * h;
+  const float* b_base = Bs + (wn * WN + r32) * GLDT + 4 * h;
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) load_tiles(kt + 1);
+    const float* ap = a_base + cur * TA;
+    const float* bp = b_base + cur * TB;
+#pragma unroll
+    for (int q = 0; q < GBK / 8; ++q) {
+      // lane (r, h) feeds k = 8 q + 4 h + j of both operands: the order of the chain is a function of k alone
+      gf32x4 a[AI], b[BI];
+#pragma unroll
+      for (int ai = 0; ai < AI; ++ai) a[ai] = *reinterpret_cast<const gf32x4*>(ap + ai * 32 * GLDT + q * 8);
+#pragma unroll
+      for (int bi = 0; bi < BI; ++bi) b[bi] = *reinterpret_cast<const gf32x4*>(bp + bi * 32 * GLDT + q * 8);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int ai = 0; ai < AI; ++ai)
+#pragma unroll
+          for (int bi = 0; bi < BI; ++bi)
+            acc[ai][bi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ai][j], b[bi][j], acc[ai][bi], 0, 0, 0);
+    }
+    if (kt + 1 < nk) store_tiles(cur ^ 1);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int bi = 0; bi < BI; ++bi) {
+    const int gj = n0 + wn * WN + bi * 32 + r32;
+    const bool jok = gj < p.N;
+    float bj = 0.f;
+    if (EPI == EPI_G) bj = (p.bias && jok) ? p.bias[gj] : 0.f;
+#pragma unroll
+    for (int ai = 0; ai < AI; ++ai)
+#pragma unroll
+      for (int e4 = 0; e4 < 4; ++e4) {
+        const int gi0 = m0 + wm * WM + ai * 32 + 8 * e4 + 4 * h;
+        if (EPI == EPI_G) {
+          gf32x4 g4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int gi = gi0 + e;
+            if (gi < p.M && jok) {
+              const float z = acc[ai][bi][4 * e4 + e] + bj;
+              const float g = p.labels[gi] == gj ? p.gl[gi] : p.sf * expf(z - p.lse[gi]);
+              g4[e] = g;
+              p.G[(int64_t)gi * p.ldg + gj] = g;
+            }
+          }
+          if (jok && gi0 < p.M) *reinterpret_cast<gf32x4*>(p.GT + (int64_t)gj * p.ldgt + gi0) = g4;   // gi0 + 3 < ldgt: both multiples of 4
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int gi = gi0 + e;
+            if (gi < p.M && jok) {
+              float v = acc[ai][bi][4 * e4 + e];
+              if (EPI == EPI_X) v = (float)((double)v + p.coef[gi] * (double)p.x[(int64_t)gi * p.ldx + gj]);
+              p.out[(int64_t)gi * p.ldo + gj] = v;
+            }
+          }
+        }
+      }
+  }
+}
+
+// grad_bias: one wave per class.  Lane l owns the rows i = l (mod 64) of the WHOLE batch and adds them in ascending order to
+// its double gb[c][l], which lives in the workspace between the panels (row0 is the panel's first row, a multiple of 32, so
+// the lane of a row does not depend on the panel); the last panel adds the 64 lanes by a fixed xor butterfly and rounds once.
+// The reads run along the rows of G^T: coalesced.
+__global__ __launch_bounds__(256) void grad_bias_kernel(const float* __restrict__ GT, int64_t ldgt, int rows, int64_t row0, int64_t C,
+                                                        int first, int last, double* __restrict__ gb, float* __restrict__ grad_bias) {
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= C) return;
+  double a = first ? 0.0 : gb[c * 64 + lane];
+  const float* g = GT + c * ldgt;
+  for (int i = (int)((lane - row0) & 63); i < rows; i += 64) a += (double)g[i];
+  if (!last) {
+    gb[c * 64 + lane] = a;
+    return;
+  }
+  a = gwave_sum_f64(a);
+  if (lane == 0) grad_bias[c] = (float)a;
+}
+
+// backward of tf.nn.l2_normalize(w, dim=0), one wave per class, in place over gw
+__global__ __launch_bounds__(256) void grad_finish_kernel(const float* __restrict__ rows, int64_t ldc, int E, int64_t C,
+                                                          const double* __restrict__ q, float* __restrict__ grad_rows) {
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= C) return;
+  const float* w = rows + c * ldc;
+  float* g = grad_rows + c * ldc;
+  const double qc = q[c];
+  if (!(qc > 1e-12)) {
+    for (int e = lane; e < E; e += 64) g[e] = (float)((double)g[e] / 1e-6);
+    return;
+  }
+  const double inv = 1.0 / sqrt(qc);
+  double dot = 0.0;
+  for (int e = lane; e < E; e += 64) dot = fma((double)w[e] * inv, (double)g[e], dot);
+  dot = gwave_sum_f64(dot);
+  for (int e = lane; e < E; e += 64) g[e] = (float)(((double)g[e] - ((double)w[e] * inv) * dot) * inv);
+}
+
+template <int BM, int BN, bool VEC, int EPI>
+hipError_t launch_nt(const NtArgs& a, hipStream_t s) {
+  constexpr size_t smem = (size_t)2 * (BM + BN) * GLDT * sizeof(float);
+  static std::mutex mu;            // per-device attribute; any thread may make the first launch on a device
+  static bool set_for[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    if (!set_for[dev & 63]) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nt_gemm_kernel<BM, BN, VEC, EPI>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e != hipSuccess) return e;
+      set_for[dev & 63] = true;
+    }
+  }
+  const int64_t tiles = (int64_t)a.nMt * a.nNt;
+  hipLaunchKernelGGL((nt_gemm_kernel<BM, BN, VEC, EPI>), dim3((unsigned)tiles), dim3(256), smem, s, a);
+  return hipGetLastError();
+}
+
+bool grad_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+struct GradLayout {
+  int64_t ldh, ldt;                 // row of w^ [C, ldh] and of (w^)^T [E, ldt], floats
+  int64_t fwd, what, q, wt, tgt, gl, coef, gb, panel;     // byte offsets
+  int64_t per_row;                  // bytes of the panel per row: G, G^T and x^T
+};
+
+GradLayout grad_layout(int64_t n, int64_t C, int E) {
+  GradLayout L;
+  L.ldh = up(E, 4);
+  L.ldt = up(C, 4);
+  int64_t o = 0;
+  L.fwd = o;   o += up(loss_workspace_bytes(n, C), 256);
+  L.what = o;  o += up(C * L.ldh * 4, 256);
+  L.q = o;     o += up(C * 8, 256);
+  L.wt = o;    o += up((int64_t)E * L.ldt * 4, 256);
+  L.tgt = o;   o += up(n * 4, 256);
+  L.gl = o;    o += up(n * 4, 256);
+  L.coef = o;  o += up(n * 8, 256);
+  L.gb = o;    o += up(C * 64 * 8, 256);              // 64 lane sums per class
+  L.panel = o;
+  L.per_row = 4 * (L.ldt + C + E);
+  return L;
+}
+
+int64_t full_panel(int64_t n) { return n < kMaxPanel ? up(n, kPanelStep) : kMaxPanel; }
+
+}  // namespace
+
+int64_t loss_grad_workspace_bytes(int64_t n, int64_t C, int E, int least) {
+  if (n <= 0 || C <= 0 || E <= 0) return 0;
+  const GradLayout L = grad_layout(n, C, E);
+  return L.panel + (least ? kPanelStep : full_panel(n)) * L.per_row;
+}
+
+hipError_t launch_loss_grad_forward_rows(const float* x, int64_t ldx, int64_t n, int E, const int32_t* labels, const float* rows,
+                                         int64_t ldc, int64_t C, const float* bias, int head, int m, double margin, double fa,
+                                         void* ws, hipStream_t s) {
+  const GradLayout L = grad_layout(n, C, E);
+  char* w = static_cast<char*>(ws);
+  const float* use = rows;
+  int64_t ldu = ldc;
+  if (head != XV_LOSS_SOFTMAX) {
+    float* what = reinterpret_cast<float*>(w + L.what);
+    hipLaunchKernelGGL(grad_normalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, s, rows, ldc, E, C, what, L.ldh,
+                       reinterpret_cast<double*>(w + L.q));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    use = what;
+    ldu = L.ldh;
+  }
+  return launch_loss_rows(x, ldx, n, E, labels, use, ldu, C, bias, head, m, margin, fa, reinterpret_cast<float*>(w + L.tgt),
+                          w + L.fwd, s);
+}
+
+hipError_t launch_loss_grad_rest(const float* x, int64_t ldx, int n, int E, const int32_t* labels, const float* rows, int64_t ldc,
+                                 int C, const float* bias, int head, int m, double margin, double fa, double grad_scale,
+                                 float* loss, float* target, float* lse, int32_t* top1, float* grad_x, int64_t ldgx,
+                                 float* grad_rows, float* grad_bias, void* ws, int64_t ws_bytes, hipStream_t s) {
+  const GradLayout L = grad_layout(n, C, E);
+  char* w = static_cast<char*>(ws);
+  const bool angular = head != XV_LOSS_SOFTMAX;
+  const float* use = angular ? reinterpret_cast<const float*>(w + L.what) : rows;
+  const int64_t ldu = angular ? L.ldh : ldc;
+  float* tgt = reinterpret_cast<float*>(w + L.tgt);
+  float* gl = reinterpret_cast<float*>(w + L.gl);
+  double* coef = reinterpret_cast<double*>(w + L.coef);
+  double* gb = reinterpret_cast<double*>(w + L.gb);
+  float* wt = reinterpret_cast<float*>(w + L.wt);
+
+  hipError_t e = launch_loss_tiles(x, ldx, n, E, labels, use, ldu, C, bias, tgt, loss, lse, top1, w + L.fwd, s);
+  if (e != hipSuccess) return e;
+  e = hipMemcpyAsync(target, tgt, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return e;
+
+  GradHead hp = {};
+  hp.head = head;
+  hp.m = m;
+  hp.margin = margin;
+  hp.cos_m = cos(margin);
+  hp.sin_m = sin(margin);
+  hp.cos_pi_m = cos(3.14159265358979323846 - margin);
+  hp.fa = (head == XV_LOSS_SOFTMAX || (head == XV_LOSS_ASOFTMAX && m == 1)) ? 0.0 : fa;
+  hp.s = grad_scale;
+  hipLaunchKernelGGL(grad_label_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, ldx, (int64_t)n, E, labels, use, ldu, bias,
+                     hp, lse, gl, coef);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (grad_x) {
+    hipLaunchKernelGGL(grad_transpose_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)((E + 63) / 64)), dim3(256), 0, s, use, ldu,
+                       (int64_t)C, (int64_t)E, wt, L.ldt);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+
+  int64_t P = (ws_bytes - L.panel) / L.per_row / kPanelStep * kPanelStep;
+  if (P > full_panel(n)) P = full_panel(n);
+  float* G = reinterpret_cast<float*>(w + L.panel);
+  float* GT = G + P * L.ldt;
+  float* XT = GT + (int64_t)C * P;
+  for (int64_t r0 = 0; r0 < n; r0 += P) {
+    const int pn = (int)(n - r0 < P ? n - r0 : P);
+    const float* xp = x + r0 * ldx;
+    NtArgs a = {};
+    a.A = xp; a.lda = ldx; a.M = pn; a.B = use; a.ldb = ldu; a.N = C; a.K = E;
+    a.nMt = (pn + 127) / 128; a.nNt = (C + 127) / 128;
+    a.bias = bias; a.labels = labels + r0; a.lse = lse + r0; a.gl = gl + r0; a.sf = (float)grad_scale;
+    a.G = G; a.ldg = L.ldt; a.GT = GT; a.ldgt = P;
+    const bool vec = grad_aligned16(xp) && grad_aligned16(use) && ldx % 4 == 0 && ldu % 4 == 0;
+    e = vec ? launch_nt<128, 128, true, EPI_G>(a, s) : launch_nt<128, 128, false, EPI_G>(a, s);
+    if (e != hipSuccess) return e;
+    if (grad_bias) {
+      hipLaunchKernelGGL(grad_bias_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, GT, P, pn, r0, (int64_t)C, r0 == 0 ? 1 : 0,
+                         r0 + pn >= n ? 1 : 0, gb, grad_bias);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (grad_x) {
+      NtArgs b = {};
+      b.A = G; b.lda = L.ldt; b.M = pn; b.B = wt; b.ldb = L.ldt; b.N = E; b.K = C;
+      b.nMt = (pn + 63) / 64; b.nNt = (E + 63) / 64;
+      b.coef = coef + r0; b.x = xp; b.ldx = ldx; b.out = grad_x + r0 * ldgx; b.ldo = ldgx;
+      e = launch_nt<64, 64, true, EPI_X>(b, s);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(grad_transpose_kernel, dim3((unsigned)((pn + 63) / 64), (unsigned)((E + 63) / 64)), dim3(256), 0, s, xp, ldx,
+                       (int64_t)pn, (int64_t)E, XT, P);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    NtArgs c = {};
+    c.A = GT; c.lda = P; c.M = C; c.B = XT; c.ldb = P; c.N = E; c.K = pn;
+    c.nMt = (C + 127) / 128; c.nNt = (E + 127) / 128;
+    c.out = grad_rows; c.ldo = ldc; c.first = r0 == 0 ? 1 : 0;
+    e = launch_nt<128, 128, true, EPI_ACC>(c, s);
+    if (e != hipSuccess) return e;
+  }
+  if (angular) {
+    hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, rows, ldc, E, (int64_t)C,
+                       reinterpret_cast<const double*>(w + L.q), grad_rows);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace xv

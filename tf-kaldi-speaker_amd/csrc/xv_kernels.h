@@ -344,6 +344,23 @@ hipError_t launch_loss_tiles(const float* x, int64_t ldx, int n, int E, const in
                              const float* bias, const float* target, float* loss, float* lse, int32_t* top1, void* ws,
                              hipStream_t s);
 
+// loss and gradients of the classifier heads (csrc/loss_grad.hip).  ws as sized by loss_grad_workspace_bytes (least != 0: the
+// smallest legal size, a panel of 32 rows).  _forward_rows normalises the raw rows into ws and evaluates the targets there; the
+// first word of ws is the label flag of launch_loss_rows, to be read back before _rest is launched.
+int64_t loss_grad_workspace_bytes(int64_t n, int64_t C, int E, int least);
+hipError_t launch_loss_grad_forward_rows(const float* x, int64_t ldx, int64_t n, int E, const int32_t* labels, const float* rows,
+                                         int64_t ldc, int64_t C, const float* bias, int head, int m, double margin, double fa,
+                                         void* ws, hipStream_t s);
+hipError_t launch_loss_grad_rest(const float* x, int64_t ldx, int n, int E, const int32_t* labels, const float* rows, int64_t ldc,
+                                 int C, const float* bias, int head, int m, double margin, double fa, double grad_scale,
+                                 float* loss, float* target, float* lse, int32_t* top1, float* grad_x, int64_t ldgx,
+                                 float* grad_rows, float* grad_bias, void* ws, int64_t ws_bytes, hipStream_t s);
+
+// one optimizer step on one float32 tensor (csrc/opt_step.hip); ws holds opt_workspace_bytes(count) bytes when clip_norm > 0
+int64_t opt_workspace_bytes(int64_t count);
+hipError_t launch_opt_step(int kind, int nesterov, float* w, const float* g, float* slot0, float* slot1, int64_t count, double lr,
+                           double l2, double clip_norm, double momentum, int64_t step, void* ws, hipStream_t s);
+
 // back-end training statistics (csrc/backend.hip): G = sum_r w_r (x_r - c)(x_r - c)^T in double (c, w may be null), both
 // triangles of g [d, d]; ws holds gram_f64_workspace_bytes(n, d) bytes; rows fp32, or double in the _rows64 form
 int64_t gram_f64_workspace_bytes(int64_t n, int d);

@@ -5,9 +5,11 @@ tf.losses.sparse_softmax_cross_entropy.  Per row: the loss, the target logit aft
 class (the argmax of the logits before the margin, model/trainer.py:1097); the [n, C] logit matrix is never written.
 
 The annealing weight lambda = max(lambda_min, lambda_base (1 + gamma step)^-power) (loss.py:173-176) is evaluated here in
-double and reaches the kernel as fa = 1 / (1 + lambda).  Gradients, the auxiliary losses (`aux_loss_func`), the triplet and
-end-to-end losses are not implemented.  Arrays go in as numpy or as float32 device tensors, like scoring.py.  No CPU path:
-without a HIP device classifier_loss and ClassifierHead raise RuntimeError; head_config and valid_params are pure host code."""
+double and reaches the kernel as fa = 1 / (1 + lambda).  ClassifierHead.loss_and_grad adds the gradients with respect to x, the
+kernel and the bias (csrc/loss_grad.hip, xv_loss_classifier_grad); gradients through the encoder, the auxiliary losses
+(`aux_loss_func`), the triplet and end-to-end losses are not implemented.  Arrays go in as numpy or as float32 device tensors,
+like scoring.py.  No CPU path: without a HIP device classifier_loss and ClassifierHead raise RuntimeError; head_config and
+valid_params are pure host code."""
 import collections
 import copy
 import ctypes as C
@@ -26,6 +28,7 @@ _PREFIX = {"asoftmax": "asoftmax", "additive_margin_softmax": "amsoftmax", "addi
 _OTHER_LOSSES = ("ge2e", "semihard_triplet_loss", "angular_triplet_loss", "e2e_valid_loss", "generalized_angular_triplet_loss")
 
 LossResult = collections.namedtuple("LossResult", "loss target_logit lse top1 mean")
+GradResult = collections.namedtuple("GradResult", "loss target_logit lse top1 mean grad_x grad_kernel grad_bias")
 
 
 def _dict(params):
@@ -99,9 +102,20 @@ def _f32(x, device, torch):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to("cuda:%d" % device)
 
 
+def _labels_dev(labels, n, dev, torch):
+    if isinstance(labels, torch.Tensor):
+        ld = labels.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+    else:
+        ld = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).to(dev)
+    if ld.shape[0] != n:
+        raise ValueError("labels: %d labels for %d rows" % (ld.shape[0], n))
+    return ld
+
+
 class ClassifierHead(object):
     """`softmax/output/kernel` [E, C] (and bias [C]) prepared once on the device: class rows [C, E], column-normalised for the
-    angular heads, raw for softmax.  loss(x, labels) then runs any number of batches against them."""
+    angular heads, raw for softmax.  loss(x, labels) then runs any number of batches against them.  `raw_rows` gives the rows
+    without the normalisation: loss_and_grad differentiates with respect to them."""
 
     def __init__(self, kernel, bias=None, params=None, device=0):
         func = _dict(params).get("loss_func")
@@ -128,6 +142,31 @@ class ClassifierHead(object):
                                                    int(func != "softmax"), _p(self.classes), self._ldc, C.c_void_p(stream)))
             self.bias = None if bias is None else _f32(bias, self.device, torch)
         self._ws = None
+        self._gws = None
+        self._raw_rows = None
+        self._kernel_src = None if func == "softmax" else kernel        # a reference, no copy: the raw rows are made on first need
+
+    @property
+    def raw_rows(self):
+        """The class rows [C, ldc] WITHOUT the normalisation: what loss_and_grad differentiates with respect to.  For softmax
+        these are `classes` themselves (no second tensor); for the angular heads they are made from the kernel on first use, so
+        a head that only validates allocates nothing more than before.  A caller that updates them in place (HeadTrainer) leaves
+        `classes` of an angular head, and with it loss(), at the old kernel."""
+        if self._raw_rows is None:
+            if self.loss_func == "softmax":
+                self._raw_rows = self.classes
+            else:
+                torch = _need_device()
+                lib = _lib.load()
+                with torch.cuda.device(self.device):
+                    kd = _f32(self._kernel_src, self.device, torch)
+                    rows = torch.zeros((self.num_classes, self._ldc), dtype=torch.float32, device=kd.device)
+                    stream = torch.cuda.current_stream(self.device).cuda_stream
+                    _lib.check(lib.xv_loss_prepare_classes(self.device, _p(kd), self.num_classes, self.embed_dim, self.num_classes, 0,
+                                                           _p(rows), self._ldc, C.c_void_p(stream)))
+                    torch.cuda.current_stream(self.device).synchronize()      # kd may be a temporary
+                self._raw_rows, self._kernel_src = rows, None
+        return self._raw_rows
 
     def loss(self, x, labels, global_step=0, validation=False, as_tensor=False):
         """x [n, E], labels [n] -> LossResult(loss [n], target_logit [n], lse [n], top1 [n], mean).  A label outside
@@ -162,6 +201,58 @@ class ClassifierHead(object):
             loss = loss.cpu().numpy()
             return LossResult(loss, target.cpu().numpy(), lse.cpu().numpy(), top1.cpu().numpy(),
                               float(loss.astype(np.float64).mean()) if n else float("nan"))
+
+    def _grad_device(self, x, labels, global_step, grad_scale, need_grad_x, grad_rows=None, grad_bias=None):
+        """One xv_loss_classifier_grad against self.raw_rows -> device tensors (out [3, n], top1 [n], grad_x [n, E] or None,
+        grad_rows [C, ldc], grad_bias [C] or None).  grad_rows / grad_bias may be given (they are overwritten)."""
+        _, head, margin, fa = head_config(self.params, global_step, False)
+        torch = _need_device()
+        lib = _lib.load()
+        if len(tuple(x.shape)) != 2 or int(x.shape[1]) != self.embed_dim:
+            raise ValueError("x: expected [n, %d], got shape %s" % (self.embed_dim, tuple(x.shape)))
+        n = int(x.shape[0])
+        with torch.cuda.device(self.device):
+            xd = _f32(x, self.device, torch)
+            ld = _labels_dev(labels, n, xd.device, torch)
+            out = torch.empty((3, max(n, 1)), dtype=torch.float32, device=xd.device)
+            top1 = torch.empty((max(n, 1),), dtype=torch.int32, device=xd.device)
+            gx = torch.empty((max(n, 1), self.embed_dim), dtype=torch.float32, device=xd.device) if need_grad_x else None
+            if grad_rows is None:
+                grad_rows = torch.zeros((self.num_classes, self._ldc), dtype=torch.float32, device=xd.device)     # zeros: the padding
+            if grad_bias is None and self.bias is not None:
+                grad_bias = torch.empty((self.num_classes,), dtype=torch.float32, device=xd.device)
+            if n == 0:                              # nothing to launch: the gradient of an empty sum
+                grad_rows.zero_()
+                if grad_bias is not None:
+                    grad_bias.zero_()
+                return out[:, :0], top1[:0], None if gx is None else gx[:0], grad_rows, grad_bias
+            need = int(lib.xv_loss_grad_workspace(n, self.num_classes, self.embed_dim))
+            if self._gws is None or self._gws.numel() < need:
+                self._gws = torch.empty(need, dtype=torch.uint8, device=xd.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            scale = 1.0 / n if grad_scale is None else float(grad_scale)
+            _lib.check(lib.xv_loss_classifier_grad(self.device, _p(xd), self.embed_dim, n, self.embed_dim, _p(ld), _p(self.raw_rows),
+                                                   self._ldc, self.num_classes, None if self.bias is None else _p(self.bias), head,
+                                                   margin, fa, scale, _p(out[0]), _p(out[1]), _p(out[2]), _p(top1),
+                                                   None if gx is None else _p(gx), self.embed_dim, _p(grad_rows),
+                                                   None if grad_bias is None else _p(grad_bias), _p(self._gws), self._gws.numel(),
+                                                   C.c_void_p(stream)))
+        return out[:, :n], top1[:n], None if gx is None else gx[:n], grad_rows, grad_bias
+
+    def loss_and_grad(self, x, labels, global_step=0, grad_scale=None, need_grad_x=True, as_tensor=False):
+        """x [n, E], labels [n] -> GradResult(loss, target_logit, lse, top1 [n], mean, grad_x [n, E] or None, grad_kernel [E, C],
+        grad_bias [C] or None): the training loss of the head (training margins, annealed at `global_step`) and the gradients of
+        grad_scale * sum_i loss_i (default 1 / n, the mean) with respect to x, `softmax/output/kernel` and the bias, as TensorFlow
+        differentiates model/loss.py (the rule: include/xvec_hip.h, xv_loss_classifier_grad).  The per-row values are the bits
+        loss() gives with the same margins."""
+        out, top1, gx, grows, gbias = self._grad_device(x, labels, global_step, grad_scale, need_grad_x)
+        n = int(out.shape[1])
+        gk = grows[:, :self.embed_dim].t()
+        mean = float(out[0].double().mean()) if n else float("nan")
+        if as_tensor:
+            return GradResult(out[0], out[1], out[2], top1, mean, gx, gk.contiguous(), gbias)
+        host = lambda t: None if t is None else t.cpu().numpy()                         # noqa: E731
+        return GradResult(host(out[0]), host(out[1]), host(out[2]), host(top1), mean, host(gx), host(gk.contiguous()), host(gbias))
 
 
 def classifier_loss(x, labels, kernel, bias=None, params=None, global_step=0, validation=False, device=0, as_tensor=False):
