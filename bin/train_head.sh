@@ -8,6 +8,7 @@ config=
 seed=
 precision=
 keep_head=false
+segment_layers=false
 
 if [ -f path.sh ]; then . ./path.sh; fi
 if [ -f parse_options.sh ] || command -v parse_options.sh >/dev/null 2>&1; then
@@ -31,6 +32,7 @@ if [ $# != 6 ]; then
   echo "  --seed <N>               # default: params.seed or 0"
   echo "  --precision <f32|bf16x3|f16x3|f16f6>"
   echo "  --keep-head <false>      # start from the checkpoint's own softmax kernel when its shape fits"
+  echo "  --segment-layers <false> # also train the two dense layers behind the pooling node (run the head alone first)"
   echo ""
   exit 100
 fi
@@ -41,6 +43,7 @@ if [ -n "$config" ]; then opts="$opts --config $config"; fi
 if [ -n "$seed" ]; then opts="$opts --seed $seed"; fi
 if [ -n "$precision" ]; then opts="$opts --precision $precision"; fi
 if $keep_head; then opts="$opts --keep-head"; fi
+if $segment_layers; then opts="$opts --segment-layers"; fi
 
 here=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export PYTHONPATH=$here:$PYTHONPATH

@@ -711,6 +711,52 @@ int xv_opt_step(int device, int kind, int use_nesterov, float* w_dev, const floa
                 int64_t count, double learning_rate, double l2, double clip_norm, double momentum, int64_t step, void* ws_dev,
                 int64_t ws_bytes, void* stream);
 
+/* ---- one segment-level layer with its CURRENT weights, forward and backward (csrc/seg_grad.hip): what training the two dense
+ * layers behind the frozen `pooling` node together with the classifier head needs (egs/voxceleb/v1/nnet/lib/finetune.py:6-7,
+ * the noupdate_var_list route of model/trainer.py:309-320, 501-527).  A layer is dense + batch norm + activation
+ * (model/tdnn.py:137-179): x_dev [n, in_dim] with leading dimension ldx; w_dev [out_dim, ldw] holds the ROWS of the weights, the
+ * transpose of the TensorFlow `kernel` [in_dim, out_dim]; bias_dev [out_dim]; optionally gamma, beta, moving_mean and
+ * moving_variance [out_dim] (all four or none: XV_ERR_INVALID otherwise), eps = 1e-3; act one of XV_SEG_ACT_*.
+ * Batch norm runs in INFERENCE mode: moving_mean and moving_variance are constants, gamma and beta are trained.  The
+ * reference feeds is_training = True and normalises with batch statistics; here the layers are trained on exactly the function
+ * extraction and validation evaluate, and every row's result is independent of the batch around it: **parity unpinned**.
+ * The rule (K = in_dim, N = out_dim; i rows, j output columns, k input columns):
+ *   forward   z_ij = sum_k x_ik w_jk + b_j;  r_j = 1 / sqrt(mv_j + eps);  h_ij = gamma_j r_j (z_ij - mm_j) + beta_j (h = z
+ *             without batch norm);  y_ij = act(h_ij): h, max(h, 0), or h > 0 ? h : 0.2 h (TensorFlow's leaky-ReLU slope).
+ *             Writes z_dev [n, ldz], which the backward pass reads, and y_dev [n, ldy].
+ *             Rounding order, every step float32: the products of z are exact fp32 on v_mfma_f32_32x32x2_f32, one fmaf chain
+ *             over k ascending from 0 whose order is a function of K alone, then + b_j;  r_j = float(1 / sqrt(double(mv_j) +
+ *             1e-3));  s_j = gamma_j * r_j;  d = z - mm_j;  h = fma(s_j, d, beta_j);  leaky ReLU multiplies by float(0.2).
+ *   backward  given gy [n, ldgy], x, z and the parameters:  a_ij = gy_ij act'(h_ij), act' = [h > 0] for ReLU, 1 where h > 0 and
+ *             0.2 elsewhere for leaky ReLU (zero belongs to the lower branch, as TensorFlow differentiates both), 1 for none;
+ *             h is recomputed from z by the very instructions of the forward pass, so the mask agrees with the y written.
+ *             gbeta_j = sum_i a_ij;  ggamma_j = sum_i a_ij r_j (z_ij - mm_j);  gz_ij = a_ij gamma_j r_j (gz = a without batch
+ *             norm);  gbias_j = sum_i gz_ij;  gw_jk = sum_i gz_ij x_ik, rows layout [out_dim, ldw], the columns beyond in_dim
+ *             left alone;  gx_ik = sum_j gz_ij w_jk [n, ldgx], or gx_dev = NULL to skip that product (the first trained layer
+ *             never needs it).  ggamma_dev and gbeta_dev are written with batch norm only (and required then).
+ * Properties (tests/test_gpu_seg_grad.py): no floating-point atomics; the column sums gbeta, ggamma and gbias run in double in a
+ * fixed order by row index and are rounded once; the sum over the rows in gw is one fmaf chain in ascending row index whatever
+ * the panel size; every output is bit-identical on every repeat, for every legal ws_bytes and whatever the workspace and the
+ * outputs held before; row i of z, y and gx depends on row i and the parameters only.  The per-element error bound is derived
+ * in the header of csrc/seg_grad.hip.  Both calls are stream-ordered and never wait.  n = 0 is legal: XV_OK, nothing touched.
+ * 1 <= in_dim <= 16384, 1 <= out_dim <= 4096, n <= 2^24: XV_ERR_UNSUPPORTED beyond.  A leading dimension below its width, an
+ * unknown activation, a missing pointer or some but not all of the four batch-norm pointers: XV_ERR_INVALID.
+ * Workspace: xv_seg_forward needs none.  xv_seg_backward takes any 16-byte aligned ws_bytes >= xv_seg_workspace_min(n, in_dim,
+ * out_dim) (XV_ERR_WORKSPACE below it): 1536 N for the lane sums + 4 K round4(N) for the transposed weights, each rounded up to
+ * 256, + a panel of P rows of 4 (round4(N) + N + K) bytes each, P = 64.  xv_seg_workspace is the size at which P reaches
+ * min(round64(n), 1024) and nothing more is used.  Both are 0 for n = 0. */
+enum { XV_SEG_ACT_NONE = 0, XV_SEG_ACT_RELU = 1, XV_SEG_ACT_LRELU = 2 };
+int64_t xv_seg_workspace(int64_t n, int in_dim, int out_dim);
+int64_t xv_seg_workspace_min(int64_t n, int in_dim, int out_dim);
+int xv_seg_forward(int device, const float* x_dev, int64_t ldx, int64_t n, int in_dim, const float* w_dev, int64_t ldw, int out_dim,
+                   const float* bias_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev, const float* var_dev,
+                   int act, float* z_dev, int64_t ldz, float* y_dev, int64_t ldy, void* stream);
+int xv_seg_backward(int device, const float* gy_dev, int64_t ldgy, const float* x_dev, int64_t ldx, const float* z_dev, int64_t ldz,
+                    int64_t n, int in_dim, const float* w_dev, int64_t ldw, int out_dim, const float* gamma_dev,
+                    const float* beta_dev, const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx,
+                    float* gw_dev, float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes,
+                    void* stream);
+
 /* ---- metric-learning loss heads on the GPU (csrc/metric_loss.hip): what validation needs for a checkpoint trained with
  * `semihard_triplet_loss` (model/loss.py:387-527) or `angular_triplet_loss` (:530-663; validated with `e2e_valid_loss`,
  * :666-734, model/trainer.py:424-427).  Pinned to the reference's float64 numpy twins (model/test_utils.py:21-86, 118-154,

@@ -27,6 +27,7 @@ XV_POOL_SELF_ATTENTION = 1
 XV_ACT_RELU, XV_ACT_LRELU, XV_ACT_PRELU = 0, 1, 2
 XV_LOSS_SOFTMAX, XV_LOSS_ASOFTMAX, XV_LOSS_AMSOFTMAX, XV_LOSS_ARCSOFTMAX = 0, 1, 2, 3
 XV_OPT_SGD, XV_OPT_MOMENTUM, XV_OPT_ADAM = 0, 1, 2
+XV_SEG_ACT_NONE, XV_SEG_ACT_RELU, XV_SEG_ACT_LRELU = 0, 1, 2
 XV_METRIC_SEMIHARD, XV_METRIC_ANGULAR_ALL, XV_METRIC_ANGULAR_HARD, XV_METRIC_GE2E_SOFTMAX, XV_METRIC_GE2E_CONTRASTIVE = 0, 1, 2, 3, 4
 XV_LOGREG_MAX_SYSTEMS = 8
 XV_LOGREG_MAX_THRESHOLDS = 8
@@ -44,6 +45,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_vbx_workspace", "xv_vbx",
            "xv_loss_prepare_classes", "xv_loss_workspace", "xv_loss_classifier",
            "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_loss_classifier_grad", "xv_opt_workspace", "xv_opt_step",
+           "xv_seg_workspace", "xv_seg_workspace_min", "xv_seg_forward", "xv_seg_backward",
            "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
            "xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse",
@@ -216,6 +218,13 @@ def load():
     lib.xv_opt_workspace.argtypes = [i64]
     lib.xv_opt_workspace.restype = i64
     lib.xv_opt_step.argtypes = [i32, i32, i32, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i64, vp, i64, vp]
+    lib.xv_seg_workspace.argtypes = [i64, i32, i32]
+    lib.xv_seg_workspace.restype = i64
+    lib.xv_seg_workspace_min.argtypes = [i64, i32, i32]
+    lib.xv_seg_workspace_min.restype = i64
+    lib.xv_seg_forward.argtypes = [i32, vp, i64, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64, vp]
+    lib.xv_seg_backward.argtypes = [i32, vp, i64, vp, i64, vp, i64, i64, i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp,
+                                    vp, i64, vp]
     lib.xv_metric_loss_workspace.argtypes = [i64, vp, i32, i32]
     lib.xv_metric_loss_workspace.restype = i64
     lib.xv_metric_loss_slot_bytes.argtypes = [i32, i32, i32]
@@ -257,7 +266,7 @@ def load():
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
                      "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_opt_workspace", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_vbx_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
+                     "xv_loss_workspace", "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_opt_workspace", "xv_seg_workspace", "xv_seg_workspace_min", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_vbx_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

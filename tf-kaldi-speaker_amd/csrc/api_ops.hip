@@ -460,6 +460,68 @@ int xv_opt_step(int device, int kind, int use_nesterov, float* w_dev, const floa
   });
 }
 
+int64_t xv_seg_workspace(int64_t n, int in_dim, int out_dim) { return seg_workspace_bytes(n, in_dim, out_dim, 0); }
+
+int64_t xv_seg_workspace_min(int64_t n, int in_dim, int out_dim) { return seg_workspace_bytes(n, in_dim, out_dim, 1); }
+
+namespace {
+
+// the checks the two calls of a segment-level layer share; `op` names the caller in the message
+int seg_check(const char* op, int64_t n, int in_dim, int out_dim, int64_t ldx, int64_t ldw, const void* gamma, const void* beta,
+              const void* mm, const void* mv, int act) {
+  if (in_dim < 1 || in_dim > 16384 || out_dim < 1 || out_dim > 4096 || n > (1 << 24))
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= in_dim <= 16384, 1 <= out_dim <= 4096, n <= 2^24, got %d, %d, %lld", op, in_dim,
+                out_dim, (long long)n);
+  if (n < 0 || ldx < in_dim || ldw < in_dim) return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
+  const int given = (gamma != nullptr) + (beta != nullptr) + (mm != nullptr) + (mv != nullptr);
+  if (given != 0 && given != 4)
+    return fail(nullptr, XV_ERR_INVALID, "%s: batch norm needs gamma, beta, moving_mean and moving_variance, or none of them", op);
+  if (act < XV_SEG_ACT_NONE || act > XV_SEG_ACT_LRELU) return fail(nullptr, XV_ERR_INVALID, "%s: unknown activation %d", op, act);
+  return XV_OK;
+}
+
+}  // namespace
+
+// dense + inference-mode batch norm + activation with the current weights (include/xvec_hip.h)
+int xv_seg_forward(int device, const float* x_dev, int64_t ldx, int64_t n, int in_dim, const float* w_dev, int64_t ldw, int out_dim,
+                   const float* bias_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev, const float* var_dev,
+                   int act, float* z_dev, int64_t ldz, float* y_dev, int64_t ldy, void* stream) {
+  if (!x_dev || !w_dev || !bias_dev || !z_dev || !y_dev) return fail(nullptr, XV_ERR_INVALID, "xv_seg_forward: null pointer");
+  const int rc = seg_check("xv_seg_forward", n, in_dim, out_dim, ldx, ldw, gamma_dev, beta_dev, mean_dev, var_dev, act);
+  if (rc != XV_OK) return rc;
+  if (ldz < out_dim || ldy < out_dim) return fail(nullptr, XV_ERR_INVALID, "xv_seg_forward: bad dimensions");
+  if (n == 0) return XV_OK;
+  return with_device(device, "xv_seg_forward", [&] {
+    return launch_seg_forward(x_dev, ldx, (int)n, in_dim, w_dev, ldw, out_dim, bias_dev, gamma_dev, beta_dev, mean_dev, var_dev, act,
+                              z_dev, ldz, y_dev, ldy, to_stream(stream));
+  });
+}
+
+int xv_seg_backward(int device, const float* gy_dev, int64_t ldgy, const float* x_dev, int64_t ldx, const float* z_dev, int64_t ldz,
+                    int64_t n, int in_dim, const float* w_dev, int64_t ldw, int out_dim, const float* gamma_dev,
+                    const float* beta_dev, const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx,
+                    float* gw_dev, float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes,
+                    void* stream) {
+  if (!gy_dev || !x_dev || !z_dev || !w_dev || !gw_dev || !gbias_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: null pointer");
+  const int rc = seg_check("xv_seg_backward", n, in_dim, out_dim, ldx, ldw, gamma_dev, beta_dev, mean_dev, var_dev, act);
+  if (rc != XV_OK) return rc;
+  if (gamma_dev && (!ggamma_dev || !gbeta_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: batch norm needs ggamma_dev and gbeta_dev");
+  if (ldgy < out_dim || ldz < out_dim || (gx_dev && ldgx < in_dim)) return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: bad dimensions");
+  if (n == 0) return XV_OK;
+  if (!ws_dev || ws_bytes < seg_workspace_bytes(n, in_dim, out_dim, 1))
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_seg_backward: workspace of %lld bytes, at least %lld needed",
+                (long long)(ws_dev ? ws_bytes : 0), (long long)seg_workspace_bytes(n, in_dim, out_dim, 1));
+  if ((reinterpret_cast<uintptr_t>(ws_dev) & 15) != 0)
+    return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: the workspace must be 16-byte aligned");
+  return with_device(device, "xv_seg_backward", [&] {
+    return launch_seg_backward(gy_dev, ldgy, x_dev, ldx, z_dev, ldz, (int)n, in_dim, w_dev, ldw, out_dim, gamma_dev, beta_dev, mean_dev,
+                               var_dev, act, gx_dev, ldgx, gw_dev, gbias_dev, ggamma_dev, gbeta_dev, ws_dev, ws_bytes,
+                               to_stream(stream));
+  });
+}
+
 int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
                     int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
                     int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,

@@ -15,7 +15,8 @@
 //    does not come from the fp32 tile.
 //  * per PANEL of P rows (P a multiple of 32, at most 1024, as many as the workspace holds), in ascending row order:
 //      - nt_gemm_kernel<EPI_G>: z = x . w^T again with v_mfma_f32_32x32x2_f32 (the tile skeleton of loss_tile_kernel: K in
-//        steps of 32, [row][32 + 4] floats in LDS, register-staged double buffering, zero-filled edges), G_ic = s expf(z_ic -
+//        steps of 32, [row][32 + 4] floats in LDS, register-staged double buffering, zero-filled edges; it lives in
+//        csrc/nt_gemm.h, which csrc/seg_grad.hip shares), G_ic = s expf(z_ic -
 //        lse_i), the entry at column l_i swapped for G_il by the tile that owns it; written as G [P, C] and G^T [C, P];
 //      - grad_bias: one wave per class, lane l adds the rows i = l (mod 64) of the batch in ascending order to a double that
 //        lives in the workspace between the panels; a fixed butterfly over the 64 lanes after the last panel;
@@ -49,23 +50,18 @@
 //   grad_bias_c:    sum_i |dG_ic| + u |grad_bias_c|                                 (double sum, rounded once)
 //   grad_rows_ce:   softmax: a_ce + u |grad_rows_ce|.  Angular: with D = sum_e |w^_ce| a_ce the error of w^_c . gw_c,
 //                   (a_ce + |w^_ce| D) / sqrt(q_c) + 2 u |grad_rows_ce|; below the floor a_ce / 1e-6 + u |grad_rows_ce|.
-#include <mutex>
-
-#include "xv_kernels.h"
+#include "nt_gemm.h"
 
 namespace xv {
 
-typedef float gf32x16 __attribute__((ext_vector_type(16)));
-typedef float gf32x4 __attribute__((ext_vector_type(4)));
+using ntg::gf32x16;
+using ntg::gf32x4;
+using ntg::up;
 
 namespace {
 
-constexpr int GBK = 32;
-constexpr int GLDT = GBK + 4;                 // padded LDS row (floats), as csrc/loss.hip
 constexpr int kMaxPanel = 1024;
 constexpr int kPanelStep = 32;                // a panel is a whole number of K steps of the gw product
-
-__host__ __device__ constexpr int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 __device__ __forceinline__ double gwave_sum_f64(double v) {
 #pragma unroll
@@ -95,19 +91,6 @@ __global__ __launch_bounds__(256) void grad_normalize_kernel(const float* __rest
   const double inv = 1.0 / sqrt(s > 1e-12 ? s : 1e-12);
   for (int e = k; e < E; e += 4) what[c * ldh + e] = (float)((double)r[e] * inv);
   if (k == 0) q[c] = s;
-}
-
-// dst [cols, ldd] = src [rows, lds]^T, 64 x 64 through LDS; grid (ceil(rows / 64), ceil(cols / 64)), cols <= 2048 here
-__global__ __launch_bounds__(256) void grad_transpose_kernel(const float* __restrict__ src, int64_t lds, int64_t rows, int64_t cols,
-                                                             float* __restrict__ dst, int64_t ldd) {
-  __shared__ float tile[64][65];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t r0 = (int64_t)blockIdx.x * 64, c0 = (int64_t)blockIdx.y * 64;      // rows (classes) on x: no 65535 limit
-  for (int rl = wave; rl < 64; rl += 4)
-    tile[rl][lane] = (r0 + rl < rows && c0 + lane < cols) ? src[(r0 + rl) * lds + c0 + lane] : 0.f;
-  __syncthreads();
-  for (int cl = wave; cl < 64; cl += 4)
-    if (c0 + cl < cols && r0 + lane < rows) dst[(c0 + cl) * ldd + r0 + lane] = tile[lane][cl];
 }
 
 // ---------------------------------------------------------------------------------------------- the label's entry
@@ -218,54 +201,15 @@ struct NtArgs {
 
 template <int BM, int BN, bool VEC, int EPI>
 __global__ __launch_bounds__(256, 2) void nt_gemm_kernel(NtArgs p) {
-  constexpr int TA = BM * GLDT, TB = BN * GLDT;      // floats per operand tile
   constexpr int WM = BM / 2, WN = BN / 2;            // per wave
   constexpr int AI = WM / 32, BI = WN / 32;
-  constexpr int RA = BM / 32, RB = BN / 32;          // staging passes
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                    // [2][BM][GLDT]
-  float* Bs = smem + 2 * TA;           // [2][BN][GLDT]
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int r32 = lane & 31, h = lane >> 5;
-  const int c4 = tid & 7, lr = tid >> 3;
-  const int nk = (p.K + GBK - 1) / GBK;
   const int mt = (int)(blockIdx.x % (unsigned)p.nMt), nt = (int)(blockIdx.x / (unsigned)p.nMt);
   const int m0 = mt * BM, n0 = nt * BN;
-
-  gf32x4 ra[RA], rb[RB];
-  auto load_rows = [&](const float* base, int64_t ld, int row0, int nrows, int kt, gf32x4* r, int passes) {
-    const int k = kt * GBK + c4 * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (i >= passes) break;
-      const int row = row0 + lr + 32 * i;
-      gf32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (row < nrows && k < p.K) {
-        const float* src = base + (int64_t)row * ld + k;
-        if (VEC && k + 4 <= p.K) {
-          v = *reinterpret_cast<const gf32x4*>(src);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (k + e < p.K) v[e] = src[e];
-        }
-      }
-      r[i] = v;
-    }
-  };
-  auto load_tiles = [&](int kt) {
-    load_rows(p.A, p.lda, m0, p.M, kt, ra, RA);
-    load_rows(p.B, p.ldb, n0, p.N, kt, rb, RB);
-  };
-  auto store_tiles = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < RA; ++i) *reinterpret_cast<gf32x4*>(As + buf * TA + (lr + 32 * i) * GLDT + c4 * 4) = ra[i];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) *reinterpret_cast<gf32x4*>(Bs + buf * TB + (lr + 32 * i) * GLDT + c4 * 4) = rb[i];
-  };
 
   // accumulator layout: element e of lane (r32, h) is D[8 * (e / 4) + 4 * h + e % 4][r32] (A row, B row)
   gf32x16 acc[AI][BI];
@@ -284,36 +228,7 @@ __global__ __launch_bounds__(256, 2) void nt_gemm_kernel(NtArgs p) {
         acc[ai][bi][e] = v;
       }
 
-  load_tiles(0);
-  store_tiles(0);
-  __syncthreads();
-
-  const float* a_base = As + (wm * WM + r32) * GLDT + 4 * h;
-  const float* b_base = Bs + (wn * WN + r32) * GLDT + 4 * h;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load_tiles(kt + 1);
-    const float* ap = a_base + cur * TA;
-    const float* bp = b_base + cur * TB;
-#pragma unroll
-    for (int q = 0; q < GBK / 8; ++q) {
-      // lane (r, h) feeds k = 8 q + 4 h + j of both operands: the order of the chain is a function of k alone
-      gf32x4 a[AI], b[BI];
-#pragma unroll
-      for (int ai = 0; ai < AI; ++ai) a[ai] = *reinterpret_cast<const gf32x4*>(ap + ai * 32 * GLDT + q * 8);
-#pragma unroll
-      for (int bi = 0; bi < BI; ++bi) b[bi] = *reinterpret_cast<const gf32x4*>(bp + bi * 32 * GLDT + q * 8);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int ai = 0; ai < AI; ++ai)
-#pragma unroll
-          for (int bi = 0; bi < BI; ++bi)
-            acc[ai][bi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ai][j], b[bi][j], acc[ai][bi], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store_tiles(cur ^ 1);
-    __syncthreads();
-  }
+  ntg::nt_mainloop<BM, BN, VEC>(p.A, p.lda, p.M, p.B, p.ldb, p.N, p.K, m0, n0, acc, smem);      // csrc/nt_gemm.h
 
 #pragma unroll
   for (int bi = 0; bi < BI; ++bi) {
@@ -396,26 +311,12 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const float* __restric
 
 template <int BM, int BN, bool VEC, int EPI>
 hipError_t launch_nt(const NtArgs& a, hipStream_t s) {
-  constexpr size_t smem = (size_t)2 * (BM + BN) * GLDT * sizeof(float);
   static std::mutex mu;            // per-device attribute; any thread may make the first launch on a device
   static bool set_for[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!set_for[dev & 63]) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nt_gemm_kernel<BM, BN, VEC, EPI>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return e;
-      set_for[dev & 63] = true;
-    }
-  }
-  const int64_t tiles = (int64_t)a.nMt * a.nNt;
-  hipLaunchKernelGGL((nt_gemm_kernel<BM, BN, VEC, EPI>), dim3((unsigned)tiles), dim3(256), smem, s, a);
-  return hipGetLastError();
+  return ntg::nt_launch(nt_gemm_kernel<BM, BN, VEC, EPI>, ntg::nt_smem_bytes<BM, BN>(), mu, set_for, (int64_t)a.nMt * a.nNt, a, s);
 }
 
-bool grad_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool grad_aligned16(const void* p) { return ntg::aligned16(p); }
 
 struct GradLayout {
   int64_t ldh, ldt;                 // row of w^ [C, ldh] and of (w^)^T [E, ldt], floats
@@ -504,9 +405,7 @@ hipError_t launch_loss_grad_rest(const float* x, int64_t ldx, int n, int E, cons
                      hp, lse, gl, coef);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (grad_x) {
-    hipLaunchKernelGGL(grad_transpose_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)((E + 63) / 64)), dim3(256), 0, s, use, ldu,
-                       (int64_t)C, (int64_t)E, wt, L.ldt);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = ntg::nt_transpose(use, ldu, (int64_t)C, (int64_t)E, wt, L.ldt, s)) != hipSuccess) return e;
   }
 
   int64_t P = (ws_bytes - L.panel) / L.per_row / kPanelStep * kPanelStep;
@@ -538,9 +437,7 @@ hipError_t launch_loss_grad_rest(const float* x, int64_t ldx, int n, int E, cons
       e = launch_nt<64, 64, true, EPI_X>(b, s);
       if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(grad_transpose_kernel, dim3((unsigned)((pn + 63) / 64), (unsigned)((E + 63) / 64)), dim3(256), 0, s, xp, ldx,
-                       (int64_t)pn, (int64_t)E, XT, P);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = ntg::nt_transpose(xp, ldx, (int64_t)pn, (int64_t)E, XT, P, s)) != hipSuccess) return e;
     NtArgs c = {};
     c.A = GT; c.lda = P; c.M = C; c.B = XT; c.ldb = P; c.N = E; c.K = pn;
     c.nMt = (C + 127) / 128; c.nNt = (E + 127) / 128;

@@ -361,6 +361,17 @@ int64_t opt_workspace_bytes(int64_t count);
 hipError_t launch_opt_step(int kind, int nesterov, float* w, const float* g, float* slot0, float* slot1, int64_t count, double lr,
                            double l2, double clip_norm, double momentum, int64_t step, void* ws, hipStream_t s);
 
+// one segment-level layer, dense + inference-mode batch norm + activation, forward and backward (csrc/seg_grad.hip).  gamma, beta,
+// mm, mv: all four or all null.  ws as sized by seg_workspace_bytes (least != 0: the smallest legal size, a panel of 64 rows).
+int64_t seg_workspace_bytes(int64_t n, int K, int N, int least);
+hipError_t launch_seg_forward(const float* x, int64_t ldx, int n, int K, const float* w, int64_t ldw, int N, const float* bias,
+                              const float* gamma, const float* beta, const float* mm, const float* mv, int act, float* z, int64_t ldz,
+                              float* y, int64_t ldy, hipStream_t s);
+hipError_t launch_seg_backward(const float* gy, int64_t ldgy, const float* x, int64_t ldx, const float* z, int64_t ldz, int n, int K,
+                               const float* w, int64_t ldw, int N, const float* gamma, const float* beta, const float* mm,
+                               const float* mv, int act, float* gx, int64_t ldgx, float* gw, float* gbias, float* ggamma,
+                               float* gbeta, void* ws, int64_t ws_bytes, hipStream_t s);
+
 // back-end training statistics (csrc/backend.hip): G = sum_r w_r (x_r - c)(x_r - c)^T in double (c, w may be null), both
 // triangles of g [d, d]; ws holds gram_f64_workspace_bytes(n, d) bytes; rows fp32, or double in the _rows64 form
 int64_t gram_f64_workspace_bytes(int64_t n, int d);

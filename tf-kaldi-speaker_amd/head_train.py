@@ -229,13 +229,16 @@ def read_learning_rate_file(path):
 
 # ---------------------------------------------------------------------------------------------- the driver
 def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_model_dir, weights=None, seed=0, keep_head=False,
-               precision=None, log=None):
+               precision=None, log=None, segment_layers=False):
     """Train the head of `trainer` (a Trainer built for "predict" with the pre-trained weights loaded; its params name the head,
     the optimizer and the schedule) on train_dir and write <out_model_dir>/nnet after every epoch of num_steps_per_epoch steps:
     model-<step>.npz (model_io.save_model: every variable of `weights` unchanged plus the new softmax/output/kernel and bias),
     config.json, feature_dim, and one line each in valid_loss (`epoch loss eer`) and learning_rate (`epoch rate`) in
     finetune.py's formats (:174-183).  Validation is the existing Trainer.valid + scoring.pairwise_eer on the new directory.
     `weights` defaults to the trainer's checkpoint; keep_head starts from its softmax kernel when the shape fits.
+    With segment_layers the frozen forward stops at the `pooling` node and the two segment-level layers behind it are trained
+    with the head (tail_train.TailTrainer): the checkpoints then also hold their new kernels, biases, gamma and beta; every
+    other variable, their moving statistics included, is unchanged.
     -> [(epoch, step, valid loss, eer, learning rate)]."""
     from . import scoring
     from . import valid as valid_mod
@@ -257,16 +260,24 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     rule = LearningRateRule(params, learning_rate if schedule is None else schedule[0], schedule)
 
     endpoint = trainer.embeddings
-    trainer.embeddings = "output"                                        # the caller's trainer gets its endpoint back on exit
+    trainer.embeddings = "pooling" if segment_layers else "output"       # the caller's trainer gets its endpoint back on exit
     try:
-        probe = trainer.predict(np.zeros((1, int(p["min_segment_len"]), trainer.dim), dtype=np.float32))
-        embed_dim = int(probe.shape[-1])
+        if segment_layers:
+            from . import tail_train
+            tail_train.check_supported(params)
+            embed_dim = int(weights[tail_train.segment_variables(params)[1].kernel].shape[1])
+        else:
+            probe = trainer.predict(np.zeros((1, int(p["min_segment_len"]), trainer.dim), dtype=np.float32))
+            embed_dim = int(probe.shape[-1])
         kernel = bias = None
         if keep_head:
             k = weights.get(model_io.SOFTMAX_KERNEL)
             if k is not None and tuple(k.shape) == (embed_dim, num_classes):
                 kernel, bias = np.asarray(k), weights.get(model_io.SOFTMAX_BIAS)
-        head = HeadTrainer(params, embed_dim, num_classes, trainer._device_index, seed, kernel, bias)
+        if segment_layers:
+            head = tail_train.TailTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
+        else:
+            head = HeadTrainer(params, embed_dim, num_classes, trainer._device_index, seed, kernel, bias)
         frozen = {k: v for k, v in weights.items() if k not in (model_io.SOFTMAX_KERNEL, model_io.SOFTMAX_BIAS)}
         nnet = os.path.join(out_model_dir, "nnet")
         history, step = [], 0
@@ -279,9 +290,12 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
                 if log is not None:
                     log("epoch %d step %d loss %f acc %f" % (epoch, step, res.loss, res.accuracy))
             out = dict(frozen)
-            out[model_io.SOFTMAX_KERNEL] = head.kernel()
-            if head.bias() is not None:
-                out[model_io.SOFTMAX_BIAS] = head.bias()
+            if segment_layers:
+                out.update(head.variables())
+            else:
+                out[model_io.SOFTMAX_KERNEL] = head.kernel()
+                if head.bias() is not None:
+                    out[model_io.SOFTMAX_BIAS] = head.bias()
             model_io.save_model(out_model_dir, p, trainer.dim, out, step=step)
             judge = Trainer(params, out_model_dir, trainer.dim, single_cpu=True, device=trainer._device_index,
                             precision=precision or trainer._precision)

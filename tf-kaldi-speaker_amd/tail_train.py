@@ -1,0 +1,263 @@
+"""Train the two segment-level layers together with the classifier head: the first part of stage two of every fine-tune
+(egs/voxceleb/v1/nnet/lib/finetune.py:6-7: "... and then update the entire network"), as the reference's `noupdate_var_list`
+does it when the frame-level layers are named as fixed (model/trainer.py:309-320, 501-527).
+
+Everything up to the `pooling` node stays as the checkpoint has it, so no frame-level backward pass is needed.  A step is: the
+frozen forward to `pooling` (Trainer.predict, by the caller), xv_seg_forward through tdnn6 and tdnn7 (tdnn12 / tdnn13 for the
+extended TDNN) with their CURRENT weights, one xv_loss_classifier_grad for the loss and grad_x, xv_seg_backward through both
+layers (csrc/seg_grad.hip), one xv_opt_step per tensor.  Trained: the two dense kernels and biases, gamma and beta of their
+batch norms, the head.  NOT trained: the moving statistics.  Batch norm runs in INFERENCE mode (the reference feeds
+is_training=True and normalises with batch statistics): the layers are trained on exactly the function extraction and
+validation evaluate, as head_train.py does: **parity unpinned**.
+
+`weight_l2_regularizer` goes on the two dense kernels only (tf.layers.dense(kernel_regularizer=...), model/tdnn.py:137-160),
+the head keeps the rule of head_train.optimizer_config, the clip is per tensor (model/trainer.py:529-533), Adam's step count
+is shared.  segment_variables, check_supported and l2_assignment are pure host code; the rest needs a HIP device."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from . import head_train
+from . import losses
+from . import model_io
+
+StepResult = head_train.StepResult
+SegSpec = collections.namedtuple("SegSpec", "kernel bias bn act")       # variable names (bn: the scope or None), XV_SEG_ACT_*
+
+_SCOPES = {"tdnn": ("tdnn", 6, 7), "extended_tdnn": ("etdnn", 12, 13), "resnet_18": ("resnet_18", 6, 7)}
+_BN = ("gamma", "beta", "moving_mean", "moving_variance")
+
+
+def _dict(params):
+    return params if isinstance(params, dict) else params.dict
+
+
+def check_supported(params):
+    """NotImplementedError for what the segment-level backward pass does not cover, then for everything HeadTrainer refuses."""
+    d = _dict(params)
+    if d.get("network_relu_type") == "prelu":
+        raise NotImplementedError("network_relu_type prelu: the trainable alpha of the segment layers is not implemented")
+    if d.get("feature_norm"):
+        raise NotImplementedError("feature_norm: the gradient of the l2 scaling behind the last layer is not implemented")
+    if d.get("network_type", "tdnn") not in _SCOPES:
+        raise NotImplementedError("Not implement %s network" % d.get("network_type"))
+    losses.head_config(params, 0, False)
+    if d.get("sample_with_prob"):
+        raise NotImplementedError("sample_with_prob is not implemented")
+    head_train.optimizer_config(params)
+
+
+def segment_variables(params):
+    """-> (SegSpec of the first layer, SegSpec of the second) under the scope names csrc/api_graph.hip uses."""
+    d = _dict(params)
+    scope, a, b = _SCOPES[d.get("network_type", "tdnn")]
+    act = _lib.XV_SEG_ACT_LRELU if d.get("network_relu_type") == "lrelu" else _lib.XV_SEG_ACT_RELU
+    name = lambda i, what: "%s/tdnn%d_%s" % (scope, i, what)                # noqa: E731
+    first = SegSpec(name(a, "dense/kernel"), name(a, "dense/bias"), name(a, "bn"), act)
+    second = SegSpec(name(b, "dense/kernel"), name(b, "dense/bias"), None if d.get("last_layer_no_bn") else name(b, "bn"),
+                     _lib.XV_SEG_ACT_NONE if d.get("last_layer_linear") else act)
+    return first, second
+
+
+def trained_names(params):
+    """The TensorFlow names of every variable TailTrainer updates, the head's last."""
+    out = []
+    for spec in segment_variables(params):
+        out += [spec.kernel, spec.bias]
+        if spec.bn:
+            out += [spec.bn + "/gamma", spec.bn + "/beta"]
+    out.append(model_io.SOFTMAX_KERNEL)
+    if _dict(params).get("loss_func") == "softmax":
+        out.append(model_io.SOFTMAX_BIAS)
+    return out
+
+
+def l2_assignment(params):
+    """name -> the l2 factor of its update: weight_l2_regularizer on the two dense kernels, optimizer_config's rule on the
+    head's kernel, 0 on every bias, gamma and beta."""
+    d = _dict(params)
+    reg = float(d.get("weight_l2_regularizer", 0.0))
+    out = dict.fromkeys(trained_names(params), 0.0)
+    for spec in segment_variables(params):
+        out[spec.kernel] = reg
+    out[model_io.SOFTMAX_KERNEL] = head_train.optimizer_config(params)[3]
+    return out
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class SegLayer(object):
+    """One layer's parameters, gradients and optimizer slots on the device.  w holds the rows [N, ldw] of the weights (the
+    transpose of the TensorFlow kernel [K, N]; ldw = K rounded up to 4, the padding stays zero)."""
+
+    def __init__(self, kernel, bias, bn, act, device=0, num_slots=0):
+        torch = losses._need_device()
+        kernel = np.asarray(kernel, dtype=np.float32)
+        if kernel.ndim != 2 or tuple(np.shape(bias)) != (kernel.shape[1],):
+            raise ValueError("kernel [K, N] and bias [N] expected, got %s and %s" % (kernel.shape, np.shape(bias)))
+        self.in_dim, self.out_dim = int(kernel.shape[0]), int(kernel.shape[1])
+        self.ldw = (self.in_dim + 3) // 4 * 4
+        self.act, self.device = int(act), int(device)
+        self._torch, self._lib = torch, _lib.load()
+        dev = "cuda:%d" % self.device
+        with torch.cuda.device(self.device):
+            self.w = torch.zeros((self.out_dim, self.ldw), dtype=torch.float32, device=dev)
+            self.w[:, :self.in_dim] = torch.from_numpy(np.ascontiguousarray(kernel.T)).to(dev)
+            self.b = losses._f32(bias, self.device, torch)
+            self.bn = None
+            if bn is not None:
+                if any(tuple(np.shape(v)) != (self.out_dim,) for v in bn):
+                    raise ValueError("batch norm: four vectors of %d elements expected" % self.out_dim)
+                self.bn = [losses._f32(v, self.device, torch) for v in bn]         # gamma, beta, moving_mean, moving_variance
+            self.gw = torch.zeros_like(self.w)                                     # the padding columns stay zero
+            self.gb = torch.zeros_like(self.b)
+            self.ggamma = None if self.bn is None else torch.zeros_like(self.b)
+            self.gbeta = None if self.bn is None else torch.zeros_like(self.b)
+            self.slots = {name: [torch.zeros_like(t) for _ in range(num_slots)] for name, t, _ in self.trained()}
+        self._x = self._z = self._ws = None
+
+    def trained(self):
+        """[(name, parameter, gradient)] in the order the optimizer takes them."""
+        out = [("kernel", self.w, self.gw), ("bias", self.b, self.gb)]
+        if self.bn is not None:
+            out += [("gamma", self.bn[0], self.ggamma), ("beta", self.bn[1], self.gbeta)]
+        return out
+
+    def forward(self, x):
+        """x [n, K] on the device, float32 contiguous -> y [n, N]; x and z are kept for backward()."""
+        torch = self._torch
+        n = int(x.shape[0])
+        if tuple(x.shape) != (n, self.in_dim):
+            raise ValueError("x: expected [n, %d], got shape %s" % (self.in_dim, tuple(x.shape)))
+        with torch.cuda.device(self.device):
+            z = torch.empty((max(n, 1), self.out_dim), dtype=torch.float32, device=x.device)
+            y = torch.empty((max(n, 1), self.out_dim), dtype=torch.float32, device=x.device)
+            bn = self.bn or [None] * 4
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._lib.xv_seg_forward(self.device, _p(x), self.in_dim, n, self.in_dim, _p(self.w), self.ldw, self.out_dim,
+                                                _p(self.b), _p(bn[0]), _p(bn[1]), _p(bn[2]), _p(bn[3]), self.act, _p(z), self.out_dim,
+                                                _p(y), self.out_dim, C.c_void_p(stream)))
+        self._x, self._z = x, z
+        return y[:n]
+
+    def backward(self, gy, want_gx):
+        """gy [n, N] on the device -> gx [n, K] or None; the gradients of the parameters go to gw, gb, ggamma, gbeta."""
+        torch = self._torch
+        x, z = self._x, self._z
+        n = int(x.shape[0])
+        if tuple(gy.shape) != (n, self.out_dim) or not gy.is_contiguous():
+            raise ValueError("gy: expected a contiguous [%d, %d], got shape %s" % (n, self.out_dim, tuple(gy.shape)))
+        with torch.cuda.device(self.device):
+            if n == 0:                                  # the gradient of an empty sum
+                for _, _, g in self.trained():
+                    g.zero_()
+                return torch.zeros((0, self.in_dim), dtype=torch.float32, device=x.device) if want_gx else None
+            gx = torch.empty((n, self.in_dim), dtype=torch.float32, device=x.device) if want_gx else None
+            need = int(self._lib.xv_seg_workspace(n, self.in_dim, self.out_dim))
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+            bn = self.bn or [None] * 4
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._lib.xv_seg_backward(self.device, _p(gy), self.out_dim, _p(x), self.in_dim, _p(z), self.out_dim, n,
+                                                 self.in_dim, _p(self.w), self.ldw, self.out_dim, _p(bn[0]), _p(bn[1]), _p(bn[2]),
+                                                 _p(bn[3]), self.act, _p(gx), self.in_dim, _p(self.gw), _p(self.gb), _p(self.ggamma),
+                                                 _p(self.gbeta), _p(self._ws), self._ws.numel(), C.c_void_p(stream)))
+        return gx
+
+    def kernel(self):
+        """The TensorFlow kernel [K, N], float32 numpy."""
+        return np.ascontiguousarray(self.w[:, :self.in_dim].t().cpu().numpy())
+
+
+class TailTrainer(object):
+    """The two segment-level layers, built from the checkpoint's variables, and a head_train.HeadTrainer behind them."""
+
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None):
+        check_supported(params)
+        self.params = params
+        self.specs = segment_variables(params)
+        kind = head_train.optimizer_config(params)[0]
+        num_slots = {_lib.XV_OPT_SGD: 0, _lib.XV_OPT_MOMENTUM: 1, _lib.XV_OPT_ADAM: 2}[kind]
+        self.layers = []
+        for spec in self.specs:
+            missing = [k for k in (spec.kernel, spec.bias) + (tuple(spec.bn + "/" + s for s in _BN) if spec.bn else ()) if k not in weights]
+            if missing:
+                raise KeyError("the checkpoint lacks %s" % ", ".join(missing))
+            bn = [weights[spec.bn + "/" + s] for s in _BN] if spec.bn else None
+            self.layers.append(SegLayer(weights[spec.kernel], weights[spec.bias], bn, spec.act, device, num_slots))
+        if self.layers[1].in_dim != self.layers[0].out_dim:
+            raise ValueError("%s has %d rows, %s %d columns" % (self.specs[1].kernel, self.layers[1].in_dim, self.specs[0].kernel,
+                                                                  self.layers[0].out_dim))
+        self.pool_dim, self.embed_dim = self.layers[0].in_dim, self.layers[1].out_dim
+        self.head = head_train.HeadTrainer(params, self.embed_dim, num_classes, device, seed, kernel, bias)
+        self.l2 = l2_assignment(params)
+        torch = losses._need_device()
+        self._torch, self._lib, self.device = torch, _lib.load(), int(device)
+        largest = max([layer.w.numel() for layer in self.layers] + [self.head.head.raw_rows.numel()])
+        with torch.cuda.device(self.device):
+            self._ws = torch.empty(max(int(self._lib.xv_opt_workspace(largest)), 8), dtype=torch.uint8, device=self.layers[0].w.device)
+        self.num_steps = 0                                                   # adam's t, shared by every tensor
+
+    def tensors(self):
+        """[(TensorFlow name, parameter, gradient, slots)] of everything trained, in the order of trained_names()."""
+        out = []
+        for spec, layer in zip(self.specs, self.layers):
+            names = {"kernel": spec.kernel, "bias": spec.bias, "gamma": (spec.bn or "") + "/gamma", "beta": (spec.bn or "") + "/beta"}
+            out += [(names[k], w, g, layer.slots[k]) for k, w, g in layer.trained()]
+        h = self.head
+        out.append((model_io.SOFTMAX_KERNEL, h.head.raw_rows, h._grad_rows, h._row_slots))
+        if h.head.bias is not None:
+            out.append((model_io.SOFTMAX_BIAS, h.head.bias, h._grad_bias, h._bias_slots))
+        return out
+
+    def forward(self, pooled):
+        """pooled [n, pool_dim] -> the `output` endpoint [n, embed_dim] on the device, with the current weights."""
+        torch = self._torch
+        with torch.cuda.device(self.device):
+            x = losses._f32(pooled, self.device, torch)
+            return self.layers[1].forward(self.layers[0].forward(x))
+
+    def _apply(self, w, g, slots, lr, l2):
+        h = self.head
+        stream = self._torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.xv_opt_step(self.device, h.kind, int(h.nesterov), _p(w), _p(g), _p(slots[0]) if slots else None,
+                                         _p(slots[1]) if len(slots) > 1 else None, w.numel(), float(lr), l2, h.clip_norm, h.momentum,
+                                         self.num_steps, _p(self._ws), self._ws.numel(), C.c_void_p(stream)))
+
+    def step(self, pooled, labels, learning_rate, global_step=0):
+        """One training step on a batch of pooled rows [n, pool_dim]: forward through both layers, the head's mean loss at
+        `global_step` and its gradients, backward through both layers, then per tensor l2 (kernels only), the clip and the
+        update -> StepResult(mean loss, top-1 accuracy), both of the parameters BEFORE the update."""
+        torch = self._torch
+        h = self.head
+        with torch.cuda.device(self.device):
+            y = self.forward(pooled)
+            out, top1, gx, _, _ = h.head._grad_device(y, labels, global_step, None, True, h._grad_rows, h._grad_bias)
+            n = int(out.shape[1])
+            g1 = self.layers[1].backward(gx, True)
+            self.layers[0].backward(g1, False)
+            self.num_steps += 1
+            h.num_steps = self.num_steps
+            for name, w, g, slots in self.tensors():
+                self._apply(w, g, slots, learning_rate, self.l2[name])
+            lab = losses._labels_dev(labels, n, out.device, torch)
+            return StepResult(float(out[0].double().mean()) if n else float("nan"),
+                              float((top1 == lab).double().mean()) if n else float("nan"))
+
+    def variables(self):
+        """name -> float32 numpy of every trained variable under its TensorFlow name (kernels as [in, out])."""
+        out = collections.OrderedDict()
+        for spec, layer in zip(self.specs, self.layers):
+            out[spec.kernel] = layer.kernel()
+            out[spec.bias] = layer.b.cpu().numpy().copy()
+            if spec.bn:
+                out[spec.bn + "/gamma"] = layer.bn[0].cpu().numpy().copy()
+                out[spec.bn + "/beta"] = layer.bn[1].cpu().numpy().copy()
+        out[model_io.SOFTMAX_KERNEL] = self.head.kernel()
+        if self.head.bias() is not None:
+            out[model_io.SOFTMAX_BIAS] = self.head.bias()
+        return out

@@ -2,13 +2,15 @@
 egs/voxceleb/v1/nnet/lib/finetune.py, with its positional arguments.
 
     python -m tf_kaldi_speaker_amd.train_head [--gpu N] [--checkpoint C] [--config new.json] [--seed S] [--precision P]
-                                              [--keep-head] pretrain_model train_dir train_spklist valid_dir valid_spklist
+                                              [--keep-head] [--segment-layers] pretrain_model train_dir train_spklist valid_dir valid_spklist
                                               finetune_model
 
 `--config` names the configuration of the NEW model (loss_func, margins, optimizer, learning-rate schedule, batch shape); without
 it the pre-trained model's config.json is used.  The network hyper-parameters must be those of the pre-trained model: its
 variables are copied unchanged.  `--checkpoint` is a checkpoint name under <pretrain_model>/nnet (default: the one its
-`checkpoint` file names).  One line per epoch: `epoch <e> step <s> loss <valid loss> eer <eer> lr <rate>`."""
+`checkpoint` file names).  `--segment-layers` trains the two dense layers behind the pooling node together with the head
+(tail_train.py); the intended flow is the head first, then `--segment-layers --keep-head` on the directory the first run wrote.
+One line per epoch: `epoch <e> step <s> loss <valid loss> eer <eer> lr <rate>`."""
 import argparse
 import os
 import sys
@@ -26,6 +28,8 @@ def build_parser():
     parser.add_argument("--seed", type=int, default=-1, help="Seed of the initialisation and of the batches (default: params.seed or 0).")
     parser.add_argument("--precision", type=str, default="", help="f32 | bf16x3 | f16x3 | f16f6 of the frozen forward (default: the trainer's)")
     parser.add_argument("--keep-head", action="store_true", help="Start from the checkpoint's own softmax kernel when its shape fits.")
+    parser.add_argument("--segment-layers", action="store_true", help="Train the two segment-level layers behind the pooling node "
+                        "together with the head (everything in front of it stays frozen).")
     parser.add_argument("--verbose", action="store_true", help="One line per step.")
     parser.add_argument("pretrain_model", type=str, help="The pre-trained model directory.")
     parser.add_argument("train_dir", type=str, help="The data directory of the training set.")
@@ -59,7 +63,8 @@ def main(argv=None):
     seed = args.seed if args.seed >= 0 else int(params.dict.get("seed", 0))
     history = head_train.train_head(trainer, args.train_dir, args.train_spklist, args.valid_dir, args.valid_spklist,
                                     args.finetune_model, weights=weights, seed=seed, keep_head=args.keep_head,
-                                    precision=args.precision or None, log=print if args.verbose else None)
+                                    precision=args.precision or None, log=print if args.verbose else None,
+                                    segment_layers=args.segment_layers)
     for epoch, step, loss, eer, lr in history:
         print("epoch %d step %d loss %f eer %f lr %.8f" % (epoch, step, loss, eer, lr))
     trainer.close()
