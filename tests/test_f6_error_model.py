@@ -3,7 +3,8 @@
 * its fp6 quantiser against the rules of csrc/xv_f6.h: in half-up mode bit for bit against e2m3_code / e8m0_of (mirrored below; the
   weight packer host_e2m3 is the same code): E8M0 scale 2^ceil(log2(amax / 7.5)), saturation at 7.5, subnormal steps of 1/8,
   magnitudes rounded half up; the activations go through the hardware converters, which round to nearest even (rne=True, hand-picked
-  ties only: the converters themselves are not run here);
+  ties only; the converters themselves run in tests/test_gpu_layer_isolated.py, whose exact selection cases compare their codes
+  with this rule bit for bit on the GPU);
 * the hazard the library's demotion exists for: a compensated per-channel spread inside the 32-channel blocks (same function) pushes
   the two-unit reader beyond 1e-4, and the same model with that reader on f16x3 is back at the benign figure."""
 import importlib.util
