@@ -92,7 +92,7 @@ def extra_write(addrs, width):
 
 
 def epilogue(s):
-    """extra cycles per 64-row pass of the 128 x 32 wave-tile epilogues (csrc/xv_epilogue.h, xv_f6.h) under row swizzle s:
+    """extra cycles per 64-row pass of the 128 x 32 wave-tile epilogues (csrc/xv_epilogue_n32.h, xv_f6.h) under row swizzle s:
     (pooling form: stage_f32 + two row4 sweeps, fp6 form: stage + row-per-lane read / write + read-back, split-blocked form)"""
     stage = sum(extra_write([(fl * 16 + (l & 15)) * 128 + (((4 * ct + (l >> 4)) ^ s(fl * 16 + (l & 15))) << 4) for l in range(64)], 16)
                 for fl in range(4) for ct in range(2))

@@ -1,6 +1,6 @@
 """Float64 reference of one frame-layer GEMM on the GPU's own fp32 input, with a per-element error bar.
 
-Restates the library's rules (csrc/api_weights.hip upload_layer / act_exponent / host_quant32, csrc/xv_epilogue.h split2t and the
+Restates the library's rules (csrc/api_weights.hip upload_layer / act_exponent / host_quant32, csrc/xv_common.h split2t, csrc/xv_epilogue_n32.h the
 folded epilogue, csrc/xv_f6.h): how a layer's weights and its fp32 input are split into the operands its kernel multiplies, and
 which float scale / shift its epilogue applies.  The operands are exactly representable, so
 

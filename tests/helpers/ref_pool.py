@@ -1,6 +1,6 @@
 """Pooling on its own: float64 references, per-element error bars, and fp32 emulations of the pooling kernels (numpy only).
 
-The pooling kernels (csrc/pool.hip, the pooling epilogues of csrc/xv_epilogue.h) are checked against a float64 pooling of the
+The pooling kernels (csrc/pool.hip, the pooling epilogues of csrc/xv_epilogue.h and csrc/xv_epilogue_n32.h) are checked against a float64 pooling of the
 frames the GPU itself produced, so the GEMM's error is not in the budget and every bar below follows from fp32 summation
 alone.  u = 2^-24 (unit round-off), n = frames of the utterance, k = 64-row slots it touches in the packed batch.
 

@@ -192,7 +192,7 @@ def _subnormal_slot_case():
 
 def test_a_slot_of_subnormal_weights_stays_finite():
     """The reciprocal of a subnormal slot weight overflows: `s1 * (1 / s0)` as the value epilogue first had it gives an
-    infinite slot mean and a NaN variance.  The epilogue takes the reciprocal of normal sums only (csrc/xv_epilogue.h); the
+    infinite slot mean and a NaN variance.  The epilogue takes the reciprocal of normal sums only (csrc/xv_epilogue_n32.h); the
     emulation of the earlier form is kept as a mutant and must fail."""
     x, w = _subnormal_slot_case()
     mean, std = rp.emu_att_heads(lambda xc, wh: rp.emu_att_fused(xc, wh, 0), x, w, True)

@@ -210,7 +210,7 @@ int upload_layer(xv_handle* h, Layer& L) {
     XV_HIP(h, L.wt.alloc(elems * sizeof(float)));
     XV_HIP(h, hipMemcpy(L.wt.p, wt.data(), elems * sizeof(float), hipMemcpyHostToDevice));
   } else {
-    // split-blocked: row n, block kb: [32 x hi | 32 x lo] for k = 32*kb .. 32*kb+31 (xv_epilogue.h)
+    // split-blocked: row n, block kb: [32 x hi | 32 x lo] for k = 32*kb .. 32*kb+31 (xv_common.h)
     const bool f16 = h->desc.precision == XV_PREC_F16X3 || h->desc.precision == XV_PREC_F16F6;
     float wscale = 1.f;
     if (f16) {

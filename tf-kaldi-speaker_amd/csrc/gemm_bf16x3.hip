@@ -8,7 +8,7 @@
 // the exact v_mfma_f32_32x32x2_f32 path at a relative error of ~5e-6 per layer (measured in
 // tests/test_gpu_parity.py against the float64 oracle; the bar is 1e-4).
 //
-// Both operands arrive in the split-blocked format of xv_epilogue.h: per row, 128-byte blocks
+// Both operands arrive in the split-blocked format of xv_common.h: per row, 128-byte blocks
 // [32 x bf16 hi | 32 x bf16 lo].  One block is one K step of 32 for one row, so
 //   * every global access is a full 128-byte line (8 lanes x 16 bytes),
 //   * 16-byte chunk q of a block is exactly a lane's MFMA fragment: plane q>>2 (hi / lo), k chunk q&3 = lane>>4 of
@@ -88,7 +88,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // The activation fragment addresses use ONE swizzle and ONE row offset per lane ((32*mi + r) >> 1 == r >> 1 mod 8)
 // plus ds_read immediates, which frees the registers for the third weight buffer at 3 workgroups / CU.
 // EPI selects the epilogue at compile time: 0 = activations (fp32 / SB / residual / fused statistics pooling),
-// 1 / 2 = the attention forms of xv_epilogue.h (score partials of the last key layer / weighted moments of the value).
+// 1 / 2 = the attention forms of xv_epilogue_n32.h (score partials of the last key layer / weighted moments of the value).
 // A separate instantiation keeps the default kernel's code -- and its register allocation -- untouched.
 // F16 selects the split format of both operands (bf16 hi/lo or fp16 hi/lo: same bytes, same MFMA rate).
 
@@ -257,7 +257,7 @@ __device__ __forceinline__ void w14p2_tile(const GemmArgs& p, int m0, int n0, in
     }
     store_wave_tile_n32_f6(p, acc, m0, n0 + wave * 32, lane_e, wave, smem3);      // XV_PREC_F16F6 producer: the two-unit block format
   } else if constexpr (EPI != 0) store_wave_tile_n32_att<EPI>(p, acc, m0, n0 + wave * 32, lane_e, wave, smem3);
-  else store_wave_tile_n32<64, F16>(p, acc, m0, n0 + wave * 32, lane_e, wave, smem3);
+  else store_wave_tile_n32<F16>(p, acc, m0, n0 + wave * 32, lane_e, wave, smem3);
   XV_EPI_STAMP(p, 3);
 }
 
@@ -402,7 +402,7 @@ __device__ __forceinline__ void w1p3_tile(const GemmArgs& p, int m0, int n0, cha
   const int lane_e = end_k_loop(p, lane);
   if constexpr (EPI == 3) store_wave_tile_n32_f6(p, acc, m0, n0 + wave * 32, lane_e, wave, smem3);      // XV_PREC_F16F6 producer
   else if constexpr (EPI != 0) store_wave_tile_n32_att<EPI>(p, acc, m0, n0 + wave * 32, lane_e, wave, smem3);
-  else store_wave_tile_n32<64, F16>(p, acc, m0, n0 + wv * 32, lane_e, wave, smem3);      // wv: the block this wave computed (`narrow`)
+  else store_wave_tile_n32<F16>(p, acc, m0, n0 + wv * 32, lane_e, wave, smem3);      // wv: the block this wave computed (`narrow`)
   XV_EPI_STAMP(p, 3);
 }
 

@@ -7,7 +7,7 @@
 // instruction runs at four times the f16 rate: a product costs 1 + 2 x 1/4 MFMA units instead of the 3 of bf16x3 / f16x3
 // (tools/mfma_mix_bench.hip: 1.6x at the same tile).
 //
-// Activation block of one (row, 32 channels), 128 bytes like the split-blocked format of xv_epilogue.h:
+// Activation block of one (row, 32 channels), 128 bytes like the split-blocked format of xv_common.h:
 //   chunks 0-3  32 x f16 hi (unchanged: the main fragment read is the one of the f16x3 kernel)
 //   chunk 4 / 5 bytes 0-15 of the 32 x 6-bit codes of q6(hi) / q6(lo)
 //   chunk 6 / 7 bytes 16-23 of the codes of q6(hi) / q6(lo) | one dword {byte 0: E8M0 scale of q6(hi), byte 1: of q6(lo)} | 4 bytes pad

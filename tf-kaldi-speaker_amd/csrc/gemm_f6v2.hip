@@ -409,7 +409,7 @@ __device__ __forceinline__ void f6v2_tile(const GemmArgs& p, int m0, int n0, cha
     else store_wave_tile_n32_f6(q, acc, m0, n0 + wave * 32, lane_e, wave, smem);
   } else {
     if constexpr (OUT_F6) store_wave_tile_n32_f6(p, acc, m0, n0 + wave * 32, lane_e, wave, smem);
-    else store_wave_tile_n32<64, true>(p, acc, m0, n0 + wave * 32, lane_e, wave, smem);
+    else store_wave_tile_n32<true>(p, acc, m0, n0 + wave * 32, lane_e, wave, smem);
   }
 }
 

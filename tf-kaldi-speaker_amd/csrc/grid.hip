@@ -16,7 +16,7 @@
 // spent on border rows -- 1 / (F + 1) of the positions, 17 % in stage 4 -- nor, under resnet_time_stride, on the input
 // rows between two output frames.  The border of the output is then zeroed by grid_zero_border_kernel, which writes
 // the border positions only.
-#include "xv_epilogue.h"
+#include "xv_common.h"
 
 namespace xv {
 

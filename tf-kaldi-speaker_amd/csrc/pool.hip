@@ -1,7 +1,7 @@
 // HBM-bound kernels of the x-vector path: statistics pooling, attentive pooling, row maps,
 // l2 scaling and small elementwise stages.  All are wavefront(64)-shaped reductions:
 // coalesced 16-byte loads, DPP/shuffle reduction inside a wave, one LDS hop across waves.
-#include "xv_epilogue.h"
+#include "xv_common.h"
 
 namespace xv {
 
@@ -302,7 +302,7 @@ hipError_t launch_att_pool(const float* value, int64_t ldv, int dv, const float*
   return hipGetLastError();
 }
 
-// ---- fused attentive pooling: the three small kernels around the attention epilogue of the GEMM (xv_epilogue.h)
+// ---- fused attentive pooling: the three small kernels around the attention epilogue of the GEMM (xv_epilogue_n32.h)
 // scores[r, h] = scale * sum over the 32-channel blocks (ascending) of the partial dot products the key layer stored
 __global__ __launch_bounds__(256) void att_scores_reduce_kernel(const float* __restrict__ part, int64_t ld, int nblk, int H,
                                                                 int64_t rows, float scale, float* __restrict__ scores) {
@@ -418,7 +418,7 @@ __global__ void im2col_sb_kernel(const float* __restrict__ x, int64_t ldx, int c
       v[e] = kk < K ? x[(m + dr) * ldx + (kk - dr * cin)] : 0.f;
     }
     uint32_t hi, lo;
-    split2(v[0], v[1], hi, lo, f16);                 // hi/lo split in the format the GEMM consumes (xv_epilogue.h)
+    split2(v[0], v[1], hi, lo, f16);                 // hi/lo split in the format the GEMM consumes (xv_common.h)
     if (f16) ovf_report(ovf, fmaxf(fabsf(v[0]), fabsf(v[1])));      // a feature beyond the fp16 range
     mx = fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1])));
     char* blk = out + m * (int64_t)ldsb * 4 + (k >> 5) * 128 + (k & 31) * 2;
@@ -452,7 +452,7 @@ hipError_t launch_im2col_sb(const float* x, int64_t ldx, int cin, int w, int64_t
 // The cin_pad form of the first layer (one tap: a feature row becomes one SB row, zero padded to ldsb channels) and the per-utterance
 // lower-range guard of the fp16 formats in ONE pass over the features.  The workgroup knows its utterance; a lane takes 8 channels
 // of a row: 8-byte loads where the row stride and the pointer allow (a 30-dim row is only 8-byte aligned), the split of
-// xv_epilogue.h, then the hi and the lo halves as one 16-byte store each.  No division inside the loop.  Two grids:
+// xv_common.h, then the hi and the lo halves as one 16-byte store each.  No division inside the loop.  Two grids:
 //  * no utterance longer than kStageSingleRows: grid (1, utterance), 1024 threads.  The workgroup sees the whole utterance and
 //    decides by itself, as feat_utt_guard_kernel does: plain stores, nothing to combine.
 //  * else grid (chunks of kStageRows rows, utterance), 256 threads, so that a long utterance is spread over as many workgroups
@@ -501,7 +501,7 @@ __global__ __launch_bounds__(1024) void feat_stage_sb_kernel(const float* __rest
       uint32_t hi[4], lo[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        split2(v[2 * e], v[2 * e + 1], hi[e], lo[e], f16);          // hi/lo split in the format the GEMM consumes (xv_epilogue.h)
+        split2(v[2 * e], v[2 * e + 1], hi[e], lo[e], f16);          // hi/lo split in the format the GEMM consumes (xv_common.h)
         const float m2 = fmaxf(fabsf(v[2 * e]), fabsf(v[2 * e + 1]));
         bad |= !(m2 <= kF16Max);                                    // a feature beyond the fp16 range
         mx = fmaxf(mx, m2);

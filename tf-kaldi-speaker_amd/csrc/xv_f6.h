@@ -2,7 +2,7 @@
 // output in the activation block format of gemm_f16f6.hip (f16 hi | fp6 codes of hi and lo | their E8M0 scales, 128 bytes per
 // (row, 32 channels)).  Used by gemm_f16f6.hip and by the F6-output instantiation of the multi-tap f16 kernel (gemm_bf16x3.hip).
 #pragma once
-#include "xv_epilogue.h"
+#include "xv_epilogue_n32.h"
 
 namespace xv {
 
@@ -83,7 +83,8 @@ __device__ __forceinline__ void f6_block_of_row(char* rp, int sw, bool check, ui
 
 // Epilogue that writes the output in the activation block format above (the consumer is another two-unit layer): BN scale / shift +
 // activation as usual, the 64 x 32 fp32 values of a pass staged row-major in the wave's LDS scratch, then ONE ROW PER LANE
-// (the conversion of f6_block_of_row, written out here), and the usual row-contiguous 16-byte stores (row map applied) follow.
+// (the same conversion as f6_block_of_row, kept as this function's own copy: with the call the compiler loads the row map in front of
+// the conversion and the producers reach the register limit), and the usual row-contiguous 16-byte stores (row map applied) follow.
 __device__ __forceinline__ void store_wave_tile_n32_f6(const GemmArgs& p, const f32x4 (&acc)[8][2], int mbase, int nbase, int lane,
                                                        int wave, char* lds) {
   constexpr int ROWS = 64, NPASS = 2, FPP = 4;
@@ -107,7 +108,7 @@ __device__ __forceinline__ void store_wave_tile_n32_f6(const GemmArgs& p, const 
 #pragma unroll
     for (int it = 0; it < ROWS / 8; ++it) {
       const int m = mbase + ps * ROWS + it * 8 + rrow;
-      rmap[it] = m < p.M ? (p.rowmap ? p.rowmap[m] : m) : -1;
+      rmap[it] = rowmap_entry(p, m);
     }
 #pragma unroll
     for (int fl = 0; fl < FPP; ++fl)
@@ -120,7 +121,7 @@ __device__ __forceinline__ void store_wave_tile_n32_f6(const GemmArgs& p, const 
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = apply_act(fmaf(t[i], sc[ct][i], sh[ct][i]), p.act, al[i]);
         const int row = fl * 16 + c16;
-        *reinterpret_cast<f32x4*>(scratch + row * 128 + (((4 * ct + g4) ^ swz8(row)) << 4)) = v;
+        *reinterpret_cast<f32x4*>(n32_slot(scratch, row, 4 * ct + g4)) = v;
       }
     wave_lds_sync();
     {   // one row per lane
@@ -174,10 +175,9 @@ __device__ __forceinline__ void store_wave_tile_n32_f6(const GemmArgs& p, const 
 #pragma unroll 4
     for (int it = 0; it < ROWS / 8; ++it) {
       const int row = it * 8 + rrow;
-      f32x4 v = *reinterpret_cast<const f32x4*>(scratch + row * 128 + ((rchunk ^ swz8(row)) << 4));
-      int r = rmap[it];
-      const bool zero = r < -1;
-      r = zero ? -r - 2 : r;
+      f32x4 v = *reinterpret_cast<const f32x4*>(n32_slot(scratch, row, rchunk));
+      bool zero;
+      const int r = rowmap_decode(rmap[it], zero);
       if (zero) v = z;
       if (r >= 0 && blk_ok) {
         char* dst = reinterpret_cast<char*>(p.Ysb) + (int64_t)r * p.ldsb * 4 + (nbase >> 5) * 128 + rchunk * 16;
@@ -213,9 +213,7 @@ __device__ __forceinline__ void store_wave_tile_n32_res(const GemmArgs& p, const
   const int n = nbase + rchunk * 4;
   const bool nok = n < p.N, blk_ok = nbase < p.ldsb;
   auto row_of = [&](int m, bool& zero) -> int {
-    int r = m < p.M ? (p.rowmap ? p.rowmap[m] : m) : -1;
-    zero = r < -1;
-    return zero ? -r - 2 : r;
+    return rowmap_decode(rowmap_entry(p, m), zero);
   };
 #pragma unroll
   for (int ps = 0; ps < NPASS; ++ps) {
@@ -231,7 +229,7 @@ __device__ __forceinline__ void store_wave_tile_n32_res(const GemmArgs& p, const
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaf(t[i], sc[i], sh[i]);
         const int row = fl * 16 + c16;
-        *reinterpret_cast<f32x4*>(scratch + row * 128 + (((4 * ct + g4) ^ swz8(row)) << 4)) = v;
+        *reinterpret_cast<f32x4*>(n32_slot(scratch, row, 4 * ct + g4)) = v;
       }
     }
     wave_lds_sync();
@@ -241,7 +239,7 @@ __device__ __forceinline__ void store_wave_tile_n32_res(const GemmArgs& p, const
 #pragma unroll 2
       for (int it = 0; it < ROWS / 8; ++it) {
         const int row = it * 8 + rrow;
-        f32x4* slot = reinterpret_cast<f32x4*>(scratch + row * 128 + ((rchunk ^ swz8(row)) << 4));
+        f32x4* slot = reinterpret_cast<f32x4*>(n32_slot(scratch, row, rchunk));
         f32x4 v = *slot;
         bool zero;
         const int r = row_of(mbase + ps * ROWS + row, zero);
@@ -274,7 +272,7 @@ __device__ __forceinline__ void store_wave_tile_n32_res(const GemmArgs& p, const
 #pragma unroll 2
       for (int it = 0; it < ROWS / 8; ++it) {
         const int row = it * 8 + rrow;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(scratch + row * 128 + ((rchunk ^ swz8(row)) << 4));
+        const f32x4 v = *reinterpret_cast<const f32x4*>(n32_slot(scratch, row, rchunk));
         bool zero;
         const int r = row_of(mbase + ps * ROWS + row, zero);     // (a zero row was staged as zeros: the all-zero block)
         if (r >= 0 && blk_ok)

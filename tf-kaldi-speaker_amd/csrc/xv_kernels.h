@@ -46,7 +46,7 @@ struct GemmArgs {
   float* Y;               // fp32 output (may be nullptr when only the split planes are wanted)
   int64_t ldy;
   // bf16x3 path: activations consumed by a split GEMM are carried in the split-blocked (SB)
-  // format of xv_epilogue.h (per row: blocks of [32 x bf16 hi | 32 x bf16 lo], 128 bytes).
+  // format of xv_common.h (per row: blocks of [32 x bf16 hi | 32 x bf16 lo], 128 bytes).
   const void* Xsb;        // SB input (bf16x3 kernel), row stride ldsbx elements (x4 bytes)
   int64_t ldsbx;          // multiple of 32; == cin for convolutions
   void* Ysb;              // SB output or nullptr
@@ -410,7 +410,7 @@ hipError_t launch_att_scores(const float* key, int64_t ldk, int64_t rows, const 
 // softmax over time per (utterance, head), in place on scores [rows, H]; also writes the
 // [B, H, Lmax]-free packed layout weights_out[h * rows + r] when weights_out != nullptr.
 hipError_t launch_att_softmax(float* scores, int H, const int32_t* off0, int B, int ctx, hipStream_t s);
-// fused attention (csrc/xv_epilogue.h, attention epilogue of the bf16x3 GEMM):
+// fused attention (csrc/xv_epilogue_n32.h, attention epilogue of the bf16x3 GEMM):
 // scores[r, h] = scale * sum_blk part[(blk * H + h) * ld + r], blocks in ascending order (deterministic)
 hipError_t launch_att_scores_reduce(const float* part, int64_t ld, int nblk, int H, int64_t rows, float scale,
                                     float* scores, hipStream_t s);
