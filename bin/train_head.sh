@@ -9,6 +9,7 @@ seed=
 precision=
 keep_head=false
 segment_layers=false
+frame_layers=false
 
 if [ -f path.sh ]; then . ./path.sh; fi
 if [ -f parse_options.sh ] || command -v parse_options.sh >/dev/null 2>&1; then
@@ -33,6 +34,8 @@ if [ $# != 6 ]; then
   echo "  --precision <f32|bf16x3|f16x3|f16f6>"
   echo "  --keep-head <false>      # start from the checkpoint's own softmax kernel when its shape fits"
   echo "  --segment-layers <false> # also train the two dense layers behind the pooling node (run the head alone first)"
+  echo "  --frame-layers <false>   # also train the 1-tap frame layers in front of the pooling node; implies --segment-layers"
+  echo "                           # (run the head alone first, then --segment-layers, then this)"
   echo ""
   exit 100
 fi
@@ -44,6 +47,7 @@ if [ -n "$seed" ]; then opts="$opts --seed $seed"; fi
 if [ -n "$precision" ]; then opts="$opts --precision $precision"; fi
 if $keep_head; then opts="$opts --keep-head"; fi
 if $segment_layers; then opts="$opts --segment-layers"; fi
+if $frame_layers; then opts="$opts --frame-layers"; fi
 
 here=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export PYTHONPATH=$here:$PYTHONPATH

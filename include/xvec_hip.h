@@ -757,6 +757,41 @@ int xv_seg_backward(int device, const float* gy_dev, int64_t ldgy, const float* 
                     float* gw_dev, float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes,
                     void* stream);
 
+/* ---- statistics pooling of the caller's own packed rows, forward and backward (csrc/pool_grad.hip; model/pooling.py:27-52): the
+ * piece between the 1-tap frame layers (tdnn4 / tdnn5; tdnn8 .. tdnn10 of the extended TDNN), which on packed frames are
+ * xv_seg_forward / xv_seg_backward with one row per frame, and the segment-level layers, when both are trained behind the frozen
+ * tdnn3_relu / tdnn7_relu node (tf_kaldi_speaker_amd/frame_train.py).  The pooling inside xv_forward is fused into the last
+ * frozen GEMM and cannot be called on a tensor of the caller's.
+ * Layout: utterance b owns the rows offsets[b] .. offsets[b + 1]) of x_dev [*, ldx], C = channels columns; offsets_dev
+ *   [batch + 1] lives on the device, ascends, offsets[0] >= 0.  total_rows is a host value >= offsets[batch]; it sizes grids and
+ *   nothing else.  Rows outside [offsets[0], offsets[batch]) and columns >= C are never read or written.  pooled_dev
+ *   [batch, ldp] = [mean | std], 2 C wide; var_dev [batch, ldv] = the variance BEFORE the floor, C wide; gp_dev [batch, ldgp] =
+ *   the gradient with respect to pooled; gx_dev [*, ldgx] has the row numbering of x.
+ * Forward, per utterance of n frames and channel, every step rounded to float32 once:
+ *   m = S / float(n), S = sum_t x_t (a division, not a product with a rounded reciprocal);
+ *   v = Q / float(n), Q = sum_t d_t^2 with d_t = x_t - m about the COMPUTED mean, each term one fma (two sweeps, never
+ *   E[x^2] - m^2);  std = sqrtf(v <= 1e-12f ? 1e-12f : v).  n = 0: m = 0, v = 0, std = sqrtf(1e-12f).
+ *   Order of S and Q, a function of n alone: 16 partial sums, partial s taking the frames s, s + 16, s + 32, ... in ascending
+ *   order from 0, then a binary tree over the 16, neighbours first (k = 16 in the bars of tests/helpers/ref_pool.py).
+ * Backward:  live = v > 1e-12f, read from var_dev (the reference's floor mask is a constant to TensorFlow: a floored channel
+ *   passes no gradient from std);  a = gm / float(n);  b = live ? gs / (float(n) * std) : 0;  d = x_t - m;  gx_t = fma(b, d, a),
+ *   each operation rounded to float32 once; gm = gp[c], gs = gp[C + c].  That is gx = gm / n + gs (x - m) / (n std): the term of
+ *   d var / d mean multiplies sum_t (x_t - m) = 0 and is dropped.  Nothing is written for n = 0.
+ *   Per element |gx^ - gx| <= u (2 |a| + 4 |b d|)(1 + 2^-20) + 2^-149, u = 2^-24, against the float64 rule at the same float32
+ *   m, std, v and gp (derived in the header of csrc/pool_grad.hip).
+ * Properties (tests/test_gpu_pool_grad.py): no atomics; the outputs of an utterance are a pure function of its own rows and
+ *   gradient row: the same bits on every repeat, alone or in any batch, at any position and row alignment of the packed buffer,
+ *   for any total_rows, with 16-byte or 4-byte accesses, and whatever the outputs held before.  Both calls only enqueue work and
+ *   never wait.
+ * 1 <= channels <= 4096, total_rows <= 2^24 (and batch <= 2^24): XV_ERR_UNSUPPORTED beyond.  A leading dimension below its width
+ *   (ldx, ldv, ldgx < C; ldp, ldgp < 2 C), a missing pointer, a negative batch or total_rows: XV_ERR_INVALID before any launch.
+ *   batch = 0: XV_OK, nothing touched. */
+int xv_stat_pool_forward(int device, const float* x_dev, int64_t ldx, int channels, const int32_t* offsets_dev, int64_t batch,
+                         int64_t total_rows, float* pooled_dev, int64_t ldp, float* var_dev, int64_t ldv, void* stream);
+int xv_stat_pool_backward(int device, const float* gp_dev, int64_t ldgp, const float* x_dev, int64_t ldx, int channels,
+                          const int32_t* offsets_dev, int64_t batch, int64_t total_rows, const float* pooled_dev, int64_t ldp,
+                          const float* var_dev, int64_t ldv, float* gx_dev, int64_t ldgx, void* stream);
+
 /* ---- metric-learning loss heads on the GPU (csrc/metric_loss.hip): what validation needs for a checkpoint trained with
  * `semihard_triplet_loss` (model/loss.py:387-527) or `angular_triplet_loss` (:530-663; validated with `e2e_valid_loss`,
  * :666-734, model/trainer.py:424-427).  Pinned to the reference's float64 numpy twins (model/test_utils.py:21-86, 118-154,

@@ -522,6 +522,50 @@ int xv_seg_backward(int device, const float* gy_dev, int64_t ldgy, const float* 
   });
 }
 
+namespace {
+
+// the checks the two statistics-pooling calls share; `op` names the caller in the message
+int stat_pool_check(const char* op, int channels, int64_t batch, int64_t total_rows, int64_t ldx, int64_t ldp, int64_t ldv) {
+  if (channels < 1 || channels > 4096 || total_rows > (1 << 24))
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= channels <= 4096, total_rows <= 2^24, got %d, %lld", op, channels,
+                (long long)total_rows);
+  if (batch < 0 || total_rows < 0 || ldx < channels || ldp < 2 * (int64_t)channels || ldv < channels)
+    return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
+  return XV_OK;
+}
+
+}  // namespace
+
+// statistics pooling of the caller's packed rows, and its gradient (include/xvec_hip.h, csrc/pool_grad.hip)
+int xv_stat_pool_forward(int device, const float* x_dev, int64_t ldx, int channels, const int32_t* offsets_dev, int64_t batch,
+                         int64_t total_rows, float* pooled_dev, int64_t ldp, float* var_dev, int64_t ldv, void* stream) {
+  const int rc = stat_pool_check("xv_stat_pool_forward", channels, batch, total_rows, ldx, ldp, ldv);
+  if (rc != XV_OK) return rc;
+  if (batch == 0) return XV_OK;
+  if (!x_dev || !offsets_dev || !pooled_dev || !var_dev) return fail(nullptr, XV_ERR_INVALID, "xv_stat_pool_forward: null pointer");
+  if (batch > (int64_t)1 << 24) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_stat_pool_forward: batch <= 2^24, got %lld", (long long)batch);
+  return with_device(device, "xv_stat_pool_forward", [&] {
+    return launch_stat_pool_forward(x_dev, ldx, channels, offsets_dev, batch, total_rows, pooled_dev, ldp, var_dev, ldv,
+                                    to_stream(stream));
+  });
+}
+
+int xv_stat_pool_backward(int device, const float* gp_dev, int64_t ldgp, const float* x_dev, int64_t ldx, int channels,
+                          const int32_t* offsets_dev, int64_t batch, int64_t total_rows, const float* pooled_dev, int64_t ldp,
+                          const float* var_dev, int64_t ldv, float* gx_dev, int64_t ldgx, void* stream) {
+  const int rc = stat_pool_check("xv_stat_pool_backward", channels, batch, total_rows, ldx, ldp, ldv);
+  if (rc != XV_OK) return rc;
+  if (ldgp < 2 * (int64_t)channels || ldgx < channels) return fail(nullptr, XV_ERR_INVALID, "xv_stat_pool_backward: bad dimensions");
+  if (batch == 0) return XV_OK;
+  if (!gp_dev || !x_dev || !offsets_dev || !pooled_dev || !var_dev || !gx_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_stat_pool_backward: null pointer");
+  if (batch > (int64_t)1 << 24) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_stat_pool_backward: batch <= 2^24, got %lld", (long long)batch);
+  return with_device(device, "xv_stat_pool_backward", [&] {
+    return launch_stat_pool_backward(gp_dev, ldgp, x_dev, ldx, channels, offsets_dev, batch, total_rows, pooled_dev, ldp, var_dev,
+                                     ldv, gx_dev, ldgx, to_stream(stream));
+  });
+}
+
 int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
                     int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
                     int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,

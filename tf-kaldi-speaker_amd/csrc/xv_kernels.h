@@ -372,6 +372,14 @@ hipError_t launch_seg_backward(const float* gy, int64_t ldgy, const float* x, in
                                const float* mv, int act, float* gx, int64_t ldgx, float* gw, float* gbias, float* ggamma,
                                float* gbeta, void* ws, int64_t ws_bytes, hipStream_t s);
 
+// statistics pooling of the caller's own packed rows and its gradient (csrc/pool_grad.hip); offsets [batch + 1] on the device,
+// total_rows a host bound that sizes the backward's grid and clamps what an offset can reach
+hipError_t launch_stat_pool_forward(const float* x, int64_t ldx, int C, const int32_t* offsets, int64_t batch, int64_t total_rows,
+                                    float* pooled, int64_t ldp, float* var, int64_t ldv, hipStream_t s);
+hipError_t launch_stat_pool_backward(const float* gp, int64_t ldgp, const float* x, int64_t ldx, int C, const int32_t* offsets,
+                                     int64_t batch, int64_t total_rows, const float* pooled, int64_t ldp, const float* var,
+                                     int64_t ldv, float* gx, int64_t ldgx, hipStream_t s);
+
 // back-end training statistics (csrc/backend.hip): G = sum_r w_r (x_r - c)(x_r - c)^T in double (c, w may be null), both
 // triangles of g [d, d]; ws holds gram_f64_workspace_bytes(n, d) bytes; rows fp32, or double in the _rows64 form
 int64_t gram_f64_workspace_bytes(int64_t n, int d);

@@ -1,0 +1,256 @@
+"""Train the 1-tap frame layers behind the last multi-tap convolution together with the segment-level layers and the head: the
+next part of stage two of every fine-tune (egs/voxceleb/v1/nnet/lib/finetune.py:6-7: "... and then update the entire network"),
+as the reference's `noupdate_var_list` does it when only the multi-tap layers are named as fixed (model/trainer.py:309-320,
+501-527).
+
+The frozen forward stops at `tdnn3_relu` (`tdnn7_relu` for the extended TDNN), a public frame-level node that
+Trainer.predict_packed returns as packed rows [total_out_frames, C] on the device.  Behind it tdnn4 and tdnn5 (tdnn8, tdnn9,
+tdnn10) have kernel width 1: on packed frames they are dense + batch norm + activation with one row per frame, which is what
+xv_seg_forward / xv_seg_backward compute (tail_train.SegLayer).  The one new mathematical piece is statistics pooling on the
+CURRENT activations and its gradient (csrc/pool_grad.hip; model/pooling.py:27-52):
+    m = mean_t x_t,  v = mean_t (x_t - m)^2,  std = sqrt(max(v, 1e-12)),  pooled = [m | std];
+    gx_t = gm / n + [v > 1e-12] gs (x_t - m) / (n std)
+(the floor mask is a constant to TensorFlow; the term of d v / d m multiplies sum_t (x_t - m) = 0).
+
+A step is: SegLayer.forward per frame layer on the packed rows, StatPool.forward, the two segment layers, one
+xv_loss_classifier_grad, the segment layers backward (now with gx for the first), StatPool.backward, the frame layers backward
+(no gx for the first), one xv_opt_step per tensor.  Trained: every dense kernel and bias, gamma and beta of every batch norm
+behind the frozen node, the head.  NOT trained: the moving statistics.  Batch norm runs in INFERENCE mode and the pooling floor
+mask is a constant: **parity unpinned**, as for tail_train.py.
+
+`weight_l2_regularizer` goes on every dense kernel, the frame layers' included (model/tdnn.py: every layer takes
+kernel_regularizer); the head keeps the rule of head_train.optimizer_config, the clip is per tensor, Adam's step count is shared.
+frame_variables, frozen_node, trained_names, l2_assignment and check_supported are pure host code; the rest needs a HIP device."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from . import head_train
+from . import losses
+from . import tail_train
+
+StepResult = head_train.StepResult
+SegSpec = tail_train.SegSpec
+
+# network_type -> (variable scope, the trailing 1-tap frame layers, the frame layer whose activation is the frozen node)
+_FRAME = {"tdnn": ("tdnn", (4, 5), 3), "extended_tdnn": ("etdnn", (8, 9, 10), 7)}
+_BN = tail_train._BN
+
+
+def _dict(params):
+    return params if isinstance(params, dict) else params.dict
+
+
+def check_supported(params):
+    """NotImplementedError for what the frame-level stage does not cover: ResNet-18 (its dense1 / dense2 follow 2-D
+    convolutions), any pooling other than statistics pooling, then everything tail_train.check_supported refuses."""
+    d = _dict(params)
+    if d.get("network_type", "tdnn") == "resnet_18":
+        raise NotImplementedError("resnet_18: no 1-tap frame layers lie between its convolutions and the pooling node")
+    if d.get("pooling_type", "statistics_pooling") != "statistics_pooling":
+        raise NotImplementedError("pooling_type %s: only the gradient of statistics_pooling is implemented" % d.get("pooling_type"))
+    tail_train.check_supported(params)
+    if d.get("network_type", "tdnn") not in _FRAME:
+        raise NotImplementedError("Not implement %s network" % d.get("network_type"))
+
+
+def frame_variables(params):
+    """-> the SegSpecs of the trailing 1-tap frame layers, in forward order, under the scope names csrc/api_graph.hip uses:
+    tdnn4, tdnn5 for the TDNN and tdnn8, tdnn9, tdnn10 for the extended TDNN.  Each has a batch norm and the activation."""
+    d = _dict(params)
+    scope, layers, _ = _FRAME[d.get("network_type", "tdnn")]
+    act = _lib.XV_SEG_ACT_LRELU if d.get("network_relu_type") == "lrelu" else _lib.XV_SEG_ACT_RELU
+    return tuple(SegSpec("%s/tdnn%d_dense/kernel" % (scope, i), "%s/tdnn%d_dense/bias" % (scope, i), "%s/tdnn%d_bn" % (scope, i), act)
+                 for i in layers)
+
+
+def frozen_node(params):
+    """The frame-level endpoint the frozen forward stops at: the input of the first trained frame layer."""
+    return "tdnn%d_relu" % _FRAME[_dict(params).get("network_type", "tdnn")][2]
+
+
+def trained_names(params):
+    """The TensorFlow names of every variable FrameTrainer updates: the frame layers first, then tail_train.trained_names."""
+    out = []
+    for spec in frame_variables(params):
+        out += [spec.kernel, spec.bias, spec.bn + "/gamma", spec.bn + "/beta"]
+    return out + tail_train.trained_names(params)
+
+
+def l2_assignment(params):
+    """name -> the l2 factor of its update: weight_l2_regularizer on every dense kernel, the frame layers' included,
+    optimizer_config's rule on the head's kernel, 0 on every bias, gamma and beta."""
+    reg = float(_dict(params).get("weight_l2_regularizer", 0.0))
+    out = dict.fromkeys(trained_names(params), 0.0)
+    out.update(tail_train.l2_assignment(params))
+    for spec in frame_variables(params):
+        out[spec.kernel] = reg
+    return out
+
+
+_p = tail_train._p
+
+
+class StatPool(object):
+    """Statistics pooling of packed rows with its gradient (xv_stat_pool_forward / xv_stat_pool_backward): forward() keeps x,
+    pooled and the variance before the floor for backward()."""
+
+    def __init__(self, channels, device=0):
+        self.channels, self.device = int(channels), int(device)
+        self._torch, self._lib = losses._need_device(), _lib.load()
+        self._x = self._offsets = self._pooled = self._var = None
+        self._batch = self._rows = 0
+        self._covers = False
+
+    def forward(self, x_dev, offsets):
+        """x_dev [rows, C] on the device, float32 contiguous; offsets [B + 1] (host integers or an int32 device tensor) ->
+        pooled [B, 2 C] = [mean | std] on the device."""
+        torch = self._torch
+        c = self.channels
+        if x_dev.dim() != 2 or int(x_dev.shape[1]) != c or x_dev.dtype != torch.float32 or not x_dev.is_contiguous():
+            raise ValueError("x: expected a contiguous float32 [rows, %d], got %s" % (c, tuple(x_dev.shape)))
+        rows = int(x_dev.shape[0])
+        with torch.cuda.device(self.device):
+            if torch.is_tensor(offsets):
+                off = offsets.to(device=x_dev.device, dtype=torch.int32).contiguous()
+                covers = False                                   # not known without a copy to the host
+            else:
+                host = np.ascontiguousarray(offsets, dtype=np.int64)
+                if host.ndim != 1 or host.size < 1 or host[0] < 0 or np.any(np.diff(host) < 0) or host[-1] > rows:
+                    raise ValueError("offsets must ascend from >= 0 to at most the %d rows of x" % rows)
+                off = torch.from_numpy(host.astype(np.int32)).to(x_dev.device)
+                covers = host.size > 1 and int(host[0]) == 0 and int(host[-1]) == rows
+            batch = int(off.numel()) - 1
+            pooled = torch.empty((max(batch, 1), 2 * c), dtype=torch.float32, device=x_dev.device)
+            var = torch.empty((max(batch, 1), c), dtype=torch.float32, device=x_dev.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._lib.xv_stat_pool_forward(self.device, _p(x_dev), c, c, _p(off), batch, rows, _p(pooled), 2 * c, _p(var), c,
+                                                      C.c_void_p(stream)))
+        self._x, self._offsets, self._pooled, self._var, self._batch, self._rows = x_dev, off, pooled, var, batch, rows
+        self._covers = covers
+        return pooled[:batch]
+
+    def backward(self, g_pooled):
+        """g_pooled [B, 2 C] on the device -> gx [rows, C]; rows no utterance owns come back as zeros."""
+        torch = self._torch
+        c = self.channels
+        if self._x is None:
+            raise RuntimeError("StatPool.backward needs a forward first")
+        if tuple(g_pooled.shape) != (self._batch, 2 * c) or not g_pooled.is_contiguous():
+            raise ValueError("g_pooled: expected a contiguous [%d, %d], got %s" % (self._batch, 2 * c, tuple(g_pooled.shape)))
+        with torch.cuda.device(self.device):
+            make = torch.empty if self._covers else torch.zeros           # every row has an owner: every element is written
+            gx = make((self._rows, c), dtype=torch.float32, device=self._x.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._lib.xv_stat_pool_backward(self.device, _p(g_pooled), 2 * c, _p(self._x), c, c, _p(self._offsets), self._batch,
+                                                       self._rows, _p(self._pooled), 2 * c, _p(self._var), c, _p(gx), c,
+                                                       C.c_void_p(stream)))
+        return gx
+
+
+class FrameTrainer(object):
+    """The trailing 1-tap frame layers, statistics pooling, and a tail_train.TailTrainer (the two segment-level layers and the
+    head) behind them, all built from the checkpoint's variables."""
+
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None):
+        check_supported(params)
+        self.params = params
+        self.frame_specs = frame_variables(params)
+        self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias)
+        num_slots = len(self.tail.layers[0].slots["kernel"])
+        self.frame_layers = []
+        for spec in self.frame_specs:
+            missing = [k for k in (spec.kernel, spec.bias) + tuple(spec.bn + "/" + s for s in _BN) if k not in weights]
+            if missing:
+                raise KeyError("the checkpoint lacks %s" % ", ".join(missing))
+            k = np.asarray(weights[spec.kernel], dtype=np.float32)
+            if k.ndim != 2:
+                raise ValueError("%s: a dense kernel [cin, cout] expected, got shape %s" % (spec.kernel, k.shape))
+            self.frame_layers.append(tail_train.SegLayer(k, weights[spec.bias], [weights[spec.bn + "/" + s] for s in _BN], spec.act,
+                                                         device, num_slots))
+        for a, b, sa, sb in zip(self.frame_layers[:-1], self.frame_layers[1:], self.frame_specs[:-1], self.frame_specs[1:]):
+            if b.in_dim != a.out_dim:
+                raise ValueError("%s has %d rows, %s %d columns" % (sb.kernel, b.in_dim, sa.kernel, a.out_dim))
+        self.in_dim, self.channels = self.frame_layers[0].in_dim, self.frame_layers[-1].out_dim
+        if self.tail.pool_dim != 2 * self.channels:
+            raise ValueError("%s has %d rows, statistics pooling of %d channels gives %d" % (self.tail.specs[0].kernel, self.tail.pool_dim,
+                                                                                             self.channels, 2 * self.channels))
+        self.specs = self.frame_specs + tuple(self.tail.specs)
+        self.layers = self.frame_layers + list(self.tail.layers)
+        self.head = self.tail.head
+        self.embed_dim = self.tail.embed_dim
+        self.device = int(device)
+        self.pool = StatPool(self.channels, device)
+        self.l2 = l2_assignment(params)
+        torch = losses._need_device()
+        self._torch, self._lib = torch, _lib.load()
+        largest = max([layer.w.numel() for layer in self.layers] + [self.head.head.raw_rows.numel()])
+        if self.tail._ws.numel() < int(self._lib.xv_opt_workspace(largest)):
+            with torch.cuda.device(self.device):
+                self.tail._ws = torch.empty(int(self._lib.xv_opt_workspace(largest)), dtype=torch.uint8, device=self.tail._ws.device)
+        self.num_steps = 0                                                   # adam's t, shared by every tensor
+
+    def tensors(self):
+        """[(TensorFlow name, parameter, gradient, slots)] of everything trained, in the order of trained_names()."""
+        out = []
+        for spec, layer in zip(self.frame_specs, self.frame_layers):
+            names = {"kernel": spec.kernel, "bias": spec.bias, "gamma": spec.bn + "/gamma", "beta": spec.bn + "/beta"}
+            out += [(names[k], w, g, layer.slots[k]) for k, w, g in layer.trained()]
+        return out + self.tail.tensors()
+
+    def _frames(self, frames_dev):
+        torch = self._torch
+        if not torch.is_tensor(frames_dev) or not frames_dev.is_cuda:
+            raise ValueError("frames_dev must be a device tensor: the frames never leave the device")
+        if frames_dev.dim() != 2 or int(frames_dev.shape[1]) != self.in_dim or frames_dev.dtype != torch.float32:
+            raise ValueError("frames_dev: expected float32 [rows, %d], got %s" % (self.in_dim, tuple(frames_dev.shape)))
+        return frames_dev.contiguous()
+
+    def _forward(self, frames_dev, offsets):
+        x = self._frames(frames_dev)
+        for layer in self.frame_layers:
+            x = layer.forward(x)
+        pooled = self.pool.forward(x.contiguous(), offsets)
+        return self.tail.layers[1].forward(self.tail.layers[0].forward(pooled.contiguous()))
+
+    def forward(self, frames_dev, offsets):
+        """frames_dev [rows, in_dim] on the device (the frozen node's packed output), offsets [B + 1] of its rows -> the
+        `output` endpoint [B, embed_dim] on the device, with the current weights."""
+        with self._torch.cuda.device(self.device):
+            return self._forward(frames_dev, offsets)
+
+    def step(self, frames_dev, offsets, labels, learning_rate, global_step=0):
+        """One training step on a batch of packed frames: forward through the frame layers, the pooling and the segment layers,
+        the head's mean loss at `global_step` and its gradients, backward through all of them, then per tensor l2 (kernels only),
+        the clip and the update -> StepResult(mean loss, top-1 accuracy), both of the parameters BEFORE the update."""
+        torch = self._torch
+        h = self.head
+        with torch.cuda.device(self.device):
+            y = self._forward(frames_dev, offsets)
+            out, top1, gx, _, _ = h.head._grad_device(y, labels, global_step, None, True, h._grad_rows, h._grad_bias)
+            n = int(out.shape[1])
+            g = self.tail.layers[1].backward(gx, True)
+            g = self.tail.layers[0].backward(g, True)
+            g = self.pool.backward(g)
+            for i in range(len(self.frame_layers) - 1, -1, -1):
+                g = self.frame_layers[i].backward(g, i > 0)
+            self.num_steps += 1
+            self.tail.num_steps = h.num_steps = self.num_steps
+            for name, w, gw, slots in self.tensors():
+                self.tail._apply(w, gw, slots, learning_rate, self.l2[name])
+            lab = losses._labels_dev(labels, n, out.device, torch)
+            return StepResult(float(out[0].double().mean()) if n else float("nan"),
+                              float((top1 == lab).double().mean()) if n else float("nan"))
+
+    def variables(self):
+        """name -> float32 numpy of every trained variable under its TensorFlow name (kernels as [in, out])."""
+        out = collections.OrderedDict()
+        for spec, layer in zip(self.frame_specs, self.frame_layers):
+            out[spec.kernel] = layer.kernel()
+            out[spec.bias] = layer.b.cpu().numpy().copy()
+            out[spec.bn + "/gamma"] = layer.bn[0].cpu().numpy().copy()
+            out[spec.bn + "/beta"] = layer.bn[1].cpu().numpy().copy()
+        out.update(self.tail.variables())
+        return out

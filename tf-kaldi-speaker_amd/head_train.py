@@ -228,8 +228,31 @@ def read_learning_rate_file(path):
 
 
 # ---------------------------------------------------------------------------------------------- the driver
+def _frame_step(trainer, head, feats, labels, lr, step):
+    """One FrameTrainer step on the batch feats [B, T, dim]: the frozen forward to trainer.embeddings (a frame-level node) hands
+    its packed rows over on the device; utterance b owns out_rows / B of them (T less the node's context)."""
+    if not trainer.is_loaded:
+        trainer._lazy_load()
+    torch = trainer._torch
+    b, t, d = feats.shape
+    with torch.cuda.device(trainer._device_index):
+        dev = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32).reshape(b * t, d)).to("cuda:%d" % trainer._device_index)
+        offsets = np.arange(b + 1, dtype=np.int32) * t
+        frames = trainer.predict_packed(dev, offsets)
+        try:                                             # the range guard of the fp16 precisions, as Trainer.predict applies it
+            trainer.raise_on_flags(trainer.check_overflow())
+        except FloatingPointError as e:
+            if not trainer._range_fallback:
+                raise
+            frames = trainer._fallback_trainer(str(e)).predict_packed(dev, offsets, trainer.embeddings)
+        per = int(frames.shape[0]) // b
+        if per * b != int(frames.shape[0]) or per < 1:
+            raise RuntimeError("%s returned %d rows for %d chunks of %d frames" % (trainer.embeddings, int(frames.shape[0]), b, t))
+        return head.step(frames, np.arange(b + 1, dtype=np.int64) * per, labels, lr, global_step=step)
+
+
 def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_model_dir, weights=None, seed=0, keep_head=False,
-               precision=None, log=None, segment_layers=False):
+               precision=None, log=None, segment_layers=False, frame_layers=False):
     """Train the head of `trainer` (a Trainer built for "predict" with the pre-trained weights loaded; its params name the head,
     the optimizer and the schedule) on train_dir and write <out_model_dir>/nnet after every epoch of num_steps_per_epoch steps:
     model-<step>.npz (model_io.save_model: every variable of `weights` unchanged plus the new softmax/output/kernel and bias),
@@ -239,6 +262,10 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     With segment_layers the frozen forward stops at the `pooling` node and the two segment-level layers behind it are trained
     with the head (tail_train.TailTrainer): the checkpoints then also hold their new kernels, biases, gamma and beta; every
     other variable, their moving statistics included, is unchanged.
+    With frame_layers (which implies segment_layers) the frozen forward stops at frame_train.frozen_node (tdnn3_relu, or
+    tdnn7_relu for the extended TDNN): its packed frames stay on the device (Trainer.predict_packed) and the 1-tap frame layers
+    behind it, the statistics pooling, the segment-level layers and the head are trained by frame_train.FrameTrainer.  The
+    checkpoints then hold the new frame-layer kernels, biases, gamma and beta as well.
     -> [(epoch, step, valid loss, eer, learning rate)]."""
     from . import scoring
     from . import valid as valid_mod
@@ -260,7 +287,13 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     rule = LearningRateRule(params, learning_rate if schedule is None else schedule[0], schedule)
 
     endpoint = trainer.embeddings
-    trainer.embeddings = "pooling" if segment_layers else "output"       # the caller's trainer gets its endpoint back on exit
+    if frame_layers:
+        from . import frame_train
+        frame_train.check_supported(params)                              # before the trainer is touched
+        segment_layers = True
+        trainer.embeddings = frame_train.frozen_node(params)
+    else:
+        trainer.embeddings = "pooling" if segment_layers else "output"   # the caller's trainer gets its endpoint back on exit
     try:
         if segment_layers:
             from . import tail_train
@@ -274,7 +307,9 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
             k = weights.get(model_io.SOFTMAX_KERNEL)
             if k is not None and tuple(k.shape) == (embed_dim, num_classes):
                 kernel, bias = np.asarray(k), weights.get(model_io.SOFTMAX_BIAS)
-        if segment_layers:
+        if frame_layers:
+            head = frame_train.FrameTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
+        elif segment_layers:
             head = tail_train.TailTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
         else:
             head = HeadTrainer(params, embed_dim, num_classes, trainer._device_index, seed, kernel, bias)
@@ -284,8 +319,11 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
         for epoch in range(num_epochs):
             lr = rule.rate(epoch)
             for batch in plan_train_batches(train_dir, train_spklist, params, seed, epoch):
-                emb = trainer.predict(read_train_batch(batch, trainer.dim))
-                res = head.step(emb, batch.labels, lr, global_step=step)
+                feats = read_train_batch(batch, trainer.dim)
+                if frame_layers:
+                    res = _frame_step(trainer, head, feats, batch.labels, lr, step)
+                else:
+                    res = head.step(trainer.predict(feats), batch.labels, lr, global_step=step)
                 step += 1
                 if log is not None:
                     log("epoch %d step %d loss %f acc %f" % (epoch, step, res.loss, res.accuracy))

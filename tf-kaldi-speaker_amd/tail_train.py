@@ -2,7 +2,8 @@
 (egs/voxceleb/v1/nnet/lib/finetune.py:6-7: "... and then update the entire network"), as the reference's `noupdate_var_list`
 does it when the frame-level layers are named as fixed (model/trainer.py:309-320, 501-527).
 
-Everything up to the `pooling` node stays as the checkpoint has it, so no frame-level backward pass is needed.  A step is: the
+Everything up to the `pooling` node stays as the checkpoint has it, so no frame-level backward pass is needed (frame_train.py
+goes on from here: the 1-tap frame layers in front of the pooling node, through the gradient of statistics pooling).  A step is: the
 frozen forward to `pooling` (Trainer.predict, by the caller), xv_seg_forward through tdnn6 and tdnn7 (tdnn12 / tdnn13 for the
 extended TDNN) with their CURRENT weights, one xv_loss_classifier_grad for the loss and grad_x, xv_seg_backward through both
 layers (csrc/seg_grad.hip), one xv_opt_step per tensor.  Trained: the two dense kernels and biases, gamma and beta of their

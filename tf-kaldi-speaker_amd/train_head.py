@@ -2,14 +2,17 @@
 egs/voxceleb/v1/nnet/lib/finetune.py, with its positional arguments.
 
     python -m tf_kaldi_speaker_amd.train_head [--gpu N] [--checkpoint C] [--config new.json] [--seed S] [--precision P]
-                                              [--keep-head] [--segment-layers] pretrain_model train_dir train_spklist valid_dir valid_spklist
+                                              [--keep-head] [--segment-layers] [--frame-layers] pretrain_model train_dir train_spklist valid_dir valid_spklist
                                               finetune_model
 
 `--config` names the configuration of the NEW model (loss_func, margins, optimizer, learning-rate schedule, batch shape); without
 it the pre-trained model's config.json is used.  The network hyper-parameters must be those of the pre-trained model: its
 variables are copied unchanged.  `--checkpoint` is a checkpoint name under <pretrain_model>/nnet (default: the one its
 `checkpoint` file names).  `--segment-layers` trains the two dense layers behind the pooling node together with the head
-(tail_train.py); the intended flow is the head first, then `--segment-layers --keep-head` on the directory the first run wrote.
+(tail_train.py); `--frame-layers` (which implies `--segment-layers`) also trains the 1-tap frame layers between the last
+multi-tap convolution and the pooling node, through the gradient of statistics pooling (frame_train.py).  The intended flow is
+three runs: the head first, then `--segment-layers --keep-head` on the directory the first run wrote, then
+`--frame-layers --keep-head` on the directory of the second.
 One line per epoch: `epoch <e> step <s> loss <valid loss> eer <eer> lr <rate>`."""
 import argparse
 import os
@@ -30,6 +33,9 @@ def build_parser():
     parser.add_argument("--keep-head", action="store_true", help="Start from the checkpoint's own softmax kernel when its shape fits.")
     parser.add_argument("--segment-layers", action="store_true", help="Train the two segment-level layers behind the pooling node "
                         "together with the head (everything in front of it stays frozen).")
+    parser.add_argument("--frame-layers", action="store_true", help="Also train the 1-tap frame layers behind the last multi-tap "
+                        "convolution (tdnn4, tdnn5; tdnn8 .. tdnn10 of the extended TDNN) through the gradient of statistics pooling; "
+                        "implies --segment-layers.")
     parser.add_argument("--verbose", action="store_true", help="One line per step.")
     parser.add_argument("pretrain_model", type=str, help="The pre-trained model directory.")
     parser.add_argument("train_dir", type=str, help="The data directory of the training set.")
@@ -64,7 +70,7 @@ def main(argv=None):
     history = head_train.train_head(trainer, args.train_dir, args.train_spklist, args.valid_dir, args.valid_spklist,
                                     args.finetune_model, weights=weights, seed=seed, keep_head=args.keep_head,
                                     precision=args.precision or None, log=print if args.verbose else None,
-                                    segment_layers=args.segment_layers)
+                                    segment_layers=args.segment_layers or args.frame_layers, frame_layers=args.frame_layers)
     for epoch, step, loss, eer, lr in history:
         print("epoch %d step %d loss %f eer %f lr %.8f" % (epoch, step, loss, eer, lr))
     trainer.close()
