@@ -10,6 +10,7 @@ precision=
 keep_head=false
 segment_layers=false
 frame_layers=false
+conv_layers=false
 
 if [ -f path.sh ]; then . ./path.sh; fi
 if [ -f parse_options.sh ] || command -v parse_options.sh >/dev/null 2>&1; then
@@ -36,6 +37,8 @@ if [ $# != 6 ]; then
   echo "  --segment-layers <false> # also train the two dense layers behind the pooling node (run the head alone first)"
   echo "  --frame-layers <false>   # also train the 1-tap frame layers in front of the pooling node; implies --segment-layers"
   echo "                           # (run the head alone first, then --segment-layers, then this)"
+  echo "  --conv-layers <false>    # train every frame-level layer, the multi-tap convolutions included; implies the other two"
+  echo "                           # (the fourth run, after --frame-layers)"
   echo ""
   exit 100
 fi
@@ -48,6 +51,7 @@ if [ -n "$precision" ]; then opts="$opts --precision $precision"; fi
 if $keep_head; then opts="$opts --keep-head"; fi
 if $segment_layers; then opts="$opts --segment-layers"; fi
 if $frame_layers; then opts="$opts --frame-layers"; fi
+if $conv_layers; then opts="$opts --conv-layers"; fi
 
 here=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export PYTHONPATH=$here:$PYTHONPATH

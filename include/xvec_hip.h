@@ -792,6 +792,62 @@ int xv_stat_pool_backward(int device, const float* gp_dev, int64_t ldgp, const f
                           const int32_t* offsets_dev, int64_t batch, int64_t total_rows, const float* pooled_dev, int64_t ldp,
                           const float* var_dev, int64_t ldv, float* gx_dev, int64_t ldgx, void* stream);
 
+/* ---- one frame-level layer on packed utterances with its CURRENT weights, forward and backward (csrc/tconv_grad.hip): a W-tap
+ * temporal convolution (tf.layers.conv2d(.., (1, W)) / tf.layers.conv1d(.., W) of model/tdnn.py: VALID, stride 1, no dilation) +
+ * batch norm in INFERENCE mode + activation.  It is what training tdnn1 .. tdnn3 (tdnn1 .. tdnn7 of the extended TDNN) needs;
+ * with taps = 1 it is the dense layer of xv_seg_forward / xv_seg_backward on packed frames (**parity unpinned**, as there).
+ * Layout: x_dev [*, ldx] has C = channels columns; utterance b owns its rows offsets[b] .. offsets[b + 1]), n_in of them, and
+ *   produces n_out = max(n_in - (W - 1), 0) output rows.  offsets_dev [batch + 1] is int32 on the device, ascends, offsets[0] >=
+ *   0.  The outputs are packed densely from row 0: out_off[b] = sum_{a < b} n_out_a, computed on the device.  total_in >=
+ *   offsets[batch] - offsets[0] and total_out >= out_off[batch] are host values that size grids and the workspace and nothing
+ *   else.  w_dev [N = out_dim, ldw] holds the ROWS of the weights with K = W C columns, k = tau C + c: the TensorFlow kernel
+ *   [W, C, N] (or [1, W, C, N]) reshaped to [W C, N] and transposed.  bias, gamma, beta, moving_mean, moving_variance [N] and act
+ *   as for xv_seg_forward.
+ * The rule, for output row t of utterance b (row out_off[b] + t of z, y and gy):
+ *   z_tj = sum_tau sum_c x[offsets[b] + t + tau, c] w[j, tau C + c] + b_j;
+ *   h, y, a = gy act'(h), gz, gbeta, ggamma and gbias are exactly the lines of xv_seg_forward / xv_seg_backward, in the same
+ *   float32 rounding order (r_j = float(1 / sqrt(double(mv_j) + 1e-3)); s_j = gamma_j * r_j; d = z - mm_j; h = fma(s_j, d,
+ *   beta_j); leaky ReLU multiplies by float(0.2); the backward recomputes h from the stored z by the forward's instructions);
+ *   gw[j, tau C + c] = sum over all output rows of all utterances of gz_tj x[offsets[b] + t + tau, c], the columns beyond K left
+ *   alone;
+ *   gx[offsets[b] + s, c] = sum_tau sum_j gz_b[s - tau, j] w[j, tau C + c] over the tau with 0 <= s - tau < n_out, [*, ldgx] in the
+ *   row numbering of x; every owned row is written, so an utterance with n_out = 0 gets zero rows.  gx_dev = NULL skips that
+ *   product (the first layer never needs it).
+ * Orders (all exact fp32 products on v_mfma_f32_32x32x2_f32, no floating-point atomics anywhere): the chain of z runs over k = tau
+ *   C + c ascending from 0, then + b_j; the chain of gx over tau ascending, then j ascending (through round4(N) - N exact zeros
+ *   per tap); the chain of gw over the output rows ascending, cut into S contiguous ranges of ceil32(ceil(total_out / S')) rows
+ *   whose sums are added in ascending order in float32, S' = max(1, min(floor(512 / (ceil(N / 64) ceil(K / 64))), 32, ceil(total_out
+ *   / 256))); the column sums gbeta, ggamma and gbias run in double over slices of max(1024, ceil64(ceil(total_out / 64))) rows,
+ *   within a slice 64 interleaved partial sums in ascending row order closed by a fixed butterfly, the slices in ascending order,
+ *   rounded once.  Every order is a function of the shapes and total_out alone.
+ * Properties (tests/test_gpu_tconv.py): every output is bit-identical on every repeat, for every legal ws_bytes and whatever the
+ *   workspace and the outputs held before; z, y and gx of an utterance are a pure function of its own rows and the parameters,
+ *   alone or in any batch, at any position.  Nothing outside [offsets[0], offsets[batch]) is read; nothing outside the first
+ *   total_out rows of z and y and the owned rows of gx is written.  ldx >= C is supported (the address of k is (k / C) ldx + k %
+ *   C past the row's start); 16-byte accesses are used only where the bases, the leading dimensions and C allow.  The
+ *   per-element error bound is derived in the header of csrc/tconv_grad.hip.  Both calls only enqueue work and never wait.
+ *   batch = 0 or total_out = 0 is legal: XV_OK, nothing touched.
+ * 1 <= taps <= 16, taps * channels <= 16384, 1 <= out_dim <= 4096, batch, total_in, total_out <= 2^24: XV_ERR_UNSUPPORTED
+ *   beyond.  A leading dimension below its width, an unknown activation, a missing pointer, some but not all of the four
+ *   batch-norm pointers, total_in < total_out in the backward call: XV_ERR_INVALID, before any launch.
+ * Workspace (16-byte aligned; XV_ERR_WORKSPACE below the least size): xv_tconv_forward keeps the row maps in the first
+ *   xv_tconv_forward_workspace(batch, total_out) bytes.  xv_tconv_backward takes any ws_bytes >= xv_tconv_workspace_min(..): the
+ *   row maps, gz [total_out, round4(N)], the slice sums and the S planes of gw.  Nothing is panelled, so xv_tconv_workspace
+ *   equals xv_tconv_workspace_min and a larger workspace is not used.  The backward call builds its own maps: it does not need
+ *   the workspace of the forward call.  All three are 0 for batch = 0 or total_out = 0. */
+int64_t xv_tconv_workspace(int64_t batch, int64_t total_in, int64_t total_out, int taps, int channels, int out_dim);
+int64_t xv_tconv_workspace_min(int64_t batch, int64_t total_in, int64_t total_out, int taps, int channels, int out_dim);
+int64_t xv_tconv_forward_workspace(int64_t batch, int64_t total_out);
+int xv_tconv_forward(int device, const float* x_dev, int64_t ldx, int channels, int taps, const int32_t* offsets_dev, int64_t batch,
+                     int64_t total_in, int64_t total_out, const float* w_dev, int64_t ldw, int out_dim, const float* bias_dev,
+                     const float* gamma_dev, const float* beta_dev, const float* mean_dev, const float* var_dev, int act,
+                     float* z_dev, int64_t ldz, float* y_dev, int64_t ldy, void* ws_dev, int64_t ws_bytes, void* stream);
+int xv_tconv_backward(int device, const float* gy_dev, int64_t ldgy, const float* x_dev, int64_t ldx, int channels, int taps,
+                      const int32_t* offsets_dev, int64_t batch, int64_t total_in, int64_t total_out, const float* z_dev, int64_t ldz,
+                      const float* w_dev, int64_t ldw, int out_dim, const float* gamma_dev, const float* beta_dev,
+                      const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx, float* gw_dev,
+                      float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- metric-learning loss heads on the GPU (csrc/metric_loss.hip): what validation needs for a checkpoint trained with
  * `semihard_triplet_loss` (model/loss.py:387-527) or `angular_triplet_loss` (:530-663; validated with `e2e_valid_loss`,
  * :666-734, model/trainer.py:424-427).  Pinned to the reference's float64 numpy twins (model/test_utils.py:21-86, 118-154,

@@ -47,6 +47,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_loss_classifier_grad", "xv_opt_workspace", "xv_opt_step",
            "xv_seg_workspace", "xv_seg_workspace_min", "xv_seg_forward", "xv_seg_backward",
            "xv_stat_pool_forward", "xv_stat_pool_backward",
+           "xv_tconv_workspace", "xv_tconv_workspace_min", "xv_tconv_forward_workspace", "xv_tconv_forward", "xv_tconv_backward",
            "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
            "xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse",
@@ -228,6 +229,16 @@ def load():
                                     vp, i64, vp]
     lib.xv_stat_pool_forward.argtypes = [i32, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp]
     lib.xv_stat_pool_backward.argtypes = [i32, vp, i64, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp]
+    lib.xv_tconv_workspace.argtypes = [i64, i64, i64, i32, i32, i32]
+    lib.xv_tconv_workspace.restype = i64
+    lib.xv_tconv_workspace_min.argtypes = [i64, i64, i64, i32, i32, i32]
+    lib.xv_tconv_workspace_min.restype = i64
+    lib.xv_tconv_forward_workspace.argtypes = [i64, i64]
+    lib.xv_tconv_forward_workspace.restype = i64
+    lib.xv_tconv_forward.argtypes = [i32, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64,
+                                     vp, i64, vp]
+    lib.xv_tconv_backward.argtypes = [i32, vp, i64, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i32,
+                                      vp, i64, vp, vp, vp, vp, vp, i64, vp]
     lib.xv_metric_loss_workspace.argtypes = [i64, vp, i32, i32]
     lib.xv_metric_loss_workspace.restype = i64
     lib.xv_metric_loss_slot_bytes.argtypes = [i32, i32, i32]

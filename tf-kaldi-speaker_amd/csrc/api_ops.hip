@@ -566,6 +566,92 @@ int xv_stat_pool_backward(int device, const float* gp_dev, int64_t ldgp, const f
   });
 }
 
+// a frame-level layer on packed utterances: W-tap temporal convolution + batch norm + activation (include/xvec_hip.h,
+// csrc/tconv_grad.hip)
+int64_t xv_tconv_workspace(int64_t batch, int64_t total_in, int64_t total_out, int taps, int channels, int out_dim) {
+  return tconv_workspace_bytes(batch, total_in, total_out, taps, channels, out_dim);
+}
+
+int64_t xv_tconv_workspace_min(int64_t batch, int64_t total_in, int64_t total_out, int taps, int channels, int out_dim) {
+  return tconv_workspace_bytes(batch, total_in, total_out, taps, channels, out_dim);
+}
+
+int64_t xv_tconv_forward_workspace(int64_t batch, int64_t total_out) { return tconv_forward_workspace_bytes(batch, total_out); }
+
+namespace {
+
+// the checks the two calls of a temporal-convolution layer share; `op` names the caller in the message
+int tconv_check(const char* op, int taps, int channels, int out_dim, int64_t batch, int64_t total_in, int64_t total_out, int64_t ldx,
+                int64_t ldw, const void* gamma, const void* beta, const void* mm, const void* mv, int act) {
+  if (taps < 1 || taps > 16 || channels < 1 || (int64_t)taps * channels > 16384 || out_dim < 1 || out_dim > 4096 ||
+      batch > (1 << 24) || total_in > (1 << 24) || total_out > (1 << 24))
+    return fail(nullptr, XV_ERR_UNSUPPORTED,
+                "%s: 1 <= taps <= 16, taps * channels <= 16384, 1 <= out_dim <= 4096, batch and rows <= 2^24, got %d, %d, %d, %lld, "
+                "%lld, %lld", op, taps, channels, out_dim, (long long)batch, (long long)total_in, (long long)total_out);
+  if (batch < 0 || total_in < 0 || total_out < 0 || ldx < channels || ldw < (int64_t)taps * channels)
+    return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
+  const int given = (gamma != nullptr) + (beta != nullptr) + (mm != nullptr) + (mv != nullptr);
+  if (given != 0 && given != 4)
+    return fail(nullptr, XV_ERR_INVALID, "%s: batch norm needs gamma, beta, moving_mean and moving_variance, or none of them", op);
+  if (act < XV_SEG_ACT_NONE || act > XV_SEG_ACT_LRELU) return fail(nullptr, XV_ERR_INVALID, "%s: unknown activation %d", op, act);
+  return XV_OK;
+}
+
+int tconv_ws_check(const char* op, const void* ws_dev, int64_t ws_bytes, int64_t need) {
+  if (!ws_dev || ws_bytes < need)
+    return fail(nullptr, XV_ERR_WORKSPACE, "%s: workspace of %lld bytes, at least %lld needed", op, (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  if ((reinterpret_cast<uintptr_t>(ws_dev) & 15) != 0)
+    return fail(nullptr, XV_ERR_INVALID, "%s: the workspace must be 16-byte aligned", op);
+  return XV_OK;
+}
+
+}  // namespace
+
+int xv_tconv_forward(int device, const float* x_dev, int64_t ldx, int channels, int taps, const int32_t* offsets_dev, int64_t batch,
+                     int64_t total_in, int64_t total_out, const float* w_dev, int64_t ldw, int out_dim, const float* bias_dev,
+                     const float* gamma_dev, const float* beta_dev, const float* mean_dev, const float* var_dev, int act,
+                     float* z_dev, int64_t ldz, float* y_dev, int64_t ldy, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (!x_dev || !offsets_dev || !w_dev || !bias_dev || !z_dev || !y_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_tconv_forward: null pointer");
+  int rc = tconv_check("xv_tconv_forward", taps, channels, out_dim, batch, total_in, total_out, ldx, ldw, gamma_dev, beta_dev, mean_dev,
+                       var_dev, act);
+  if (rc != XV_OK) return rc;
+  if (ldz < out_dim || ldy < out_dim) return fail(nullptr, XV_ERR_INVALID, "xv_tconv_forward: bad dimensions");
+  if (batch == 0 || total_out == 0) return XV_OK;
+  if ((rc = tconv_ws_check("xv_tconv_forward", ws_dev, ws_bytes, tconv_forward_workspace_bytes(batch, total_out))) != XV_OK) return rc;
+  return with_device(device, "xv_tconv_forward", [&] {
+    return launch_tconv_forward(x_dev, ldx, channels, taps, offsets_dev, batch, total_in, total_out, w_dev, ldw, out_dim, bias_dev,
+                                gamma_dev, beta_dev, mean_dev, var_dev, act, z_dev, ldz, y_dev, ldy, ws_dev, to_stream(stream));
+  });
+}
+
+int xv_tconv_backward(int device, const float* gy_dev, int64_t ldgy, const float* x_dev, int64_t ldx, int channels, int taps,
+                      const int32_t* offsets_dev, int64_t batch, int64_t total_in, int64_t total_out, const float* z_dev, int64_t ldz,
+                      const float* w_dev, int64_t ldw, int out_dim, const float* gamma_dev, const float* beta_dev,
+                      const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx, float* gw_dev,
+                      float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (!gy_dev || !x_dev || !offsets_dev || !z_dev || !w_dev || !gw_dev || !gbias_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_tconv_backward: null pointer");
+  int rc = tconv_check("xv_tconv_backward", taps, channels, out_dim, batch, total_in, total_out, ldx, ldw, gamma_dev, beta_dev,
+                       mean_dev, var_dev, act);
+  if (rc != XV_OK) return rc;
+  if (gamma_dev && (!ggamma_dev || !gbeta_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_tconv_backward: batch norm needs ggamma_dev and gbeta_dev");
+  if (ldgy < out_dim || ldz < out_dim || (gx_dev && ldgx < channels))
+    return fail(nullptr, XV_ERR_INVALID, "xv_tconv_backward: bad dimensions");
+  if (batch == 0 || total_out == 0) return XV_OK;
+  if (total_in < total_out) return fail(nullptr, XV_ERR_INVALID, "xv_tconv_backward: total_in below total_out");
+  if ((rc = tconv_ws_check("xv_tconv_backward", ws_dev, ws_bytes,
+                           tconv_workspace_bytes(batch, total_in, total_out, taps, channels, out_dim))) != XV_OK)
+    return rc;
+  return with_device(device, "xv_tconv_backward", [&] {
+    return launch_tconv_backward(gy_dev, ldgy, x_dev, ldx, channels, taps, offsets_dev, batch, total_in, total_out, z_dev, ldz, w_dev,
+                                 ldw, out_dim, gamma_dev, beta_dev, mean_dev, var_dev, act, gx_dev, ldgx, gw_dev, gbias_dev,
+                                 ggamma_dev, gbeta_dev, ws_dev, to_stream(stream));
+  });
+}
+
 int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
                     int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
                     int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,

@@ -372,6 +372,21 @@ hipError_t launch_seg_backward(const float* gy, int64_t ldgy, const float* x, in
                                const float* mv, int act, float* gx, int64_t ldgx, float* gw, float* gbias, float* ggamma,
                                float* gbeta, void* ws, int64_t ws_bytes, hipStream_t s);
 
+// one frame-level layer on packed utterances, W-tap temporal convolution + inference-mode batch norm + activation, forward and
+// backward (csrc/tconv_grad.hip).  offsets [batch + 1] on the device; total_in and total_out are host bounds that size grids.
+// ws as sized by tconv_workspace_bytes (the forward uses its first tconv_forward_workspace_bytes only).
+int64_t tconv_workspace_bytes(int64_t batch, int64_t total_in, int64_t total_out, int W, int C, int N);
+int64_t tconv_forward_workspace_bytes(int64_t batch, int64_t total_out);
+hipError_t launch_tconv_forward(const float* x, int64_t ldx, int C, int W, const int32_t* offsets, int64_t batch, int64_t total_in,
+                                int64_t total_out, const float* w, int64_t ldw, int N, const float* bias, const float* gamma,
+                                const float* beta, const float* mm, const float* mv, int act, float* z, int64_t ldz, float* y,
+                                int64_t ldy, void* ws, hipStream_t s);
+hipError_t launch_tconv_backward(const float* gy, int64_t ldgy, const float* x, int64_t ldx, int C, int W, const int32_t* offsets,
+                                 int64_t batch, int64_t total_in, int64_t total_out, const float* z, int64_t ldz, const float* w,
+                                 int64_t ldw, int N, const float* gamma, const float* beta, const float* mm, const float* mv, int act,
+                                 float* gx, int64_t ldgx, float* gw, float* gbias, float* ggamma, float* gbeta, void* ws,
+                                 hipStream_t s);
+
 // statistics pooling of the caller's own packed rows and its gradient (csrc/pool_grad.hip); offsets [batch + 1] on the device,
 // total_rows a host bound that sizes the backward's grid and clamps what an offset can reach
 hipError_t launch_stat_pool_forward(const float* x, int64_t ldx, int C, const int32_t* offsets, int64_t batch, int64_t total_rows,

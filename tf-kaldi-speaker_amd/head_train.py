@@ -251,8 +251,19 @@ def _frame_step(trainer, head, feats, labels, lr, step):
         return head.step(frames, np.arange(b + 1, dtype=np.int64) * per, labels, lr, global_step=step)
 
 
+def _conv_step(trainer, head, feats, labels, lr, step):
+    """One ConvTrainer step on the batch feats [B, T, dim]: the packed features go straight in, there is no frozen forward."""
+    if not trainer.is_loaded:
+        trainer._lazy_load()
+    torch = trainer._torch
+    b, t, d = feats.shape
+    with torch.cuda.device(trainer._device_index):
+        dev = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32).reshape(b * t, d)).to("cuda:%d" % trainer._device_index)
+        return head.step(dev, np.arange(b + 1, dtype=np.int64) * t, labels, lr, global_step=step)
+
+
 def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_model_dir, weights=None, seed=0, keep_head=False,
-               precision=None, log=None, segment_layers=False, frame_layers=False):
+               precision=None, log=None, segment_layers=False, frame_layers=False, conv_layers=False):
     """Train the head of `trainer` (a Trainer built for "predict" with the pre-trained weights loaded; its params name the head,
     the optimizer and the schedule) on train_dir and write <out_model_dir>/nnet after every epoch of num_steps_per_epoch steps:
     model-<step>.npz (model_io.save_model: every variable of `weights` unchanged plus the new softmax/output/kernel and bias),
@@ -266,6 +277,10 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     tdnn7_relu for the extended TDNN): its packed frames stay on the device (Trainer.predict_packed) and the 1-tap frame layers
     behind it, the statistics pooling, the segment-level layers and the head are trained by frame_train.FrameTrainer.  The
     checkpoints then hold the new frame-layer kernels, biases, gamma and beta as well.
+    With conv_layers (which implies the other two) nothing is frozen: conv_train.ConvTrainer trains every frame-level layer, the
+    multi-tap convolutions included, on the packed features, in exact fp32 whatever `precision` says.  The checkpoints then hold
+    the new convolution kernels in the shape the input had, and biases, gamma and beta; the moving statistics and every other
+    variable are unchanged.
     -> [(epoch, step, valid loss, eer, learning rate)]."""
     from . import scoring
     from . import valid as valid_mod
@@ -287,7 +302,11 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     rule = LearningRateRule(params, learning_rate if schedule is None else schedule[0], schedule)
 
     endpoint = trainer.embeddings
-    if frame_layers:
+    if conv_layers:
+        from . import conv_train
+        conv_train.check_supported(params)                               # before the trainer is touched
+        segment_layers = frame_layers = True
+    elif frame_layers:
         from . import frame_train
         frame_train.check_supported(params)                              # before the trainer is touched
         segment_layers = True
@@ -307,7 +326,9 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
             k = weights.get(model_io.SOFTMAX_KERNEL)
             if k is not None and tuple(k.shape) == (embed_dim, num_classes):
                 kernel, bias = np.asarray(k), weights.get(model_io.SOFTMAX_BIAS)
-        if frame_layers:
+        if conv_layers:
+            head = conv_train.ConvTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
+        elif frame_layers:
             head = frame_train.FrameTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
         elif segment_layers:
             head = tail_train.TailTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
@@ -320,7 +341,9 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
             lr = rule.rate(epoch)
             for batch in plan_train_batches(train_dir, train_spklist, params, seed, epoch):
                 feats = read_train_batch(batch, trainer.dim)
-                if frame_layers:
+                if conv_layers:
+                    res = _conv_step(trainer, head, feats, batch.labels, lr, step)
+                elif frame_layers:
                     res = _frame_step(trainer, head, feats, batch.labels, lr, step)
                 else:
                     res = head.step(trainer.predict(feats), batch.labels, lr, global_step=step)

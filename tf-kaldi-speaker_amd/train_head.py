@@ -2,7 +2,7 @@
 egs/voxceleb/v1/nnet/lib/finetune.py, with its positional arguments.
 
     python -m tf_kaldi_speaker_amd.train_head [--gpu N] [--checkpoint C] [--config new.json] [--seed S] [--precision P]
-                                              [--keep-head] [--segment-layers] [--frame-layers] pretrain_model train_dir train_spklist valid_dir valid_spklist
+                                              [--keep-head] [--segment-layers] [--frame-layers] [--conv-layers] pretrain_model train_dir train_spklist valid_dir valid_spklist
                                               finetune_model
 
 `--config` names the configuration of the NEW model (loss_func, margins, optimizer, learning-rate schedule, batch shape); without
@@ -12,7 +12,9 @@ variables are copied unchanged.  `--checkpoint` is a checkpoint name under <pret
 (tail_train.py); `--frame-layers` (which implies `--segment-layers`) also trains the 1-tap frame layers between the last
 multi-tap convolution and the pooling node, through the gradient of statistics pooling (frame_train.py).  The intended flow is
 three runs: the head first, then `--segment-layers --keep-head` on the directory the first run wrote, then
-`--frame-layers --keep-head` on the directory of the second.
+`--frame-layers --keep-head` on the directory of the second.  `--conv-layers` (which implies the other two) trains every
+frame-level layer, the multi-tap convolutions included, on the packed features (conv_train.py): a fourth run, on the directory
+of the third.
 One line per epoch: `epoch <e> step <s> loss <valid loss> eer <eer> lr <rate>`."""
 import argparse
 import os
@@ -36,6 +38,9 @@ def build_parser():
     parser.add_argument("--frame-layers", action="store_true", help="Also train the 1-tap frame layers behind the last multi-tap "
                         "convolution (tdnn4, tdnn5; tdnn8 .. tdnn10 of the extended TDNN) through the gradient of statistics pooling; "
                         "implies --segment-layers.")
+    parser.add_argument("--conv-layers", action="store_true", help="Train every frame-level layer, the multi-tap convolutions "
+                        "(tdnn1 .. tdnn3; tdnn1 .. tdnn7 of the extended TDNN) included: nothing stays frozen but the moving "
+                        "statistics; implies --frame-layers and --segment-layers.")
     parser.add_argument("--verbose", action="store_true", help="One line per step.")
     parser.add_argument("pretrain_model", type=str, help="The pre-trained model directory.")
     parser.add_argument("train_dir", type=str, help="The data directory of the training set.")
@@ -70,7 +75,8 @@ def main(argv=None):
     history = head_train.train_head(trainer, args.train_dir, args.train_spklist, args.valid_dir, args.valid_spklist,
                                     args.finetune_model, weights=weights, seed=seed, keep_head=args.keep_head,
                                     precision=args.precision or None, log=print if args.verbose else None,
-                                    segment_layers=args.segment_layers or args.frame_layers, frame_layers=args.frame_layers)
+                                    segment_layers=args.segment_layers or args.frame_layers or args.conv_layers,
+                                    frame_layers=args.frame_layers or args.conv_layers, conv_layers=args.conv_layers)
     for epoch, step, loss, eer, lr in history:
         print("epoch %d step %d loss %f eer %f lr %.8f" % (epoch, step, loss, eer, lr))
     trainer.close()
