@@ -437,6 +437,17 @@ def test_separable_toy_set_is_learned():
     feats, offsets, labels = toy_segments(2, 8, 4, LENGTHS["tdnn"], noise=0.5)
     ct = conv_train.ConvTrainer(Params(**params), weights, 8, device=0, seed=0)
     dev = torch.from_numpy(feats).cuda()
-    losses = [ct.step(dev, offsets, labels, 0.1, global_step=t).loss for t in range(20)]
+    # the same two steps with a `mark` callback on a twin: the same bits, and every stage named once, in the documented order
+    twin, seen, losses = conv_train.ConvTrainer(Params(**params), weights, 8, device=0, seed=0), [], []
+    for t in range(2):
+        losses.append(ct.step(dev, offsets, labels, 0.1, global_step=t).loss)
+        assert twin.step(dev, offsets, labels, 0.1, global_step=t, mark=seen.append).loss == losses[-1]
+        a, b = ct.variables(), twin.variables()
+        assert list(a) == list(b) and all(a[k].tobytes() == b[k].tobytes() for k in a)
+    n = len(ct.frame_layers)
+    assert seen == 2 * (["start"] + ["frame_forward/%d" % i for i in range(n)]
+                        + ["frame_forward", "pool_forward", "segment_forward", "head", "segment_backward", "pool_backward"]
+                        + ["frame_backward/%d" % i for i in range(n - 1, -1, -1)] + ["frame_backward", "optimizer"])
+    losses += [ct.step(dev, offsets, labels, 0.1, global_step=t).loss for t in range(2, 20)]
     print("separable toy set: mean loss %.4f -> %.4f" % (losses[0], losses[-1]))
     assert losses[-1] < losses[0]

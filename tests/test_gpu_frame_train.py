@@ -292,6 +292,17 @@ def test_separable_toy_set_is_learned():
     frames, offsets, labels = pc.separable_frames(2, 8, 4, CHANNELS, LENGTHS)
     ft = frame_train.FrameTrainer(Params(**params), weights, 8, device=0, seed=0)
     dev = torch.from_numpy(frames).cuda()
-    losses = [ft.step(dev, offsets, labels, 0.1, global_step=t).loss for t in range(20)]
+    # the same two steps with a `mark` callback on a twin: the same bits, and every stage named once, in the documented order
+    twin, seen, losses = frame_train.FrameTrainer(Params(**params), weights, 8, device=0, seed=0), [], []
+    for t in range(2):
+        losses.append(ft.step(dev, offsets, labels, 0.1, global_step=t).loss)
+        assert twin.step(dev, offsets, labels, 0.1, global_step=t, mark=seen.append).loss == losses[-1]
+        a, b = ft.variables(), twin.variables()
+        assert list(a) == list(b) and all(a[k].tobytes() == b[k].tobytes() for k in a)
+    n = len(ft.frame_layers)
+    assert seen == 2 * (["start"] + ["frame_forward/%d" % i for i in range(n)]
+                        + ["frame_forward", "pool_forward", "segment_forward", "head", "segment_backward", "pool_backward"]
+                        + ["frame_backward/%d" % i for i in range(n - 1, -1, -1)] + ["frame_backward", "optimizer"])
+    losses += [ft.step(dev, offsets, labels, 0.1, global_step=t).loss for t in range(2, 20)]
     print("separable toy set: mean loss %.4f -> %.4f" % (losses[0], losses[-1]))
     assert losses[-1] < losses[0]

@@ -9,7 +9,8 @@ dense layer, which is the same operator with W = 1; then batch norm, then the ac
 W-tap layer with n - (W - 1) frames; out_offsets() keeps the packed offsets.
     TDNN:           conv 5, conv 5, conv 7, dense 4, 5                                          (context 14)
     extended TDNN:  conv 5, dense, conv 5, dense, conv 7, dense, conv 9, dense 8, 9, 10         (context 22)
-Behind them frame_train.StatPool and an unchanged tail_train.TailTrainer.  A step is: the frame layers forward, StatPool.forward,
+Behind them frame_train.StatPool and an unchanged tail_train.TailTrainer: ConvTrainer is a frame_train.StackedTrainer whose frame
+layers are TConvLayers (a tail_train.Layer on xv_tconv_*), and takes its step from there.  A step is: the frame layers forward, StatPool.forward,
 the two segment layers, one xv_loss_classifier_grad, the segment layers backward, StatPool.backward, the frame layers backward
 in reverse (no gx for the first), one xv_opt_step per tensor.  Trained: every kernel (the convolutions' in the shape the
 checkpoint had, rank 4 or 3) and bias, gamma and beta of every batch norm, the head.  NOT trained: the moving statistics.
@@ -27,7 +28,6 @@ import numpy as np
 from . import _lib
 from . import frame_train
 from . import head_train
-from . import losses
 from . import tail_train
 
 StepResult = head_train.StepResult
@@ -35,7 +35,6 @@ ConvSpec = collections.namedtuple("ConvSpec", "kernel bias bn act taps")      # 
 
 # network_type -> (variable scope, the kernel widths of the frame-level layers in forward order)
 _NETS = {"tdnn": ("tdnn", (5, 5, 7, 1, 1)), "extended_tdnn": ("etdnn", (5, 1, 5, 1, 7, 1, 9, 1, 1, 1))}
-_BN = tail_train._BN
 _p = tail_train._p
 
 
@@ -66,22 +65,13 @@ def context(params):
 
 
 def trained_names(params):
-    """The TensorFlow names of every variable ConvTrainer updates: the frame layers first, then tail_train.trained_names."""
-    out = []
-    for spec in frame_variables(params):
-        out += [spec.kernel, spec.bias, spec.bn + "/gamma", spec.bn + "/beta"]
-    return out + tail_train.trained_names(params)
+    """The TensorFlow names of every variable ConvTrainer updates (frame_train.stacked_names of frame_variables)."""
+    return frame_train.stacked_names(frame_variables(params), params)
 
 
 def l2_assignment(params):
-    """name -> the l2 factor of its update: weight_l2_regularizer on every kernel, the convolutions' included,
-    optimizer_config's rule on the head's kernel, 0 on every bias, gamma and beta."""
-    reg = float(_dict(params).get("weight_l2_regularizer", 0.0))
-    out = dict.fromkeys(trained_names(params), 0.0)
-    out.update(tail_train.l2_assignment(params))
-    for spec in frame_variables(params):
-        out[spec.kernel] = reg
-    return out
+    """name -> the l2 factor of its update, the convolutions' kernels included (frame_train.stacked_l2 of frame_variables)."""
+    return frame_train.stacked_l2(frame_variables(params), params)
 
 
 def out_offsets(offsets, taps):
@@ -113,50 +103,18 @@ def rows_to_kernel(rows, shape):
     return np.ascontiguousarray(rows.T).reshape(shape).astype(np.float32)
 
 
-class TConvLayer(object):
-    """One frame-level layer's parameters, gradients and optimizer slots on the device.  w holds the rows [N, ldw] of the
-    weights (kernel_to_rows; ldw = W C rounded up to 4, the padding stays zero)."""
+class TConvLayer(tail_train.Layer):
+    """One frame-level layer on packed utterances: w holds kernel_to_rows of the TensorFlow kernel, whose shape is kept."""
 
     def __init__(self, kernel, bias, bn, act, device=0, num_slots=0):
-        torch = losses._need_device()
         rows, self.taps, self.channels = kernel_to_rows(kernel)
         self.shape = tuple(np.shape(kernel))
-        self.out_dim, self.in_dim = int(rows.shape[0]), int(rows.shape[1])
-        if tuple(np.shape(bias)) != (self.out_dim,):
-            raise ValueError("bias [%d] expected, got %s" % (self.out_dim, np.shape(bias)))
-        self.ldw = (self.in_dim + 3) // 4 * 4
-        self.act, self.device = int(act), int(device)
-        self._torch, self._lib = torch, _lib.load()
-        dev = "cuda:%d" % self.device
-        with torch.cuda.device(self.device):
-            self.w = torch.zeros((self.out_dim, self.ldw), dtype=torch.float32, device=dev)
-            self.w[:, :self.in_dim] = torch.from_numpy(rows).to(dev)
-            self.b = losses._f32(bias, self.device, torch)
-            self.bn = None
-            if bn is not None:
-                if any(tuple(np.shape(v)) != (self.out_dim,) for v in bn):
-                    raise ValueError("batch norm: four vectors of %d elements expected" % self.out_dim)
-                self.bn = [losses._f32(v, self.device, torch) for v in bn]         # gamma, beta, moving_mean, moving_variance
-            self.gw = torch.zeros_like(self.w)                                     # the padding columns stay zero
-            self.gb = torch.zeros_like(self.b)
-            self.ggamma = None if self.bn is None else torch.zeros_like(self.b)
-            self.gbeta = None if self.bn is None else torch.zeros_like(self.b)
-            self.slots = {name: [torch.zeros_like(t) for _ in range(num_slots)] for name, t, _ in self.trained()}
-        self._x = self._z = self._off = self._ws = None
+        if tuple(np.shape(bias)) != (int(rows.shape[0]),):
+            raise ValueError("bias [%d] expected, got %s" % (int(rows.shape[0]), np.shape(bias)))
+        tail_train.Layer.__init__(self, rows, bias, bn, act, device, num_slots)
+        self._off = None
         self._sizes = (0, 0, 0)
         self._covers = False
-
-    def trained(self):
-        """[(name, parameter, gradient)] in the order the optimizer takes them."""
-        out = [("kernel", self.w, self.gw), ("bias", self.b, self.gb)]
-        if self.bn is not None:
-            out += [("gamma", self.bn[0], self.ggamma), ("beta", self.bn[1], self.gbeta)]
-        return out
-
-    def _workspace(self, need, device):
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self._torch.empty(max(need, 16), dtype=self._torch.uint8, device=device)
-        return self._ws
 
     def forward(self, x, offsets):
         """x [rows, C] on the device, float32 contiguous; offsets [B + 1] host integers of its rows -> (y [total_out, N] packed
@@ -197,10 +155,8 @@ class TConvLayer(object):
         if tuple(gy.shape) != (total_out, self.out_dim) or not gy.is_contiguous():
             raise ValueError("gy: expected a contiguous [%d, %d], got shape %s" % (total_out, self.out_dim, tuple(gy.shape)))
         with torch.cuda.device(self.device):
-            if total_out == 0:                          # the gradient of an empty sum
-                for _, _, g in self.trained():
-                    g.zero_()
-                return torch.zeros((int(x.shape[0]), self.channels), dtype=torch.float32, device=x.device) if want_gx else None
+            if total_out == 0:
+                return self._empty_batch(int(x.shape[0]), self.channels, want_gx)
             gx = None
             if want_gx:
                 make = torch.empty if self._covers else torch.zeros           # every row has an owner: every element is written
@@ -221,111 +177,36 @@ class TConvLayer(object):
         return rows_to_kernel(self.w[:, :self.in_dim].cpu().numpy(), self.shape)
 
 
-class ConvTrainer(object):
-    """Every frame-level layer, statistics pooling, and a tail_train.TailTrainer (the two segment-level layers and the head)
-    behind them, all built from the checkpoint's variables."""
+class ConvTrainer(frame_train.StackedTrainer):
+    """Every frame-level layer on the packed features: TConvLayers, each handing its output offsets to the next.
+    forward(feats_dev, offsets), step(feats_dev, offsets, labels, learning_rate, global_step=0, mark=None); offsets are host
+    integers."""
+
+    _check, _specs, _l2 = staticmethod(check_supported), staticmethod(frame_variables), staticmethod(l2_assignment)
+    _CHAIN = "%s takes %d channels, %s gives %d"
+    _INPUT = ("feats_dev", "")
 
     def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None):
-        check_supported(params)
-        self.params = params
-        self.frame_specs = frame_variables(params)
-        self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias)
-        num_slots = len(self.tail.layers[0].slots["kernel"])
-        self.frame_layers = []
-        for spec in self.frame_specs:
-            missing = [k for k in (spec.kernel, spec.bias) + tuple(spec.bn + "/" + s for s in _BN) if k not in weights]
-            if missing:
-                raise KeyError("the checkpoint lacks %s" % ", ".join(missing))
-            layer = TConvLayer(weights[spec.kernel], weights[spec.bias], [weights[spec.bn + "/" + s] for s in _BN], spec.act, device,
-                               num_slots)
-            if layer.taps != spec.taps:
-                raise ValueError("%s: a kernel of %d taps expected, got shape %s" % (spec.kernel, spec.taps, layer.shape))
-            self.frame_layers.append(layer)
-        for a, b, sa, sb in zip(self.frame_layers[:-1], self.frame_layers[1:], self.frame_specs[:-1], self.frame_specs[1:]):
-            if b.channels != a.out_dim:
-                raise ValueError("%s takes %d channels, %s gives %d" % (sb.kernel, b.channels, sa.kernel, a.out_dim))
-        self.in_dim, self.channels = self.frame_layers[0].channels, self.frame_layers[-1].out_dim
+        frame_train.StackedTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias)
         self.context = sum(layer.taps - 1 for layer in self.frame_layers)
-        if self.tail.pool_dim != 2 * self.channels:
-            raise ValueError("%s has %d rows, statistics pooling of %d channels gives %d" % (self.tail.specs[0].kernel, self.tail.pool_dim,
-                                                                                             self.channels, 2 * self.channels))
-        self.specs = self.frame_specs + tuple(self.tail.specs)
-        self.layers = self.frame_layers + list(self.tail.layers)
-        self.head = self.tail.head
-        self.embed_dim = self.tail.embed_dim
-        self.device = int(device)
-        self.pool = frame_train.StatPool(self.channels, device)
-        self.l2 = l2_assignment(params)
-        torch = losses._need_device()
-        self._torch, self._lib = torch, _lib.load()
-        largest = max([layer.w.numel() for layer in self.layers] + [self.head.head.raw_rows.numel()])
-        if self.tail._ws.numel() < int(self._lib.xv_opt_workspace(largest)):
-            with torch.cuda.device(self.device):
-                self.tail._ws = torch.empty(int(self._lib.xv_opt_workspace(largest)), dtype=torch.uint8, device=self.tail._ws.device)
-        self.num_steps = 0                                                   # adam's t, shared by every tensor
 
-    def tensors(self):
-        """[(TensorFlow name, parameter, gradient, slots)] of everything trained, in the order of trained_names()."""
-        out = []
-        for spec, layer in zip(self.frame_specs, self.frame_layers):
-            names = {"kernel": spec.kernel, "bias": spec.bias, "gamma": spec.bn + "/gamma", "beta": spec.bn + "/beta"}
-            out += [(names[k], w, g, layer.slots[k]) for k, w, g in layer.trained()]
-        return out + self.tail.tensors()
+    def _layer(self, spec, kernel, bias, bn, device, num_slots):
+        layer = TConvLayer(kernel, bias, bn, spec.act, device, num_slots)
+        if layer.taps != spec.taps:
+            raise ValueError("%s: a kernel of %d taps expected, got shape %s" % (spec.kernel, spec.taps, layer.shape))
+        return layer
 
-    def _feats(self, feats_dev):
-        torch = self._torch
-        if not torch.is_tensor(feats_dev) or not feats_dev.is_cuda:
-            raise ValueError("feats_dev must be a device tensor")
-        if feats_dev.dim() != 2 or int(feats_dev.shape[1]) != self.in_dim or feats_dev.dtype != torch.float32:
-            raise ValueError("feats_dev: expected float32 [rows, %d], got %s" % (self.in_dim, tuple(feats_dev.shape)))
-        return feats_dev.contiguous()
+    def _width(self, layer):
+        return layer.channels
 
-    def _forward(self, feats_dev, offsets):
-        x, off = self._feats(feats_dev), np.ascontiguousarray(offsets, dtype=np.int64)
+    def _offsets(self, offsets):
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
         if off.size > 1 and np.any(np.diff(off) <= self.context):
             raise ValueError("every utterance needs more than the %d frames of context" % self.context)
-        for layer in self.frame_layers:
+        return off
+
+    def _walk(self, x, off, mark):
+        for i, layer in enumerate(self.frame_layers):
             x, off = layer.forward(x.contiguous(), off)
-        pooled = self.pool.forward(x.contiguous(), off)
-        return self.tail.layers[1].forward(self.tail.layers[0].forward(pooled.contiguous()))
-
-    def forward(self, feats_dev, offsets):
-        """feats_dev [rows, dim] on the device (packed features), offsets [B + 1] host integers of its rows -> the `output`
-        endpoint [B, embed_dim] on the device, with the current weights."""
-        with self._torch.cuda.device(self.device):
-            return self._forward(feats_dev, offsets)
-
-    def step(self, feats_dev, offsets, labels, learning_rate, global_step=0):
-        """One training step on a batch of packed features: forward through the frame layers, the pooling and the segment
-        layers, the head's mean loss at `global_step` and its gradients, backward through all of them, then per tensor l2
-        (kernels only), the clip and the update -> StepResult(mean loss, top-1 accuracy), both of the parameters BEFORE the
-        update."""
-        torch = self._torch
-        h = self.head
-        with torch.cuda.device(self.device):
-            y = self._forward(feats_dev, offsets)
-            out, top1, gx, _, _ = h.head._grad_device(y, labels, global_step, None, True, h._grad_rows, h._grad_bias)
-            n = int(out.shape[1])
-            g = self.tail.layers[1].backward(gx, True)
-            g = self.tail.layers[0].backward(g, True)
-            g = self.pool.backward(g)
-            for i in range(len(self.frame_layers) - 1, -1, -1):
-                g = self.frame_layers[i].backward(g, i > 0)
-            self.num_steps += 1
-            self.tail.num_steps = h.num_steps = self.num_steps
-            for name, w, gw, slots in self.tensors():
-                self.tail._apply(w, gw, slots, learning_rate, self.l2[name])
-            lab = losses._labels_dev(labels, n, out.device, torch)
-            return StepResult(float(out[0].double().mean()) if n else float("nan"),
-                              float((top1 == lab).double().mean()) if n else float("nan"))
-
-    def variables(self):
-        """name -> float32 numpy of every trained variable under its TensorFlow name (kernels in the checkpoint's shapes)."""
-        out = collections.OrderedDict()
-        for spec, layer in zip(self.frame_specs, self.frame_layers):
-            out[spec.kernel] = layer.kernel()
-            out[spec.bias] = layer.b.cpu().numpy().copy()
-            out[spec.bn + "/gamma"] = layer.bn[0].cpu().numpy().copy()
-            out[spec.bn + "/beta"] = layer.bn[1].cpu().numpy().copy()
-        out.update(self.tail.variables())
-        return out
+            mark("frame_forward/%d" % i)
+        return x, off

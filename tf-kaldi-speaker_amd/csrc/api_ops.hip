@@ -466,6 +466,25 @@ int64_t xv_seg_workspace_min(int64_t n, int in_dim, int out_dim) { return seg_wo
 
 namespace {
 
+// what every trained layer's calls check of the batch-norm pointers (all four or none) and the activation; `op` names the caller
+int layer_lines_check(const char* op, const void* gamma, const void* beta, const void* mm, const void* mv, int act) {
+  const int given = (gamma != nullptr) + (beta != nullptr) + (mm != nullptr) + (mv != nullptr);
+  if (given != 0 && given != 4)
+    return fail(nullptr, XV_ERR_INVALID, "%s: batch norm needs gamma, beta, moving_mean and moving_variance, or none of them", op);
+  if (act < XV_SEG_ACT_NONE || act > XV_SEG_ACT_LRELU) return fail(nullptr, XV_ERR_INVALID, "%s: unknown activation %d", op, act);
+  return XV_OK;
+}
+
+// the workspace of a trained layer's call: `need` bytes at a 16-byte aligned address
+int layer_ws_check(const char* op, const void* ws_dev, int64_t ws_bytes, int64_t need) {
+  if (!ws_dev || ws_bytes < need)
+    return fail(nullptr, XV_ERR_WORKSPACE, "%s: workspace of %lld bytes, at least %lld needed", op, (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  if ((reinterpret_cast<uintptr_t>(ws_dev) & 15) != 0)
+    return fail(nullptr, XV_ERR_INVALID, "%s: the workspace must be 16-byte aligned", op);
+  return XV_OK;
+}
+
 // the checks the two calls of a segment-level layer share; `op` names the caller in the message
 int seg_check(const char* op, int64_t n, int in_dim, int out_dim, int64_t ldx, int64_t ldw, const void* gamma, const void* beta,
               const void* mm, const void* mv, int act) {
@@ -473,11 +492,7 @@ int seg_check(const char* op, int64_t n, int in_dim, int out_dim, int64_t ldx, i
     return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: 1 <= in_dim <= 16384, 1 <= out_dim <= 4096, n <= 2^24, got %d, %d, %lld", op, in_dim,
                 out_dim, (long long)n);
   if (n < 0 || ldx < in_dim || ldw < in_dim) return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
-  const int given = (gamma != nullptr) + (beta != nullptr) + (mm != nullptr) + (mv != nullptr);
-  if (given != 0 && given != 4)
-    return fail(nullptr, XV_ERR_INVALID, "%s: batch norm needs gamma, beta, moving_mean and moving_variance, or none of them", op);
-  if (act < XV_SEG_ACT_NONE || act > XV_SEG_ACT_LRELU) return fail(nullptr, XV_ERR_INVALID, "%s: unknown activation %d", op, act);
-  return XV_OK;
+  return layer_lines_check(op, gamma, beta, mm, mv, act);
 }
 
 }  // namespace
@@ -504,17 +519,13 @@ int xv_seg_backward(int device, const float* gy_dev, int64_t ldgy, const float* 
                     void* stream) {
   if (!gy_dev || !x_dev || !z_dev || !w_dev || !gw_dev || !gbias_dev)
     return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: null pointer");
-  const int rc = seg_check("xv_seg_backward", n, in_dim, out_dim, ldx, ldw, gamma_dev, beta_dev, mean_dev, var_dev, act);
+  int rc = seg_check("xv_seg_backward", n, in_dim, out_dim, ldx, ldw, gamma_dev, beta_dev, mean_dev, var_dev, act);
   if (rc != XV_OK) return rc;
   if (gamma_dev && (!ggamma_dev || !gbeta_dev))
     return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: batch norm needs ggamma_dev and gbeta_dev");
   if (ldgy < out_dim || ldz < out_dim || (gx_dev && ldgx < in_dim)) return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: bad dimensions");
   if (n == 0) return XV_OK;
-  if (!ws_dev || ws_bytes < seg_workspace_bytes(n, in_dim, out_dim, 1))
-    return fail(nullptr, XV_ERR_WORKSPACE, "xv_seg_backward: workspace of %lld bytes, at least %lld needed",
-                (long long)(ws_dev ? ws_bytes : 0), (long long)seg_workspace_bytes(n, in_dim, out_dim, 1));
-  if ((reinterpret_cast<uintptr_t>(ws_dev) & 15) != 0)
-    return fail(nullptr, XV_ERR_INVALID, "xv_seg_backward: the workspace must be 16-byte aligned");
+  if ((rc = layer_ws_check("xv_seg_backward", ws_dev, ws_bytes, seg_workspace_bytes(n, in_dim, out_dim, 1))) != XV_OK) return rc;
   return with_device(device, "xv_seg_backward", [&] {
     return launch_seg_backward(gy_dev, ldgy, x_dev, ldx, z_dev, ldz, (int)n, in_dim, w_dev, ldw, out_dim, gamma_dev, beta_dev, mean_dev,
                                var_dev, act, gx_dev, ldgx, gw_dev, gbias_dev, ggamma_dev, gbeta_dev, ws_dev, ws_bytes,
@@ -590,20 +601,7 @@ int tconv_check(const char* op, int taps, int channels, int out_dim, int64_t bat
                 "%lld, %lld", op, taps, channels, out_dim, (long long)batch, (long long)total_in, (long long)total_out);
   if (batch < 0 || total_in < 0 || total_out < 0 || ldx < channels || ldw < (int64_t)taps * channels)
     return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
-  const int given = (gamma != nullptr) + (beta != nullptr) + (mm != nullptr) + (mv != nullptr);
-  if (given != 0 && given != 4)
-    return fail(nullptr, XV_ERR_INVALID, "%s: batch norm needs gamma, beta, moving_mean and moving_variance, or none of them", op);
-  if (act < XV_SEG_ACT_NONE || act > XV_SEG_ACT_LRELU) return fail(nullptr, XV_ERR_INVALID, "%s: unknown activation %d", op, act);
-  return XV_OK;
-}
-
-int tconv_ws_check(const char* op, const void* ws_dev, int64_t ws_bytes, int64_t need) {
-  if (!ws_dev || ws_bytes < need)
-    return fail(nullptr, XV_ERR_WORKSPACE, "%s: workspace of %lld bytes, at least %lld needed", op, (long long)(ws_dev ? ws_bytes : 0),
-                (long long)need);
-  if ((reinterpret_cast<uintptr_t>(ws_dev) & 15) != 0)
-    return fail(nullptr, XV_ERR_INVALID, "%s: the workspace must be 16-byte aligned", op);
-  return XV_OK;
+  return layer_lines_check(op, gamma, beta, mm, mv, act);
 }
 
 }  // namespace
@@ -619,7 +617,7 @@ int xv_tconv_forward(int device, const float* x_dev, int64_t ldx, int channels, 
   if (rc != XV_OK) return rc;
   if (ldz < out_dim || ldy < out_dim) return fail(nullptr, XV_ERR_INVALID, "xv_tconv_forward: bad dimensions");
   if (batch == 0 || total_out == 0) return XV_OK;
-  if ((rc = tconv_ws_check("xv_tconv_forward", ws_dev, ws_bytes, tconv_forward_workspace_bytes(batch, total_out))) != XV_OK) return rc;
+  if ((rc = layer_ws_check("xv_tconv_forward", ws_dev, ws_bytes, tconv_forward_workspace_bytes(batch, total_out))) != XV_OK) return rc;
   return with_device(device, "xv_tconv_forward", [&] {
     return launch_tconv_forward(x_dev, ldx, channels, taps, offsets_dev, batch, total_in, total_out, w_dev, ldw, out_dim, bias_dev,
                                 gamma_dev, beta_dev, mean_dev, var_dev, act, z_dev, ldz, y_dev, ldy, ws_dev, to_stream(stream));
@@ -642,7 +640,7 @@ int xv_tconv_backward(int device, const float* gy_dev, int64_t ldgy, const float
     return fail(nullptr, XV_ERR_INVALID, "xv_tconv_backward: bad dimensions");
   if (batch == 0 || total_out == 0) return XV_OK;
   if (total_in < total_out) return fail(nullptr, XV_ERR_INVALID, "xv_tconv_backward: total_in below total_out");
-  if ((rc = tconv_ws_check("xv_tconv_backward", ws_dev, ws_bytes,
+  if ((rc = layer_ws_check("xv_tconv_backward", ws_dev, ws_bytes,
                            tconv_workspace_bytes(batch, total_in, total_out, taps, channels, out_dim))) != XV_OK)
     return rc;
   return with_device(device, "xv_tconv_backward", [&] {

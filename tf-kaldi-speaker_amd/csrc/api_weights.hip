@@ -1,5 +1,6 @@
 // C ABI of libxvec_hip.so, the weights: xv_finalize chooses each layer's kernel and number format, folds the batch
 // normalisation and packs the weights into the layouts the gfx950 kernels read; the fp16 range flags.
+#include "layer_lines.h"
 #include "xv_model.h"
 
 using namespace xv;
@@ -7,7 +8,7 @@ using namespace xv::api;
 
 namespace {
 
-constexpr double kBnEps = 1e-3;        // tf.layers.batch_normalization default epsilon
+using lines::kBnEps;                   // the one epsilon of the training layers too
 
 uint16_t f32_to_bf16_rn(float f) {   // round to nearest even; inputs are finite weights
   uint32_t u;

@@ -9,16 +9,12 @@
 // atomics anywhere:
 //  * seg_gemm_kernel<EPI_FWD>: z = x . w^T + b, then h and y in the epilogue.  The chain of z_ij runs over k ascending from 0
 //    (a function of K alone), the bias is added last: z = float(acc + b_j).
-//  * The batch-norm line, in forward and backward the SAME device function (seg_h) on the stored float z, every step rounded to
-//    float32 on its own:  r_j = float(1 / sqrt(double(mv_j) + 1e-3)),  s_j = gamma_j * r_j,  d = z - mm_j,
-//    h = fma(s_j, d, beta_j) (one rounding).  Without batch norm h = z.  y = h (none), h > 0 ? h : 0 (ReLU),
-//    h > 0 ? h : float(0.2) * h (leaky ReLU).
+//  * The batch-norm line and the activation, in forward and backward the SAME device functions on the stored float z, are those
+//    of csrc/layer_lines.h (bn_r, bn_h, act_y, act_grad), shared with csrc/tconv_grad.hip.
 //  * backward, per PANEL of P rows (P a multiple of 64, at most 1024, as many as the workspace holds), in ascending row order:
-//      - seg_mask_kernel, one workgroup per 32 columns: a = gy act'(h) (h from z by seg_h, so the mask is the forward's),
-//        gz = a * s_j (gz = a without batch norm), written as gz [P, ldg] and gz^T [N, P]; lane l of the wave that owns column j
-//        adds the rows i = l (mod 64) of the WHOLE batch in ascending order to three doubles, a (gbeta), double(a) *
-//        (double(r_j) * (double(z) - double(mm_j))) (ggamma) and gz (gbias), which live in the workspace between the panels; a
-//        fixed xor butterfly over the 64 lanes after the last panel, rounded once;
+//      - seg_mask_kernel, one workgroup per 32 columns: a = gy act'(h) by act_grad, gz = a * s_j, written as gz
+//        [P, ldg] and gz^T [N, P]; the three double lane sums run over the rows of the WHOLE batch in ascending order and live
+//        in the workspace between the panels; the butterfly over the 64 lanes comes after the last panel, rounded once;
 //      - seg_gemm_kernel<EPI_OUT>: gx_panel = gz . (w^T)^T over a transposed copy of w, K = N;
 //      - seg_gemm_kernel<EPI_ACC>: gw += gz^T . (x_panel^T)^T, K = P.  The accumulators START from what the earlier panels left
 //        in gw, so the sum over the rows is ONE fmaf chain in ascending row index whatever P is (the scheme of
@@ -27,19 +23,11 @@
 // memory this call did not write.  Row i of z, y and gx uses row i and the parameters only.
 //
 // Error bound (u = 2^-24; checked per element in tests/test_gpu_seg_grad.py, restated in ref_seg_grad.bounds).  |.| of the
-// float64 oracle's values; t = 2^-53 (n + 64) covers the double sums before their one rounding:
+// float64 oracle's values.  Bh, By, Ba, Bg and the bounds of gbeta, ggamma and gbias are derived in csrc/layer_lines.h from this Bz:
 //   z_ij:      Bz = (K + 2) u (sum_k |x_ik w_jk| + |b_j|)                     (fmaf chain of length K, then the bias)
-//   h_ij:      Bh = 1.01 |gamma_j r_j| Bz + 4 u |gamma_j r_j (z_ij - mm_j)| + u |h_ij|     (r, s and d round once each: 3 u, the
-//              fourth u and the 1.01 cover the products of two errors; the fma rounds once).  Without batch norm Bh = Bz.
-//   y_ij:      By = Bh + 2 u |y_ij|                     (the rounding of 0.2 and of the product; the sign of h is the oracle's
-//              wherever |h| > Bh, which the test cases guarantee with a factor of 64, or where h = 0 exactly in both)
-//   a_ij:      Ba = 2 u |a_ij|                          (leaky ReLU; 0 for ReLU and none, where a is gy or 0 exactly)
-//   gz_ij:     Bg = |gamma_j r_j| Ba + 3.01 u |gz_ij|   (s carries 2 u, the product u); Bg = Ba without batch norm
-//   gbeta_j:   sum_i Ba + (u + t) sum_i |a_ij|
-//   ggamma_j:  sum_i (Ba |r_j (z_ij - mm_j)| + |a_ij r_j| Bz) + (2 u + t) sum_i |a_ij r_j (z_ij - mm_j)|   (r rounded, one rounding)
-//   gbias_j:   sum_i Bg + (u + t) sum_i |gz_ij|
 //   gw_jk:     sum_i Bg |x_ik| + (n + 32) u sum_i |gz_ij x_ik|               (fmaf chain of length n, padded to 32)
 //   gx_ik:     sum_j Bg |w_jk| + (N + 2) u sum_j |gz_ij w_jk|                (fmaf chain of length N)
+#include "layer_lines.h"
 #include "nt_gemm.h"
 
 namespace xv {
@@ -51,17 +39,8 @@ namespace {
 
 constexpr int kSegMaxPanel = 1024;
 constexpr int kSegPanelStep = 64;             // a panel is a whole number of 64-row chunks of seg_mask_kernel (and of K steps of gw)
-constexpr double kSegBnEps = 1e-3;            // kBnEps of csrc/api_weights.hip
 
 enum { EPI_FWD = 0, EPI_OUT = 1, EPI_ACC = 2 };
-
-// the batch-norm line; contraction is ruled out by spelling every rounding
-__device__ __forceinline__ float seg_r(float mv) { return (float)(1.0 / sqrt((double)mv + kSegBnEps)); }
-__device__ __forceinline__ float seg_h(float z, float s, float mm, float beta) { return fmaf(s, __fsub_rn(z, mm), beta); }
-__device__ __forceinline__ float seg_act(float h, int act) {
-  if (act == XV_SEG_ACT_NONE) return h;
-  return h > 0.f ? h : (act == XV_SEG_ACT_RELU ? 0.f : __fmul_rn(0.2f, h));
-}
 
 struct SegGemmArgs {
   const float* A; int64_t lda; int M;         // [M, K]
@@ -101,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void seg_gemm_kernel(SegGemmArgs p) {
   if (EPI == EPI_FWD) {
     bj = p.bias[gj];
     if (p.gamma) {
-      s = __fmul_rn(p.gamma[gj], seg_r(p.mv[gj]));
+      s = __fmul_rn(p.gamma[gj], lines::bn_r(p.mv[gj]));
       mm = p.mm[gj];
       beta = p.beta[gj];
     }
@@ -112,9 +91,9 @@ __global__ __launch_bounds__(256, 2) void seg_gemm_kernel(SegGemmArgs p) {
     if (gi >= p.M) continue;
     if (EPI == EPI_FWD) {
       const float z = __fadd_rn(acc[0][0][e], bj);
-      const float h = p.gamma ? seg_h(z, s, mm, beta) : z;
+      const float h = p.gamma ? lines::bn_h(z, s, mm, beta) : z;
       p.z[(int64_t)gi * p.ldz + gj] = z;
-      p.y[(int64_t)gi * p.ldy + gj] = seg_act(h, p.act);
+      p.y[(int64_t)gi * p.ldy + gj] = lines::act_y(h, p.act);
     } else {
       p.out[(int64_t)gi * p.ldo + gj] = acc[0][0][e];
     }
@@ -142,14 +121,9 @@ struct SegMaskArgs {
   float *gbeta, *ggamma, *gbias;              // written after the last panel (gbeta, ggamma: with batch norm only)
 };
 
-__device__ __forceinline__ double seg_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 constexpr int kMaskCols = 32;                 // columns per workgroup of seg_mask_kernel, 8 per wave
 
+// the twin of tc_mask_kernel (csrc/tconv_grad.hip); csrc/layer_lines.h says what they share and why the two bodies stay apart
 __global__ __launch_bounds__(256) void seg_mask_kernel(SegMaskArgs p) {
   constexpr int CW = kMaskCols / 4;
   __shared__ float ta[64][kMaskCols + 1], tz[64][kMaskCols + 1];
@@ -162,7 +136,7 @@ __global__ __launch_bounds__(256) void seg_mask_kernel(SegMaskArgs p) {
   const bool jok = jc < p.N;
   float s1 = 1.f, mm1 = 0.f, beta1 = 0.f;
   if (bn && jok) {
-    s1 = __fmul_rn(p.gamma[jc], seg_r(p.mv[jc]));
+    s1 = __fmul_rn(p.gamma[jc], lines::bn_r(p.mv[jc]));
     mm1 = p.mm[jc];
     beta1 = p.beta[jc];
   }
@@ -176,7 +150,7 @@ __global__ __launch_bounds__(256) void seg_mask_kernel(SegMaskArgs p) {
     sa[c] = sg[c] = sz[c] = 0.0;
     if (j < p.N) {
       if (bn) {
-        r2[c] = seg_r(p.mv[j]);
+        r2[c] = lines::bn_r(p.mv[j]);
         s2[c] = __fmul_rn(p.gamma[j], r2[c]);
         mm2[c] = p.mm[j];
       }
@@ -193,9 +167,9 @@ __global__ __launch_bounds__(256) void seg_mask_kernel(SegMaskArgs p) {
       float a = 0.f, z = 0.f;
       if (i < p.rows && jok) {
         z = p.z[(int64_t)i * p.ldz + jc];
-        const float h = bn ? seg_h(z, s1, mm1, beta1) : z;
+        const float h = bn ? lines::bn_h(z, s1, mm1, beta1) : z;
         const float g = p.gy[(int64_t)i * p.ldgy + jc];
-        a = p.act == XV_SEG_ACT_NONE ? g : (h > 0.f ? g : (p.act == XV_SEG_ACT_RELU ? 0.f : __fmul_rn(0.2f, g)));
+        a = lines::act_grad(g, h, p.act);
         p.gz[(int64_t)i * p.ldg + jc] = bn ? __fmul_rn(a, s1) : a;
       }
       ta[rl][c1] = a;
@@ -229,7 +203,7 @@ __global__ __launch_bounds__(256) void seg_mask_kernel(SegMaskArgs p) {
       p.part[((int64_t)2 * p.N + j) * 64 + lane] = sz[c];
       continue;
     }
-    const double a = seg_wave_sum_f64(sa[c]), g = seg_wave_sum_f64(sg[c]), z = seg_wave_sum_f64(sz[c]);
+    const double a = lines::wave_sum_f64(sa[c]), g = lines::wave_sum_f64(sg[c]), z = lines::wave_sum_f64(sz[c]);
     if (lane == 0) {
       if (bn) {
         p.gbeta[j] = (float)a;

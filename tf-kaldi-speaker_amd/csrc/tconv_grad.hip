@@ -11,9 +11,9 @@
 // along the reduction, read from LDS as one 16-byte word, and the reduction along the rows, read as four words):
 //  * tc_scan_kernel, tc_map_kernel: out_off[b] = sum_{a < b} max(n_in_a - (W - 1), 0) on the device, then for every output row
 //    its first input row, and for every owned input row (its index in its utterance, out_off, n_out, its absolute row).
-//  * tc_gemm_kernel<TC_FWD>: z = im2col(x) . w^T + b, then h and y in the epilogue by the lines of csrc/seg_grad.hip (seg_r,
-//    seg_h, seg_act restated here).  The chain of z runs over k ascending from 0, a function of W C alone; the bias comes last.
-//  * tc_mask_kernel: a = gy act'(h) (h from the stored z by the forward's own instructions), gz = a s_j, written once as gz
+//  * tc_gemm_kernel<TC_FWD>: z = im2col(x) . w^T + b, then h and y in the epilogue by the lines of csrc/layer_lines.h (bn_r,
+//    bn_h, act_y).  The chain of z runs over k ascending from 0, a function of W C alone; the bias comes last.
+//  * tc_mask_kernel: a = gy act'(h) by act_grad (h from the stored z by bn_h, the forward's), gz = a s_j, written once as gz
 //    [total_out, round4(N)].  The rows are cut into R slices of `rows_per_slice` rows (tc_slices: a function of total_out alone);
 //    within a slice lane l of the wave that owns column j adds the rows i = l (mod 64) in ascending order to three doubles (a,
 //    a r (z - mm), gz), a fixed xor butterfly over the 64 lanes closes the slice; tc_colsum_kernel adds the R slice sums in
@@ -34,11 +34,11 @@
 // Error bound (u = 2^-24; checked per element in tests/test_gpu_tconv.py, restated in ref_tconv.bounds).  |.| of the float64
 // oracle's values; n = total output rows, X = the im2col view of x, K = W C; t = 2^-53 (n + 64) covers the double sums:
 //   z_ij:      Bz = (K + 2) u (sum_k |X_ik w_jk| + |b_j|)                     (fmaf chain of length K, then the bias)
-//   h, y, a, gz, gbeta, ggamma, gbias: the lines of csrc/seg_grad.hip with this Bz (the double sums of any order of n terms
-//              stay within t)
+//   h, y, a, gz, gbeta, ggamma, gbias: the bounds of csrc/layer_lines.h with this Bz
 //   gw_jk:     sum_i Bg |X_ik| + (n + 64) u sum_i |gz_ij X_ik|               (S chains of at most n / S + 32 steps, padded to 32,
 //              then S - 1 <= 31 additions)
 //   gx_sc:     sum_{tau, j} Bg |w_j,tau C + c| + (W (N + 3) + 2) u sum_{tau, j} |gz_{s - tau, j} w_j,tau C + c|
+#include "layer_lines.h"
 #include "nt_gemm.h"
 
 namespace xv {
@@ -49,7 +49,6 @@ using ntg::up;
 
 namespace {
 
-constexpr double kTcBnEps = 1e-3;             // kBnEps of csrc/api_weights.hip
 constexpr int kTcTile = 64;
 constexpr int kTcBK = 32;
 constexpr int kTcLdRow = kTcBK + 4;           // operand tile [64 rows][32 k + 4]
@@ -60,14 +59,6 @@ constexpr int kTcMaxSplit = 32;
 constexpr int kTcMaxSlices = 64;
 
 enum { TC_FWD = 0, TC_GW = 1, TC_GX = 2 };
-
-// the batch-norm line of csrc/seg_grad.hip; contraction is ruled out by spelling every rounding
-__device__ __forceinline__ float tc_r(float mv) { return (float)(1.0 / sqrt((double)mv + kTcBnEps)); }
-__device__ __forceinline__ float tc_h(float z, float s, float mm, float beta) { return fmaf(s, __fsub_rn(z, mm), beta); }
-__device__ __forceinline__ float tc_act(float h, int act) {
-  if (act == XV_SEG_ACT_NONE) return h;
-  return h > 0.f ? h : (act == XV_SEG_ACT_RELU ? 0.f : __fmul_rn(0.2f, h));
-}
 
 // ---------------------------------------------------------------------------------------------- offsets and row maps
 // out_off [batch + 1]: one workgroup walks the utterances in chunks of 256 with a running carry
@@ -322,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void tc_gemm_kernel(TcGemmArgs p) {
     const float bj = p.bias[gj];
     float s = 0.f, mm = 0.f, beta = 0.f;
     if (p.gamma) {
-      s = __fmul_rn(p.gamma[gj], tc_r(p.mv[gj]));
+      s = __fmul_rn(p.gamma[gj], lines::bn_r(p.mv[gj]));
       mm = p.mm[gj];
       beta = p.beta[gj];
     }
@@ -331,9 +322,9 @@ __global__ __launch_bounds__(256, 2) void tc_gemm_kernel(TcGemmArgs p) {
       const int64_t gi = at.row(0, e);
       if (gi >= p.total_out || p.rowmap[gi] < 0) continue;
       const float z = __fadd_rn(acc[e], bj);
-      const float h = p.gamma ? tc_h(z, s, mm, beta) : z;
+      const float h = p.gamma ? lines::bn_h(z, s, mm, beta) : z;
       p.z[gi * p.ldz + gj] = z;
-      p.y[gi * p.ldy + gj] = tc_act(h, p.act);
+      p.y[gi * p.ldy + gj] = lines::act_y(h, p.act);
     }
   } else if (MODE == TC_GW) {
     if (gj >= K) return;
@@ -386,14 +377,9 @@ struct TcMaskArgs {
   double* part;                               // [3][N][slices]
 };
 
-__device__ __forceinline__ double tc_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 constexpr int kTcMaskCols = 32;               // columns per workgroup of tc_mask_kernel, 8 per wave
 
+// the twin of seg_mask_kernel (csrc/seg_grad.hip); csrc/layer_lines.h says what they share and why the two bodies stay apart
 __global__ __launch_bounds__(256) void tc_mask_kernel(TcMaskArgs p) {
   constexpr int CW = kTcMaskCols / 4;
   __shared__ float ta[64][kTcMaskCols + 1], tz[64][kTcMaskCols + 1];
@@ -408,7 +394,7 @@ __global__ __launch_bounds__(256) void tc_mask_kernel(TcMaskArgs p) {
   const bool jok = jc < p.N;
   float s1 = 1.f, mm1 = 0.f, beta1 = 0.f;
   if (bn && jok) {
-    s1 = __fmul_rn(p.gamma[jc], tc_r(p.mv[jc]));
+    s1 = __fmul_rn(p.gamma[jc], lines::bn_r(p.mv[jc]));
     mm1 = p.mm[jc];
     beta1 = p.beta[jc];
   }
@@ -421,7 +407,7 @@ __global__ __launch_bounds__(256) void tc_mask_kernel(TcMaskArgs p) {
     s2[c] = 1.f; r2[c] = 0.f; mm2[c] = 0.f;
     sa[c] = sg[c] = sz[c] = 0.0;
     if (j < p.N && bn) {
-      r2[c] = tc_r(p.mv[j]);
+      r2[c] = lines::bn_r(p.mv[j]);
       s2[c] = __fmul_rn(p.gamma[j], r2[c]);
       mm2[c] = p.mm[j];
     }
@@ -432,9 +418,9 @@ __global__ __launch_bounds__(256) void tc_mask_kernel(TcMaskArgs p) {
       float a = 0.f, z = 0.f;
       if (i < row1 && jok && p.rowmap[i] >= 0) {
         z = p.z[i * p.ldz + jc];
-        const float h = bn ? tc_h(z, s1, mm1, beta1) : z;
+        const float h = bn ? lines::bn_h(z, s1, mm1, beta1) : z;
         const float g = p.gy[i * p.ldgy + jc];
-        a = p.act == XV_SEG_ACT_NONE ? g : (h > 0.f ? g : (p.act == XV_SEG_ACT_RELU ? 0.f : __fmul_rn(0.2f, g)));
+        a = lines::act_grad(g, h, p.act);
         p.gz[i * p.ldg + jc] = bn ? __fmul_rn(a, s1) : a;
       }
       ta[rl][c1] = a;
@@ -460,7 +446,7 @@ __global__ __launch_bounds__(256) void tc_mask_kernel(TcMaskArgs p) {
   for (int c = 0; c < CW; ++c) {
     const int j = j0 + CW * wave + c;
     if (j >= p.N) continue;                                       // uniform over the wave
-    const double a = tc_wave_sum_f64(sa[c]), g = tc_wave_sum_f64(sg[c]), z = tc_wave_sum_f64(sz[c]);
+    const double a = lines::wave_sum_f64(sa[c]), g = lines::wave_sum_f64(sg[c]), z = lines::wave_sum_f64(sz[c]);
     if (lane == 0) {
       p.part[((int64_t)0 * p.N + j) * p.slices + blockIdx.y] = a;
       p.part[((int64_t)1 * p.N + j) * p.slices + blockIdx.y] = g;

@@ -361,8 +361,9 @@ int64_t opt_workspace_bytes(int64_t count);
 hipError_t launch_opt_step(int kind, int nesterov, float* w, const float* g, float* slot0, float* slot1, int64_t count, double lr,
                            double l2, double clip_norm, double momentum, int64_t step, void* ws, hipStream_t s);
 
-// one segment-level layer, dense + inference-mode batch norm + activation, forward and backward (csrc/seg_grad.hip).  gamma, beta,
-// mm, mv: all four or all null.  ws as sized by seg_workspace_bytes (least != 0: the smallest legal size, a panel of 64 rows).
+// one segment-level layer, dense + inference-mode batch norm + activation, forward and backward (csrc/seg_grad.hip; the lines
+// behind the product z, shared with csrc/tconv_grad.hip, and their bounds: csrc/layer_lines.h).  gamma, beta, mm, mv: all four or
+// all null.  ws as sized by seg_workspace_bytes (least != 0: the smallest legal size, a panel of 64 rows).
 int64_t seg_workspace_bytes(int64_t n, int K, int N, int least);
 hipError_t launch_seg_forward(const float* x, int64_t ldx, int n, int K, const float* w, int64_t ldw, int N, const float* bias,
                               const float* gamma, const float* beta, const float* mm, const float* mv, int act, float* z, int64_t ldz,
@@ -373,7 +374,7 @@ hipError_t launch_seg_backward(const float* gy, int64_t ldgy, const float* x, in
                                float* gbeta, void* ws, int64_t ws_bytes, hipStream_t s);
 
 // one frame-level layer on packed utterances, W-tap temporal convolution + inference-mode batch norm + activation, forward and
-// backward (csrc/tconv_grad.hip).  offsets [batch + 1] on the device; total_in and total_out are host bounds that size grids.
+// backward (csrc/tconv_grad.hip, csrc/layer_lines.h).  offsets [batch + 1] on the device; total_in and total_out are host bounds that size grids.
 // ws as sized by tconv_workspace_bytes (the forward uses its first tconv_forward_workspace_bytes only).
 int64_t tconv_workspace_bytes(int64_t batch, int64_t total_in, int64_t total_out, int W, int C, int N);
 int64_t tconv_forward_workspace_bytes(int64_t batch, int64_t total_out);

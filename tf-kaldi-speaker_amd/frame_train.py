@@ -20,8 +20,11 @@ mask is a constant: **parity unpinned**, as for tail_train.py.
 
 `weight_l2_regularizer` goes on every dense kernel, the frame layers' included (model/tdnn.py: every layer takes
 kernel_regularizer); the head keeps the rule of head_train.optimizer_config, the clip is per tensor, Adam's step count is shared.
-frame_variables, frozen_node, trained_names, l2_assignment and check_supported are pure host code; the rest needs a HIP device."""
-import collections
+frame_variables, frozen_node, trained_names, l2_assignment and check_supported are pure host code; the rest needs a HIP device.
+
+StackedTrainer is "frame layers -> StatPool -> TailTrainer" for any kind of frame layer: it builds and checks the chain, and its
+step is tail_train.TailTrainer._step.  FrameTrainer here and conv_train.ConvTrainer say only what their frame layers are;
+stacked_names and stacked_l2 give both modules their trained_names and l2_assignment."""
 import ctypes as C
 
 import numpy as np
@@ -36,7 +39,6 @@ SegSpec = tail_train.SegSpec
 
 # network_type -> (variable scope, the trailing 1-tap frame layers, the frame layer whose activation is the frozen node)
 _FRAME = {"tdnn": ("tdnn", (4, 5), 3), "extended_tdnn": ("etdnn", (8, 9, 10), 7)}
-_BN = tail_train._BN
 
 
 def _dict(params):
@@ -71,23 +73,34 @@ def frozen_node(params):
     return "tdnn%d_relu" % _FRAME[_dict(params).get("network_type", "tdnn")][2]
 
 
-def trained_names(params):
-    """The TensorFlow names of every variable FrameTrainer updates: the frame layers first, then tail_train.trained_names."""
+def stacked_names(frame_specs, params):
+    """The TensorFlow names of every variable a StackedTrainer with these frame layers updates: the frame layers first, then
+    tail_train.trained_names."""
     out = []
-    for spec in frame_variables(params):
+    for spec in frame_specs:
         out += [spec.kernel, spec.bias, spec.bn + "/gamma", spec.bn + "/beta"]
     return out + tail_train.trained_names(params)
 
 
-def l2_assignment(params):
-    """name -> the l2 factor of its update: weight_l2_regularizer on every dense kernel, the frame layers' included,
-    optimizer_config's rule on the head's kernel, 0 on every bias, gamma and beta."""
+def stacked_l2(frame_specs, params):
+    """name -> the l2 factor of its update: weight_l2_regularizer on every kernel, the frame layers' included, optimizer_config's
+    rule on the head's kernel, 0 on every bias, gamma and beta."""
     reg = float(_dict(params).get("weight_l2_regularizer", 0.0))
-    out = dict.fromkeys(trained_names(params), 0.0)
+    out = dict.fromkeys(stacked_names(frame_specs, params), 0.0)
     out.update(tail_train.l2_assignment(params))
-    for spec in frame_variables(params):
+    for spec in frame_specs:
         out[spec.kernel] = reg
     return out
+
+
+def trained_names(params):
+    """The TensorFlow names of every variable FrameTrainer updates (stacked_names of frame_variables)."""
+    return stacked_names(frame_variables(params), params)
+
+
+def l2_assignment(params):
+    """name -> the l2 factor of its update (stacked_l2 of frame_variables)."""
+    return stacked_l2(frame_variables(params), params)
 
 
 _p = tail_train._p
@@ -150,30 +163,26 @@ class StatPool(object):
         return gx
 
 
-class FrameTrainer(object):
-    """The trailing 1-tap frame layers, statistics pooling, and a tail_train.TailTrainer (the two segment-level layers and the
-    head) behind them, all built from the checkpoint's variables."""
+class StackedTrainer(object):
+    """Frame layers -> StatPool -> a tail_train.TailTrainer (the two segment-level layers and the head), all built from the
+    checkpoint's variables, and THE step through them (TailTrainer._step).  A subclass says what its frame layers are: its
+    module's three functions, _layer, _width, _walk, and its own words in _CHAIN and _INPUT."""
+
+    _check = _specs = _l2 = None        # the module's check_supported, frame_variables and l2_assignment, as staticmethods
+    _CHAIN = None       # "%s ... %d ..., %s ... %d": a layer's kernel and input width, the layer before and its output width
+    _INPUT = None       # (the argument's name in the messages, what follows "must be a device tensor")
 
     def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None):
-        check_supported(params)
+        self._check(params)
         self.params = params
-        self.frame_specs = frame_variables(params)
+        self.frame_specs = self._specs(params)
         self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias)
         num_slots = len(self.tail.layers[0].slots["kernel"])
-        self.frame_layers = []
-        for spec in self.frame_specs:
-            missing = [k for k in (spec.kernel, spec.bias) + tuple(spec.bn + "/" + s for s in _BN) if k not in weights]
-            if missing:
-                raise KeyError("the checkpoint lacks %s" % ", ".join(missing))
-            k = np.asarray(weights[spec.kernel], dtype=np.float32)
-            if k.ndim != 2:
-                raise ValueError("%s: a dense kernel [cin, cout] expected, got shape %s" % (spec.kernel, k.shape))
-            self.frame_layers.append(tail_train.SegLayer(k, weights[spec.bias], [weights[spec.bn + "/" + s] for s in _BN], spec.act,
-                                                         device, num_slots))
+        self.frame_layers = [self._layer(spec, *tail_train.layer_weights(spec, weights), device, num_slots) for spec in self.frame_specs]
         for a, b, sa, sb in zip(self.frame_layers[:-1], self.frame_layers[1:], self.frame_specs[:-1], self.frame_specs[1:]):
-            if b.in_dim != a.out_dim:
-                raise ValueError("%s has %d rows, %s %d columns" % (sb.kernel, b.in_dim, sa.kernel, a.out_dim))
-        self.in_dim, self.channels = self.frame_layers[0].in_dim, self.frame_layers[-1].out_dim
+            if self._width(b) != a.out_dim:
+                raise ValueError(self._CHAIN % (sb.kernel, self._width(b), sa.kernel, a.out_dim))
+        self.in_dim, self.channels = self._width(self.frame_layers[0]), self.frame_layers[-1].out_dim
         if self.tail.pool_dim != 2 * self.channels:
             raise ValueError("%s has %d rows, statistics pooling of %d channels gives %d" % (self.tail.specs[0].kernel, self.tail.pool_dim,
                                                                                              self.channels, 2 * self.channels))
@@ -183,74 +192,105 @@ class FrameTrainer(object):
         self.embed_dim = self.tail.embed_dim
         self.device = int(device)
         self.pool = StatPool(self.channels, device)
-        self.l2 = l2_assignment(params)
-        torch = losses._need_device()
-        self._torch, self._lib = torch, _lib.load()
-        largest = max([layer.w.numel() for layer in self.layers] + [self.head.head.raw_rows.numel()])
-        if self.tail._ws.numel() < int(self._lib.xv_opt_workspace(largest)):
-            with torch.cuda.device(self.device):
-                self.tail._ws = torch.empty(int(self._lib.xv_opt_workspace(largest)), dtype=torch.uint8, device=self.tail._ws.device)
+        self.l2 = self._l2(params)
+        self._torch = losses._need_device()
+        self.tail._fit_workspace(self.layers)
         self.num_steps = 0                                                   # adam's t, shared by every tensor
+
+    def _layer(self, spec, kernel, bias, bn, device, num_slots):
+        """The frame layer of `spec` from the checkpoint's kernel, bias and batch-norm vectors."""
+        raise NotImplementedError
+
+    def _width(self, layer):
+        """The columns a row of the layer's input has."""
+        raise NotImplementedError
+
+    def _offsets(self, offsets):
+        """The offsets as _walk takes them, checked as far as the subclass checks them."""
+        return offsets
+
+    def _walk(self, x, offsets, mark):
+        """x through every frame layer, mark("frame_forward/<i>") behind layer i -> (the last layer's rows, their offsets)."""
+        raise NotImplementedError
 
     def tensors(self):
         """[(TensorFlow name, parameter, gradient, slots)] of everything trained, in the order of trained_names()."""
-        out = []
-        for spec, layer in zip(self.frame_specs, self.frame_layers):
-            names = {"kernel": spec.kernel, "bias": spec.bias, "gamma": spec.bn + "/gamma", "beta": spec.bn + "/beta"}
-            out += [(names[k], w, g, layer.slots[k]) for k, w, g in layer.trained()]
-        return out + self.tail.tensors()
+        return tail_train.layer_tensors(self.frame_specs, self.frame_layers) + self.tail.tensors()
 
-    def _frames(self, frames_dev):
+    def _packed(self, x_dev):
         torch = self._torch
-        if not torch.is_tensor(frames_dev) or not frames_dev.is_cuda:
-            raise ValueError("frames_dev must be a device tensor: the frames never leave the device")
-        if frames_dev.dim() != 2 or int(frames_dev.shape[1]) != self.in_dim or frames_dev.dtype != torch.float32:
-            raise ValueError("frames_dev: expected float32 [rows, %d], got %s" % (self.in_dim, tuple(frames_dev.shape)))
-        return frames_dev.contiguous()
+        name, why = self._INPUT
+        if not torch.is_tensor(x_dev) or not x_dev.is_cuda:
+            raise ValueError("%s must be a device tensor%s" % (name, why))
+        if x_dev.dim() != 2 or int(x_dev.shape[1]) != self.in_dim or x_dev.dtype != torch.float32:
+            raise ValueError("%s: expected float32 [rows, %d], got %s" % (name, self.in_dim, tuple(x_dev.shape)))
+        return x_dev.contiguous()
 
-    def _forward(self, frames_dev, offsets):
-        x = self._frames(frames_dev)
-        for layer in self.frame_layers:
-            x = layer.forward(x)
+    def _forward(self, x_dev, offsets, mark=tail_train._no_mark):
+        x, offsets = self._packed(x_dev), self._offsets(offsets)
+        mark("start")
+        x, offsets = self._walk(x, offsets, mark)
+        mark("frame_forward")
         pooled = self.pool.forward(x.contiguous(), offsets)
-        return self.tail.layers[1].forward(self.tail.layers[0].forward(pooled.contiguous()))
+        mark("pool_forward")
+        y = self.tail._forward(pooled.contiguous())
+        mark("segment_forward")
+        return y
 
-    def forward(self, frames_dev, offsets):
-        """frames_dev [rows, in_dim] on the device (the frozen node's packed output), offsets [B + 1] of its rows -> the
-        `output` endpoint [B, embed_dim] on the device, with the current weights."""
+    def _backward(self, gy, mark):
+        g = self.tail._backward(gy, True)
+        mark("segment_backward")
+        g = self.pool.backward(g)
+        mark("pool_backward")
+        for i in range(len(self.frame_layers) - 1, -1, -1):
+            g = self.frame_layers[i].backward(g, i > 0)
+            mark("frame_backward/%d" % i)
+        mark("frame_backward")
+
+    def forward(self, x_dev, offsets):
+        """x_dev [rows, in_dim] on the device (packed rows), offsets [B + 1] of its rows -> the `output` endpoint [B, embed_dim]
+        on the device, with the current weights."""
         with self._torch.cuda.device(self.device):
-            return self._forward(frames_dev, offsets)
+            return self._forward(x_dev, offsets)
 
-    def step(self, frames_dev, offsets, labels, learning_rate, global_step=0):
-        """One training step on a batch of packed frames: forward through the frame layers, the pooling and the segment layers,
+    def step(self, x_dev, offsets, labels, learning_rate, global_step=0, mark=None):
+        """One training step on a batch of packed rows: forward through the frame layers, the pooling and the segment layers,
         the head's mean loss at `global_step` and its gradients, backward through all of them, then per tensor l2 (kernels only),
-        the clip and the update -> StepResult(mean loss, top-1 accuracy), both of the parameters BEFORE the update."""
-        torch = self._torch
-        h = self.head
-        with torch.cuda.device(self.device):
-            y = self._forward(frames_dev, offsets)
-            out, top1, gx, _, _ = h.head._grad_device(y, labels, global_step, None, True, h._grad_rows, h._grad_bias)
-            n = int(out.shape[1])
-            g = self.tail.layers[1].backward(gx, True)
-            g = self.tail.layers[0].backward(g, True)
-            g = self.pool.backward(g)
-            for i in range(len(self.frame_layers) - 1, -1, -1):
-                g = self.frame_layers[i].backward(g, i > 0)
-            self.num_steps += 1
-            self.tail.num_steps = h.num_steps = self.num_steps
-            for name, w, gw, slots in self.tensors():
-                self.tail._apply(w, gw, slots, learning_rate, self.l2[name])
-            lab = losses._labels_dev(labels, n, out.device, torch)
-            return StepResult(float(out[0].double().mean()) if n else float("nan"),
-                              float((top1 == lab).double().mean()) if n else float("nan"))
+        the clip and the update -> StepResult(mean loss, top-1 accuracy), both of the parameters BEFORE the update.
+
+        mark(stage), if given, is called once in front of the first frame layer ("start", the arguments are checked by then) and
+        once behind every stage as soon as its calls are queued, in this order (n frame layers): start, frame_forward/0 ..
+        frame_forward/n-1, frame_forward, pool_forward, segment_forward, head, segment_backward, pool_backward,
+        frame_backward/n-1 .. frame_backward/0, frame_backward, optimizer.  The loss is read back after the last mark."""
+        return self.tail._step(self, lambda mark: self._forward(x_dev, offsets, mark), self._backward, labels, learning_rate,
+                               global_step, mark)
 
     def variables(self):
-        """name -> float32 numpy of every trained variable under its TensorFlow name (kernels as [in, out])."""
-        out = collections.OrderedDict()
-        for spec, layer in zip(self.frame_specs, self.frame_layers):
-            out[spec.kernel] = layer.kernel()
-            out[spec.bias] = layer.b.cpu().numpy().copy()
-            out[spec.bn + "/gamma"] = layer.bn[0].cpu().numpy().copy()
-            out[spec.bn + "/beta"] = layer.bn[1].cpu().numpy().copy()
+        """name -> float32 numpy of every trained variable under its TensorFlow name (layer.kernel() gives the kernels)."""
+        out = tail_train.layer_variables(self.frame_specs, self.frame_layers)
         out.update(self.tail.variables())
         return out
+
+
+class FrameTrainer(StackedTrainer):
+    """The trailing 1-tap frame layers on the frozen node's packed rows: dense layers (tail_train.SegLayer), the offsets pass
+    through.  forward(frames_dev, offsets), step(frames_dev, offsets, labels, learning_rate, global_step=0, mark=None)."""
+
+    _check, _specs, _l2 = staticmethod(check_supported), staticmethod(frame_variables), staticmethod(l2_assignment)
+    _CHAIN = "%s has %d rows, %s %d columns"
+    _INPUT = ("frames_dev", ": the frames never leave the device")
+
+    def _layer(self, spec, kernel, bias, bn, device, num_slots):
+        k = np.asarray(kernel, dtype=np.float32)
+        if k.ndim != 2:
+            raise ValueError("%s: a dense kernel [cin, cout] expected, got shape %s" % (spec.kernel, k.shape))
+        return tail_train.SegLayer(k, bias, bn, spec.act, device, num_slots)
+
+    def _width(self, layer):
+        return layer.in_dim
+
+    def _walk(self, x, offsets, mark):
+        for i, layer in enumerate(self.frame_layers):
+            x = layer.forward(x)
+            mark("frame_forward/%d" % i)
+        return x, offsets

@@ -13,7 +13,12 @@ validation evaluate, as head_train.py does: **parity unpinned**.
 
 `weight_l2_regularizer` goes on the two dense kernels only (tf.layers.dense(kernel_regularizer=...), model/tdnn.py:137-160),
 the head keeps the rule of head_train.optimizer_config, the clip is per tensor (model/trainer.py:529-533), Adam's step count
-is shared.  segment_variables, check_supported and l2_assignment are pure host code; the rest needs a HIP device."""
+is shared.  segment_variables, check_supported and l2_assignment are pure host code; the rest needs a HIP device.
+
+What the trainers stacked in front of this one (frame_train.py, conv_train.py) share lives here, once: Layer, the device state
+of one trained layer (SegLayer and conv_train.TConvLayer add their operator); layer_weights, layer_tensors and layer_variables
+between the checkpoint's names and the layers; and TailTrainer._step, the step behind the forward (the head's loss and
+gradient, the backward, Adam's shared count, one update per tensor, the StepResult), with its optional `mark` callback."""
 import collections
 import ctypes as C
 
@@ -91,23 +96,21 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-class SegLayer(object):
-    """One layer's parameters, gradients and optimizer slots on the device.  w holds the rows [N, ldw] of the weights (the
-    transpose of the TensorFlow kernel [K, N]; ldw = K rounded up to 4, the padding stays zero)."""
+class Layer(object):
+    """What every trained layer keeps on the device: the rows [N, ldw] of the weights (ldw = the width K rounded up to 4, the
+    padding stays zero), the bias, the four batch-norm vectors or None, their gradients, the optimizer slots and a workspace
+    that only grows.  SegLayer (dense, xv_seg_*) and conv_train.TConvLayer (packed utterances, xv_tconv_*) add the operator."""
 
-    def __init__(self, kernel, bias, bn, act, device=0, num_slots=0):
+    def __init__(self, rows, bias, bn, act, device=0, num_slots=0):
         torch = losses._need_device()
-        kernel = np.asarray(kernel, dtype=np.float32)
-        if kernel.ndim != 2 or tuple(np.shape(bias)) != (kernel.shape[1],):
-            raise ValueError("kernel [K, N] and bias [N] expected, got %s and %s" % (kernel.shape, np.shape(bias)))
-        self.in_dim, self.out_dim = int(kernel.shape[0]), int(kernel.shape[1])
+        self.out_dim, self.in_dim = int(rows.shape[0]), int(rows.shape[1])
         self.ldw = (self.in_dim + 3) // 4 * 4
         self.act, self.device = int(act), int(device)
         self._torch, self._lib = torch, _lib.load()
         dev = "cuda:%d" % self.device
         with torch.cuda.device(self.device):
             self.w = torch.zeros((self.out_dim, self.ldw), dtype=torch.float32, device=dev)
-            self.w[:, :self.in_dim] = torch.from_numpy(np.ascontiguousarray(kernel.T)).to(dev)
+            self.w[:, :self.in_dim] = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32)).to(dev)
             self.b = losses._f32(bias, self.device, torch)
             self.bn = None
             if bn is not None:
@@ -127,6 +130,27 @@ class SegLayer(object):
         if self.bn is not None:
             out += [("gamma", self.bn[0], self.ggamma), ("beta", self.bn[1], self.gbeta)]
         return out
+
+    def _empty_batch(self, rows, width, want_gx):
+        """The gradient of an empty sum: zeros in every parameter gradient -> gx [rows, width] of zeros, or None."""
+        for _, _, g in self.trained():
+            g.zero_()
+        return self._torch.zeros((rows, width), dtype=self._torch.float32, device=self._x.device) if want_gx else None
+
+    def _workspace(self, need, device):
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = self._torch.empty(max(need, 16), dtype=self._torch.uint8, device=device)
+        return self._ws
+
+
+class SegLayer(Layer):
+    """A dense layer: w holds the transpose of the TensorFlow kernel [K, N]."""
+
+    def __init__(self, kernel, bias, bn, act, device=0, num_slots=0):
+        kernel = np.asarray(kernel, dtype=np.float32)
+        if kernel.ndim != 2 or tuple(np.shape(bias)) != (kernel.shape[1],):
+            raise ValueError("kernel [K, N] and bias [N] expected, got %s and %s" % (kernel.shape, np.shape(bias)))
+        Layer.__init__(self, kernel.T, bias, bn, act, device, num_slots)
 
     def forward(self, x):
         """x [n, K] on the device, float32 contiguous -> y [n, N]; x and z are kept for backward()."""
@@ -153,25 +177,54 @@ class SegLayer(object):
         if tuple(gy.shape) != (n, self.out_dim) or not gy.is_contiguous():
             raise ValueError("gy: expected a contiguous [%d, %d], got shape %s" % (n, self.out_dim, tuple(gy.shape)))
         with torch.cuda.device(self.device):
-            if n == 0:                                  # the gradient of an empty sum
-                for _, _, g in self.trained():
-                    g.zero_()
-                return torch.zeros((0, self.in_dim), dtype=torch.float32, device=x.device) if want_gx else None
+            if n == 0:
+                return self._empty_batch(0, self.in_dim, want_gx)
             gx = torch.empty((n, self.in_dim), dtype=torch.float32, device=x.device) if want_gx else None
-            need = int(self._lib.xv_seg_workspace(n, self.in_dim, self.out_dim))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+            ws = self._workspace(int(self._lib.xv_seg_workspace(n, self.in_dim, self.out_dim)), x.device)
             bn = self.bn or [None] * 4
             stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(self._lib.xv_seg_backward(self.device, _p(gy), self.out_dim, _p(x), self.in_dim, _p(z), self.out_dim, n,
                                                  self.in_dim, _p(self.w), self.ldw, self.out_dim, _p(bn[0]), _p(bn[1]), _p(bn[2]),
                                                  _p(bn[3]), self.act, _p(gx), self.in_dim, _p(self.gw), _p(self.gb), _p(self.ggamma),
-                                                 _p(self.gbeta), _p(self._ws), self._ws.numel(), C.c_void_p(stream)))
+                                                 _p(self.gbeta), _p(ws), ws.numel(), C.c_void_p(stream)))
         return gx
 
     def kernel(self):
         """The TensorFlow kernel [K, N], float32 numpy."""
         return np.ascontiguousarray(self.w[:, :self.in_dim].t().cpu().numpy())
+
+
+def layer_weights(spec, weights):
+    """-> (kernel, bias, the four batch-norm vectors or None) of `spec` from the checkpoint; KeyError names what it lacks."""
+    missing = [k for k in (spec.kernel, spec.bias) + (tuple(spec.bn + "/" + s for s in _BN) if spec.bn else ()) if k not in weights]
+    if missing:
+        raise KeyError("the checkpoint lacks %s" % ", ".join(missing))
+    return weights[spec.kernel], weights[spec.bias], [weights[spec.bn + "/" + s] for s in _BN] if spec.bn else None
+
+
+def layer_tensors(specs, layers):
+    """[(TensorFlow name, parameter, gradient, slots)] of the layers, in the order of trained_names()."""
+    out = []
+    for spec, layer in zip(specs, layers):
+        names = {"kernel": spec.kernel, "bias": spec.bias, "gamma": (spec.bn or "") + "/gamma", "beta": (spec.bn or "") + "/beta"}
+        out += [(names[k], w, g, layer.slots[k]) for k, w, g in layer.trained()]
+    return out
+
+
+def layer_variables(specs, layers):
+    """name -> float32 numpy of the layers' trained variables under their TensorFlow names (layer.kernel() gives the kernel)."""
+    out = collections.OrderedDict()
+    for spec, layer in zip(specs, layers):
+        out[spec.kernel] = layer.kernel()
+        out[spec.bias] = layer.b.cpu().numpy().copy()
+        if spec.bn:
+            out[spec.bn + "/gamma"] = layer.bn[0].cpu().numpy().copy()
+            out[spec.bn + "/beta"] = layer.bn[1].cpu().numpy().copy()
+    return out
+
+
+def _no_mark(stage):
+    pass
 
 
 class TailTrainer(object):
@@ -183,13 +236,7 @@ class TailTrainer(object):
         self.specs = segment_variables(params)
         kind = head_train.optimizer_config(params)[0]
         num_slots = {_lib.XV_OPT_SGD: 0, _lib.XV_OPT_MOMENTUM: 1, _lib.XV_OPT_ADAM: 2}[kind]
-        self.layers = []
-        for spec in self.specs:
-            missing = [k for k in (spec.kernel, spec.bias) + (tuple(spec.bn + "/" + s for s in _BN) if spec.bn else ()) if k not in weights]
-            if missing:
-                raise KeyError("the checkpoint lacks %s" % ", ".join(missing))
-            bn = [weights[spec.bn + "/" + s] for s in _BN] if spec.bn else None
-            self.layers.append(SegLayer(weights[spec.kernel], weights[spec.bias], bn, spec.act, device, num_slots))
+        self.layers = [SegLayer(*layer_weights(spec, weights), spec.act, device, num_slots) for spec in self.specs]
         if self.layers[1].in_dim != self.layers[0].out_dim:
             raise ValueError("%s has %d rows, %s %d columns" % (self.specs[1].kernel, self.layers[1].in_dim, self.specs[0].kernel,
                                                                   self.layers[0].out_dim))
@@ -198,17 +245,21 @@ class TailTrainer(object):
         self.l2 = l2_assignment(params)
         torch = losses._need_device()
         self._torch, self._lib, self.device = torch, _lib.load(), int(device)
-        largest = max([layer.w.numel() for layer in self.layers] + [self.head.head.raw_rows.numel()])
-        with torch.cuda.device(self.device):
-            self._ws = torch.empty(max(int(self._lib.xv_opt_workspace(largest)), 8), dtype=torch.uint8, device=self.layers[0].w.device)
+        self._ws = None
+        self._fit_workspace(self.layers)
         self.num_steps = 0                                                   # adam's t, shared by every tensor
+
+    def _fit_workspace(self, layers):
+        """Grow the optimizer's workspace to the largest tensor among `layers` and the head."""
+        largest = max([layer.w.numel() for layer in layers] + [self.head.head.raw_rows.numel()])
+        need = max(int(self._lib.xv_opt_workspace(largest)), 8)
+        if self._ws is None or self._ws.numel() < need:
+            with self._torch.cuda.device(self.device):
+                self._ws = self._torch.empty(need, dtype=self._torch.uint8, device=layers[0].w.device)
 
     def tensors(self):
         """[(TensorFlow name, parameter, gradient, slots)] of everything trained, in the order of trained_names()."""
-        out = []
-        for spec, layer in zip(self.specs, self.layers):
-            names = {"kernel": spec.kernel, "bias": spec.bias, "gamma": (spec.bn or "") + "/gamma", "beta": (spec.bn or "") + "/beta"}
-            out += [(names[k], w, g, layer.slots[k]) for k, w, g in layer.trained()]
+        out = layer_tensors(self.specs, self.layers)
         h = self.head
         out.append((model_io.SOFTMAX_KERNEL, h.head.raw_rows, h._grad_rows, h._row_slots))
         if h.head.bias is not None:
@@ -219,8 +270,13 @@ class TailTrainer(object):
         """pooled [n, pool_dim] -> the `output` endpoint [n, embed_dim] on the device, with the current weights."""
         torch = self._torch
         with torch.cuda.device(self.device):
-            x = losses._f32(pooled, self.device, torch)
-            return self.layers[1].forward(self.layers[0].forward(x))
+            return self._forward(losses._f32(pooled, self.device, torch))
+
+    def _forward(self, x):
+        return self.layers[1].forward(self.layers[0].forward(x))
+
+    def _backward(self, gy, want_gx):
+        return self.layers[0].backward(self.layers[1].backward(gy, True), want_gx)
 
     def _apply(self, w, g, slots, lr, l2):
         h = self.head
@@ -229,35 +285,49 @@ class TailTrainer(object):
                                          _p(slots[1]) if len(slots) > 1 else None, w.numel(), float(lr), l2, h.clip_norm, h.momentum,
                                          self.num_steps, _p(self._ws), self._ws.numel(), C.c_void_p(stream)))
 
-    def step(self, pooled, labels, learning_rate, global_step=0):
-        """One training step on a batch of pooled rows [n, pool_dim]: forward through both layers, the head's mean loss at
-        `global_step` and its gradients, backward through both layers, then per tensor l2 (kernels only), the clip and the
-        update -> StepResult(mean loss, top-1 accuracy), both of the parameters BEFORE the update."""
+    def _step(self, owner, forward, backward, labels, learning_rate, global_step, mark):
+        """THE training step, of this trainer (owner is self) and of every trainer stacked in front of it (frame_train.Stacked):
+        y = forward(mark), the head's mean loss at `global_step` and its gradients, backward(grad_y, mark), then Adam's shared
+        step count and per tensor of owner.tensors() l2, the clip and the update -> StepResult(mean loss, top-1 accuracy), both
+        of the parameters BEFORE the update.  mark(stage) is called behind the head ("head") and the updates ("optimizer"), and
+        by forward and backward behind their own stages; the loss is read back after the last mark."""
         torch = self._torch
         h = self.head
+        mark = mark or _no_mark
         with torch.cuda.device(self.device):
-            y = self.forward(pooled)
+            y = forward(mark)
             out, top1, gx, _, _ = h.head._grad_device(y, labels, global_step, None, True, h._grad_rows, h._grad_bias)
+            mark("head")
             n = int(out.shape[1])
-            g1 = self.layers[1].backward(gx, True)
-            self.layers[0].backward(g1, False)
-            self.num_steps += 1
-            h.num_steps = self.num_steps
-            for name, w, g, slots in self.tensors():
-                self._apply(w, g, slots, learning_rate, self.l2[name])
+            backward(gx, mark)
+            owner.num_steps += 1
+            self.num_steps = h.num_steps = owner.num_steps
+            for name, w, g, slots in owner.tensors():
+                self._apply(w, g, slots, learning_rate, owner.l2[name])
+            mark("optimizer")
             lab = losses._labels_dev(labels, n, out.device, torch)
             return StepResult(float(out[0].double().mean()) if n else float("nan"),
                               float((top1 == lab).double().mean()) if n else float("nan"))
 
+    def step(self, pooled, labels, learning_rate, global_step=0, mark=None):
+        """One training step on a batch of pooled rows [n, pool_dim]: forward through both layers, then _step.  mark(stage), if
+        given, is called in front of the first layer ("start", the rows are on the device by then), then behind
+        "segment_forward", "head", "segment_backward" and "optimizer", in this order."""
+        def forward(mark):
+            x = losses._f32(pooled, self.device, self._torch)
+            mark("start")
+            y = self._forward(x)
+            mark("segment_forward")
+            return y
+
+        def backward(gx, mark):
+            self._backward(gx, False)
+            mark("segment_backward")
+        return self._step(self, forward, backward, labels, learning_rate, global_step, mark)
+
     def variables(self):
         """name -> float32 numpy of every trained variable under its TensorFlow name (kernels as [in, out])."""
-        out = collections.OrderedDict()
-        for spec, layer in zip(self.specs, self.layers):
-            out[spec.kernel] = layer.kernel()
-            out[spec.bias] = layer.b.cpu().numpy().copy()
-            if spec.bn:
-                out[spec.bn + "/gamma"] = layer.bn[0].cpu().numpy().copy()
-                out[spec.bn + "/beta"] = layer.bn[1].cpu().numpy().copy()
+        out = layer_variables(self.specs, self.layers)
         out[model_io.SOFTMAX_KERNEL] = self.head.kernel()
         if self.head.bias() is not None:
             out[model_io.SOFTMAX_BIAS] = self.head.bias()

@@ -9,8 +9,10 @@ at W = 1 beside xv_seg_forward / xv_seg_backward on the same operands.  The numb
                                      [--embed 512] [--classes 7000] [--iters 20] [--warmup 3] [--rounds 3] [--op-iters 20]
 
 No time is gated: the torch and xv_seg numbers are the context.  Everything is timed in alternating rounds inside one process,
-device events around back-to-back calls after warm-up calls of each, one JSON line with every round's figure.  The parameters
-after the first step are compared with the torch step at the size that is timed."""
+device events around back-to-back calls after warm-up calls of each, one JSON line with every round's figure.  The stages and
+the frame layers are timed on ConvTrainer.step itself, through its `mark` callback (a device event at every border): that run
+reads the mean loss back like every step, after the last event.  The parameters after the first step are compared with the
+torch step at the size that is timed."""
 import argparse
 import ctypes as C
 import json
@@ -36,44 +38,23 @@ def window_ms(fn, torch, iters):
     return a.elapsed_time(b) / iters
 
 
-def staged_step(ct, feats, offsets, labels, lr, torch):
-    """ConvTrainer.step stage by stage with a device event at every border -> (milliseconds per stage, milliseconds of every
-    frame layer forward and backward); the same calls in the same order, the loss is not read back."""
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)]
+def marked_step(ct, feats, offsets, labels, lr, torch):
+    """One ConvTrainer.step(mark=...) with a device event at every mark -> (milliseconds per stage, milliseconds of every frame
+    layer forward and backward).  It is the step itself, so the mean loss is read back, after the last event."""
     n = len(ct.frame_layers)
-    fe = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
-    be = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
-    h = ct.head
-    ev[0].record()
-    x, off = feats, offsets
-    fe[0].record()
-    for i, layer in enumerate(ct.frame_layers):
-        x, off = layer.forward(x, off)
-        fe[i + 1].record()
-    ev[1].record()
-    pooled = ct.pool.forward(x, off)
-    ev[2].record()
-    y = ct.tail.layers[1].forward(ct.tail.layers[0].forward(pooled))
-    ev[3].record()
-    _, _, gx, _, _ = h.head._grad_device(y, labels, 0, None, True, h._grad_rows, h._grad_bias)
-    ev[4].record()
-    g = ct.tail.layers[0].backward(ct.tail.layers[1].backward(gx, True), True)
-    ev[5].record()
-    g = ct.pool.backward(g)
-    ev[6].record()
-    be[n].record()
-    for i in range(n - 1, -1, -1):
-        g = ct.frame_layers[i].backward(g, i > 0)
-        be[i].record()
-    ev[7].record()
-    ct.num_steps += 1
-    ct.tail.num_steps = h.num_steps = ct.num_steps
-    for name, w, gw, slots in ct.tensors():
-        ct.tail._apply(w, gw, slots, lr, ct.l2[name])
-    ev[8].record()
-    ev[8].synchronize()
-    return ([ev[i].elapsed_time(ev[i + 1]) for i in range(len(STAGES))], [fe[i].elapsed_time(fe[i + 1]) for i in range(n)],
-            [be[i + 1].elapsed_time(be[i]) for i in range(n)])
+    spare = [torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 2 * n + 1)]
+    ev = {}
+
+    def mark(stage):
+        ev[stage] = spare.pop()
+        ev[stage].record()
+    ct.step(feats, offsets, labels, lr, global_step=0, mark=mark)
+    ev["optimizer"].synchronize()
+    borders = [ev["start"]] + [ev[s] for s in STAGES]
+    fwd = [ev["start"]] + [ev["frame_forward/%d" % i] for i in range(n)]
+    bwd = [ev["frame_backward/%d" % i] for i in range(n)] + [ev["pool_backward"]]
+    return ([borders[i].elapsed_time(borders[i + 1]) for i in range(len(STAGES))], [fwd[i].elapsed_time(fwd[i + 1]) for i in range(n)],
+            [bwd[i + 1].elapsed_time(bwd[i]) for i in range(n)])
 
 
 def main(argv=None):
@@ -183,8 +164,8 @@ def main(argv=None):
             torch_ms.append(window_ms(eager, torch, args.iters))
 
         # the stages of the step, and every frame layer on its own
-        staged_step(ct, feats, offsets, labels, lr, torch)
-        runs = [staged_step(ct, feats, offsets, labels, lr, torch) for _ in range(args.iters)]
+        marked_step(ct, feats, offsets, labels, lr, torch)
+        runs = [marked_step(ct, feats, offsets, labels, lr, torch) for _ in range(args.iters)]
         per = np.array([r[0] for r in runs])
         stage_ms = {s: float(np.median(per[:, i])) for i, s in enumerate(STAGES)}
         layer_fwd = np.median(np.array([r[1] for r in runs]), axis=0).tolist()

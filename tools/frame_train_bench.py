@@ -10,7 +10,9 @@ the step each of its stages takes.  The numbers of profiles/frame_train.md come 
 64 segments of 300 frames leave 286 rows each behind tdnn3_relu: 18 304 rows through 512 -> 512 -> 1500, pooling width 3000 ->
 512 -> 512, 7000 classes, momentum.  No time is gated: the torch numbers are the context.  Everything is timed in alternating
 rounds inside one process, device events around back-to-back calls after warm-up calls of each, one JSON line with every round's
-figure.  The parameters after the first step are compared with the torch step at the size that is timed."""
+figure.  The stages are timed on FrameTrainer.step itself, through its `mark` callback (a device event at every border): that
+run reads the mean loss back like every step, after the last event.  The parameters after the first step are compared with the
+torch step at the size that is timed."""
 import argparse
 import ctypes as C
 import json
@@ -36,36 +38,14 @@ def window_ms(fn, torch, iters):
 STAGES = ("frame_forward", "pool_forward", "segment_forward", "head", "segment_backward", "pool_backward", "frame_backward", "optimizer")
 
 
-def staged_step(ft, frames, offsets, labels, lr, torch):
-    """FrameTrainer.step stage by stage with a device event at every border -> milliseconds per stage (the same calls in the same
-    order; the loss is not read back)."""
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)]
-    h = ft.head
-    ev[0].record()
-    x = frames
-    for layer in ft.frame_layers:
-        x = layer.forward(x)
-    ev[1].record()
-    pooled = ft.pool.forward(x, offsets)
-    ev[2].record()
-    y = ft.tail.layers[1].forward(ft.tail.layers[0].forward(pooled))
-    ev[3].record()
-    _, _, gx, _, _ = h.head._grad_device(y, labels, 0, None, True, h._grad_rows, h._grad_bias)
-    ev[4].record()
-    g = ft.tail.layers[0].backward(ft.tail.layers[1].backward(gx, True), True)
-    ev[5].record()
-    g = ft.pool.backward(g)
-    ev[6].record()
-    for i in range(len(ft.frame_layers) - 1, -1, -1):
-        g = ft.frame_layers[i].backward(g, i > 0)
-    ev[7].record()
-    ft.num_steps += 1
-    ft.tail.num_steps = h.num_steps = ft.num_steps
-    for name, w, gw, slots in ft.tensors():
-        ft.tail._apply(w, gw, slots, lr, ft.l2[name])
-    ev[8].record()
-    ev[8].synchronize()
-    return [ev[i].elapsed_time(ev[i + 1]) for i in range(len(STAGES))]
+def marked_step(ft, frames, offsets, labels, lr, torch):
+    """One FrameTrainer.step(mark=...) with a device event at the marks of STAGES -> milliseconds per stage.  It is the step
+    itself, so the mean loss is read back, after the last event."""
+    ev = {stage: torch.cuda.Event(enable_timing=True) for stage in ("start",) + STAGES}
+    ft.step(frames, offsets, labels, lr, global_step=0, mark=lambda stage: stage in ev and ev[stage].record())
+    ev["optimizer"].synchronize()
+    borders = [ev["start"]] + [ev[s] for s in STAGES]
+    return [borders[i].elapsed_time(borders[i + 1]) for i in range(len(STAGES))]
 
 
 def main(argv=None):
@@ -165,8 +145,8 @@ def main(argv=None):
             torch_ms.append(window_ms(eager, torch, args.iters))
 
         # the stages of the step
-        staged_step(ft, frames, offsets, labels, lr, torch)
-        per = np.array([staged_step(ft, frames, offsets, labels, lr, torch) for _ in range(args.iters)])
+        marked_step(ft, frames, offsets, labels, lr, torch)
+        per = np.array([marked_step(ft, frames, offsets, labels, lr, torch) for _ in range(args.iters)])
         stage_ms = {s: float(np.median(per[:, i])) for i, s in enumerate(STAGES)}
         total = float(sum(stage_ms.values()))
         seg_share = (stage_ms["frame_forward"] + stage_ms["segment_forward"] + stage_ms["segment_backward"]
