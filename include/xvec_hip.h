@@ -185,7 +185,8 @@ int xv_flags_decode(const int32_t* host_flags);
 int xv_node_id(const xv_handle* h, const char* endpoint_name);
 
 /* XV_PREC_F16F6: 1 if the layer that produces `endpoint_name` (any of its stage endpoints, e.g. "tdnn3_conv" / "tdnn3_bn" /
- * "tdnn3_relu"; a ResNet block output names the block's second convolution) runs on the two-unit kernel, 0 if it runs on the
+ * "tdnn3_relu"; a ResNet block output names the block's second convolution, "<block>_relu0" its first convolution and
+ * "<block>_short" the projection shortcut of an `a` block) runs on the two-unit kernel, 0 if it runs on the
  * three-unit kernels (other precisions, layers the two-unit kernel does not cover, and layers xv_finalize demoted because the
  * magnitudes inside one of their 32-channel blocks -- BN-folded scale / shift of the input channels, |w| of a K group -- are too
  * far apart for the block-scaled fp6 cross terms).  XV_ERR_INVALID for a name that is not a layer endpoint, XV_ERR_STATE before

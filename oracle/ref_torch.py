@@ -242,8 +242,11 @@ class TorchResnet18(object):
 
     def _block(self, x, name, strides, projection, ep):
         f = self._act(self._bn(self._conv_same(x, name + "_conv0", strides), name + "_bn0"), name + "_relu0")
+        ep[name + "_relu0"] = f.permute(0, 2, 3, 1)
         f = self._bn(self._conv_same(f, name + "_conv1"), name + "_bn1")
         sc = self._bn(self._conv_same(x, name + "_conv_short", strides), name + "_bn_short") if projection else x
+        if projection:
+            ep[name + "_short"] = sc.permute(0, 2, 3, 1)
         f = self._act(f + sc, name + "_relu_final")
         ep[name] = f.permute(0, 2, 3, 1)
         return f

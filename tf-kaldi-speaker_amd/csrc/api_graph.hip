@@ -131,7 +131,9 @@ int add_conv2d(xv_handle* h, const std::string& var, const std::string& bn, cons
 // model/resnet.py:152-351 (resnet_18): conv0, four stages of [conv_block, identity_block...], conv5,
 // dense1, dense2, pooling, tdnn6, tdnn7.  `channels` = width of stage 1 (64 in the reference).
 // Block outputs are exposed as extra nodes (conv0_relu, conv1a, ..., conv5_relu, dense*_relu) for
-// tests only; the reference registers just pooling / tdnn6_* / tdnn7_* / output.
+// tests only, and so are the two inner values of a residual block: "<block>_relu0", the first convolution behind its
+// activation, and "<block>_short", the projection shortcut behind its normalisation (`a` blocks only); the reference
+// registers just pooling / tdnn6_* / tdnn7_* / output.
 int build_resnet(xv_handle* h) {
   const xv_model_desc& d = h->desc;
   const int act = act_of(d);
@@ -163,10 +165,11 @@ int build_resnet(xv_handle* h) {
       const std::string b = sc + nm;
       const int s_w = bi == 0 ? sw : 1, Fi = bi == 0 ? F : Fo;
       const int s_t = (bi == 0 && stage > 1 && d.resnet_time_stride) ? 2 : 1;       // model/resnet.py:187,239,244,249
-      const int c0 = add_conv2d(h, b + "_conv0", b + "_bn0", b + "_relu0", 1, cin, nf, Fi, Fo, s_w, act, v, -1, nullptr, s_t);
+      const std::string n_relu0 = std::string(nm) + "_relu0", n_short = std::string(nm) + "_short";
+      const int c0 = add_conv2d(h, b + "_conv0", b + "_bn0", b + "_relu0", 1, cin, nf, Fi, Fo, s_w, act, v, -1, n_relu0.c_str(), s_t);
       int shortcut = v;
       if (bi == 0)      // projection shortcut: 1x1 conv + BN (model/resnet.py:71-83)
-        shortcut = add_conv2d(h, b + "_conv_short", b + "_bn_short", "", 2, cin, nf, Fi, Fo, s_w, ACT_NONE, v, -1, nullptr, s_t);
+        shortcut = add_conv2d(h, b + "_conv_short", b + "_bn_short", "", 2, cin, nf, Fi, Fo, s_w, ACT_NONE, v, -1, n_short.c_str(), s_t);
       v = add_conv2d(h, b + "_conv1", b + "_bn1", b + "_relu_final", 1, nf, nf, Fo, Fo, 1, act, c0, shortcut, nm);
       cin = nf;
     }
