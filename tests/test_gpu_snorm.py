@@ -164,7 +164,8 @@ def test_end_to_end_cosine_against_float64(lib, n, m, d):
 
 # ------------------------------------------------------------------------------------------------ 3
 def test_ties(lib):
-    """Every cohort row three times, top_k = 100: the boundary falls inside a group of equal scores."""
+    """Every cohort row three times, top_k = 100: the boundary falls inside a group of equal scores.  Then 83 times, top_k =
+    8299: the same in a row too long for the LDS stage."""
     rng = np.random.default_rng(3)
     n, m1, k = 20, 150, 24
     a, b1 = anchored(rng, n, m1, k)
@@ -173,6 +174,17 @@ def test_ties(lib):
     s = lib_matrix(lib, ad, None, bd, None)
     check_against_matrix(raw_stats(lib, ad, k, n, None, bd, k, 3 * m1, None, k, 100), s, 100, what="ties")
     check_against_matrix(raw_stats(lib, ad, k, n, None, bd, k, 3 * m1, None, k, 99), s, 99, what="ties, whole groups")
+    # the same block 83 times: m = 12450 is above the 12288 scores a workgroup stages in LDS, so the select sweeps the row in
+    # global memory.  8299 is no multiple of 83: the boundary falls inside a group of 83 equal scores in every row
+    reps = 83
+    m = reps * m1
+    b = np.tile(b1, (reps, 1))[rng.permutation(m)]
+    bd = _dev(b)
+    s = lib_matrix(lib, ad, None, bd, None)
+    desc = -np.sort(-s, axis=1)
+    assert np.array_equal(desc[:, 8298], desc[:, 8299])
+    check_against_matrix(raw_stats(lib, ad, k, n, None, bd, k, m, None, k, 8300), s, 8300, what="long ties, whole groups")
+    check_against_matrix(raw_stats(lib, ad, k, n, None, bd, k, m, None, k, 8299), s, 8299, what="long ties")
 
 
 # ------------------------------------------------------------------------------------------------ 4

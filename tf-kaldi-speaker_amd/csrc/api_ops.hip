@@ -283,6 +283,12 @@ static int score_operands(const char* who, const float* a, int64_t lda, int64_t 
   return XV_OK;
 }
 
+static int check_nbins(const char* who, int nbins) {
+  if (nbins < 256 || nbins > 65536 || (nbins & (nbins - 1)))
+    return fail(nullptr, XV_ERR_INVALID, "%s: nbins is a power of two in 256..65536, got %d", who, nbins);
+  return XV_OK;
+}
+
 int xv_score_matrix(int device, const float* a_dev, int64_t lda, int64_t n, const float* b_dev, int64_t ldb, int64_t m, int d,
                     float* out_dev, int64_t ldo, void* stream) {
   if (const int rc = score_operands("xv_score_matrix", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
@@ -308,8 +314,7 @@ int xv_score_histogram(int device, const float* a_dev, int64_t lda, int64_t n, c
                        int64_t ldb, int64_t m, const int32_t* labels_b_dev, int d, int self, int nbins, uint64_t* hist_same_dev,
                        uint64_t* hist_diff_dev, void* stream) {
   if (const int rc = score_operands("xv_score_histogram", a_dev, lda, n, b_dev, ldb, m, d)) return rc;
-  if (nbins < 256 || nbins > 65536 || (nbins & (nbins - 1)))
-    return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: nbins is a power of two in 256..65536, got %d", nbins);
+  if (const int rc = check_nbins("xv_score_histogram", nbins)) return rc;
   if (!labels_a_dev || !labels_b_dev || !hist_same_dev || !hist_diff_dev || hist_same_dev == hist_diff_dev)
     return fail(nullptr, XV_ERR_INVALID, "xv_score_histogram: null pointer");
   if (self && (a_dev != b_dev || n != m || lda != ldb || labels_a_dev != labels_b_dev))
@@ -720,8 +725,7 @@ int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, co
                       const float* b_dev, int64_t ldb, int64_t m, const float* tau_dev, const int32_t* labels_b_dev, int k, double lo,
                       double hi, int nbins, uint64_t* hist_same_dev, uint64_t* hist_diff_dev, void* stream) {
   if (const int rc = plda_operands("xv_plda_histogram", a_dev, lda, n, rho_dev, b_dev, ldb, m, k)) return rc;
-  if (nbins < 256 || nbins > 65536 || (nbins & (nbins - 1)))
-    return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: nbins is a power of two in 256..65536, got %d", nbins);
+  if (const int rc = check_nbins("xv_plda_histogram", nbins)) return rc;
   if (!(lo < hi) || !(hi - lo <= 1.7976931348623157e308))
     return fail(nullptr, XV_ERR_INVALID, "xv_plda_histogram: the range [lo, hi) is empty or not finite");
   if (!labels_a_dev || !labels_b_dev || !hist_same_dev || !hist_diff_dev || hist_same_dev == hist_diff_dev)
@@ -731,6 +735,19 @@ int xv_plda_histogram(int device, const float* a_dev, int64_t lda, int64_t n, co
                                  hi, nbins, reinterpret_cast<unsigned long long*>(hist_same_dev),
                                  reinterpret_cast<unsigned long long*>(hist_diff_dev), to_stream(stream));
   });
+}
+
+// shared argument checks of the two panel entry points (xv_cohort_stats, xv_score_topk)
+static int exclusion_labels(const char* who, const int32_t* la, const int32_t* lb) {
+  if ((la == nullptr) != (lb == nullptr))
+    return fail(nullptr, XV_ERR_INVALID, "%s: exclusion labels are given for both sides or for neither", who);
+  return XV_OK;
+}
+
+static int panel_workspace(const char* who, const void* ws, int64_t ws_bytes, int64_t need) {
+  if (ws_bytes < need || !ws)
+    return fail(nullptr, XV_ERR_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", who, (long long)(ws ? ws_bytes : 0), (long long)need);
+  return XV_OK;
 }
 
 int64_t xv_cohort_stats_workspace(int64_t n, int64_t m, int top_k) {
@@ -743,14 +760,10 @@ int xv_cohort_stats(int device, const float* a_dev, int64_t lda, int64_t n, cons
                     int top_k, float* mean_dev, float* std_dev, int32_t* count_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
   if (const int rc = score_operands("xv_cohort_stats", a_dev, lda, n, b_dev, ldb, m, k)) return rc;
   if (top_k < 0 || top_k > m) return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: 0 <= top_k <= m, got %d for m = %lld", top_k, (long long)m);
-  if ((labels_a_dev == nullptr) != (labels_b_dev == nullptr))
-    return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: exclusion labels are given for both sides or for neither");
+  if (const int rc = exclusion_labels("xv_cohort_stats", labels_a_dev, labels_b_dev)) return rc;
   if (n == 0) return XV_OK;
   if (!mean_dev || !std_dev) return fail(nullptr, XV_ERR_INVALID, "xv_cohort_stats: null pointer");
-  const int64_t need = cohort_stats_workspace_bytes(n, m);
-  if (ws_bytes < need || !ws_dev)
-    return fail(nullptr, XV_ERR_WORKSPACE, "xv_cohort_stats: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
-                (long long)need);
+  if (const int rc = panel_workspace("xv_cohort_stats", ws_dev, ws_bytes, cohort_stats_workspace_bytes(n, m))) return rc;
   return with_device(device, "cohort_stats", [&] {
     return launch_cohort_stats(a_dev, lda, (int)n, row_bias_dev, labels_a_dev, b_dev, ldb, (int)m, col_bias_dev, labels_b_dev,
                                k, top_k, mean_dev, std_dev, count_dev, ws_dev, ws_bytes, to_stream(stream));
@@ -769,14 +782,10 @@ int xv_score_topk(int device, const float* a_dev, int64_t lda, int64_t n, const 
   if (const int rc = score_operands("xv_score_topk", a_dev, lda, n, b_dev, ldb, m, k)) return rc;
   if (top_k < 1 || top_k > 1024) return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_score_topk: 1 <= top_k <= 1024, got %d", top_k);
   if (ldo < top_k) return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: ldo = %lld for top_k = %d", (long long)ldo, top_k);
-  if ((labels_a_dev == nullptr) != (labels_b_dev == nullptr))
-    return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: exclusion labels are given for both sides or for neither");
+  if (const int rc = exclusion_labels("xv_score_topk", labels_a_dev, labels_b_dev)) return rc;
   if (n == 0) return XV_OK;
   if (!scores_dev || !index_dev) return fail(nullptr, XV_ERR_INVALID, "xv_score_topk: null pointer");
-  const int64_t need = score_topk_workspace_bytes(n, m);
-  if (ws_bytes < need || !ws_dev)
-    return fail(nullptr, XV_ERR_WORKSPACE, "xv_score_topk: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
-                (long long)need);
+  if (const int rc = panel_workspace("xv_score_topk", ws_dev, ws_bytes, score_topk_workspace_bytes(n, m))) return rc;
   return with_device(device, "score_topk", [&] {
     return launch_score_topk(a_dev, lda, (int)n, row_bias_dev, labels_a_dev, b_dev, ldb, (int)m, col_bias_dev, labels_b_dev, k,
                              top_k, scores_dev, index_dev, ldo, count_dev, ws_dev, ws_bytes, to_stream(stream));

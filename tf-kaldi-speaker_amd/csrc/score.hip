@@ -44,20 +44,21 @@
 //    y_d p_d (and the second half, W_d on the enrolment side or y_d^2 on the test side, for sets of mixed n) and the bias
 //    logdet + sum_d q_d y_d^2.  The per-n vectors inv, p, q, w come from the host in float64, one table per distinct n.
 //
-// Score normalisation (Z/T/S-norm with adaptive top-K cohorts; include/xvec_hip.h has the definitions) is missing from the
-// reference (egs/sre/v1/run.sh:13) and from Kaldi's binaries: **parity unpinned**, checked against tests/helpers/ref_snorm.py.
-//  * launch_cohort_stats: score_tile_kernel (EPI_MATRIX, or EPI_PLDA when a bias is given) writes a panel of whole tile rows of
-//    scores into the workspace, so every score is the one xv_score_matrix / xv_plda_matrix would write; then
-//  * cohort_select_kernel: one workgroup per panel row.  Rows of up to 12288 scores are copied into LDS once and every sweep
-//    reads them there; longer rows are swept in global memory (L2).  An exact radix select on the order-preserving uint32
-//    image of the float (digits of 11, 11 and 10 bits, histograms in LDS with ds_add_u32) finds the K-th largest score and
-//    its multiplicity inside the top K; one sweep sums what lies above it, one more takes the centred squares, both in
-//    double and in a fixed order.  top_k = 0 (or K = all eligible columns) skips the select.  A fused epilogue that never
-//    writes the panel has not been built.
-//
-// Identification (top-K gallery search; include/xvec_hip.h has the rule) is the same panel walk with topk_select_kernel in
-// place of the statistics: the select, an ordered compaction of the hits into LDS and a bitonic sort of (score, column) keys.
-// The reference has no identification step: **parity unpinned**, checked against tests/helpers/ref_topk.py.
+// Score normalisation (Z/T/S-norm with adaptive top-K cohorts) and identification (top-K gallery search) want the K largest
+// scores of every row, never the [n, m] matrix; include/xvec_hip.h has the definitions.  Both are missing from the reference
+// (egs/sre/v1/run.sh:13) and from Kaldi's binaries: **parity unpinned**, checked against tests/helpers/ref_snorm.py and
+// ref_topk.py.  They share two things:
+//  * the panel walk (walk_panels): score_tile_kernel (EPI_MATRIX, or EPI_PLDA when a bias is given) writes a panel of whole
+//    tile rows of scores into the workspace, so every score is the one xv_score_matrix / xv_plda_matrix would write; then a
+//    select kernel runs with one workgroup per panel row.  Rows of up to 12288 scores are copied into LDS once (SelRow) and
+//    every sweep reads them there; longer rows are swept in global memory (L2).  A fused epilogue that never writes the panel
+//    has not been built;
+//  * the select (radix_select): exact, on the order-preserving uint32 image of the float (digits of 11, 11 and 10 bits,
+//    histograms in LDS with ds_add_u32): the K-th largest eligible score of the row and its multiplicity inside the top K.
+//    K = all eligible columns skips it.
+// cohort_select_kernel then sums what lies above the K-th score in one sweep and takes the centred squares in one more, both
+// in double and in a fixed order.  topk_select_kernel lets the select stop as soon as the candidates fit its sort, compacts
+// the hits into LDS in column order and sorts (score, column) keys with a bitonic network.
 #include <mutex>
 
 #include "xv_kernels.h"
@@ -450,10 +451,20 @@ __global__ __launch_bounds__(256) void plda_rows_kernel(const float* u, int64_t 
   if (bias && lane == 0) bias[r] = (float)((logdet ? logdet[k] : 0.0) + acc);
 }
 
-// ---------------------------------------------------------------------------------------------- cohort statistics
+// ---------------------------------------------------------------------------------------------- row select
 constexpr int kSelBins = 2048;                // digit histogram of the radix select: digits of 11, 11 and 10 bits
 constexpr int kSelStageMax = 12288;           // rows of up to this many scores are kept in LDS for all sweeps (48 KB)
-constexpr size_t kSelFixedBytes = kSelBins * sizeof(unsigned) + 8 * sizeof(double) + 8 * sizeof(unsigned);
+constexpr int kTopkMax = 1024;                // keys of the top-K sort: 8 KB, the bytes of the digit histogram they take over
+
+// dynamic LDS of the two select kernels: this fixed region, then the staged row [m] when STAGE
+struct SelLds {
+  unsigned hist[kSelBins];                    // digit histogram; top-K: the 64-bit sort keys [kTopkMax] once the select is done
+  double dslot[8];                            // two block_sum slots of the statistics
+  unsigned uslot[8];                          // 0-3 wave sums; the select: 4 digit found, 5 rank left in it, 6 scores down to it
+  __device__ float* stage() { return reinterpret_cast<float*>(this + 1); }
+};
+constexpr size_t kSelFixedBytes = sizeof(SelLds);
+static_assert(kTopkMax * sizeof(unsigned long long) <= sizeof(SelLds::hist), "the keys reuse the histogram");
 
 // order-preserving uint32 image of a float: a < b  <=>  key(a) < key(b); -0.0 and +0.0 share the key of +0.0
 __device__ __forceinline__ unsigned score_key(float v) {
@@ -478,42 +489,135 @@ __device__ __forceinline__ T block_sum(T v, T* slot) {
   return r;
 }
 
+// One row of a panel of scores [rows, ldp], as the workgroup of a select kernel sees it: the row is copied into LDS once when
+// STAGE, and every later sweep reads it there; a column j is eligible unless la[row] == lb[j]; `elig` counts the eligible columns.
+template <bool STAGE>
+struct SelRow {
+  const float* src;
+  const float* stage;
+  const int32_t* lb;
+  int32_t mine;
+  bool excl;
+  unsigned elig;
+  __device__ __forceinline__ SelRow(SelLds* lds, const float* panel, int64_t ldp, int m, const int32_t* la, const int32_t* lb_)
+      : src(panel + (int64_t)blockIdx.x * ldp), stage(lds->stage()), lb(lb_), mine(0), excl(la != nullptr), elig((unsigned)m) {
+    const int tid = threadIdx.x;
+    if (STAGE) {
+      float* st = lds->stage();
+      for (int j = tid; j < m; j += 256) st[j] = src[j];
+      __syncthreads();
+    }
+    mine = excl ? la[blockIdx.x] : 0;
+    if (excl) {
+      unsigned c = 0;
+      for (int j = tid; j < m; j += 256) c += lb[j] != mine ? 1u : 0u;
+      elig = block_sum(c, lds->uslot);
+    }
+  }
+  __device__ __forceinline__ float val(int j) const { return STAGE ? stage[j] : src[j]; }
+  __device__ __forceinline__ bool eligible(int j) const { return !excl || lb[j] != mine; }
+};
+
+// What the radix select finds: the key T of the K-th largest eligible score and how many copies of it (`ties`) belong to the
+// top K.  With an early stop: `ncand` scores go on to the sort, and `whole_digit` says they are all scores with a key >= T,
+// more than K of them (T is then the lowest key of the digit: the bits below it are zero).
+struct SelCut {
+  unsigned T, ties, ncand;
+  bool whole_digit;
+};
+
+// Exact radix select of the K-th largest eligible score of a row (0 < K < eligible) on score_key, by the whole workgroup:
+// three passes over digits of 11, 11 and 10 bits.  A pass counts, in an LDS histogram (ds_add_u32; integer counts commute), the
+// digit of every score whose key matches the prefix fixed so far, then walks the digits downwards to the one that holds the
+// rank-th largest.  `sweep(tally)` calls tally(j, v) for every column j of the row with its score v, in any order.
+// STOP > 0 ends the select after a pass (not the last) when everything from the digit it has just fixed upwards is at most
+// STOP scores: there is nothing to refine when all of them fit the caller's sort (the usual case of a small K in a long row:
+// one sweep instead of three).  STOP == 0: no early stop, and neither its LDS word nor its compare exist.
+template <unsigned STOP, typename Row, typename Sweep>
+__device__ __forceinline__ SelCut radix_select(SelLds* lds, const Row& row, unsigned K, Sweep sweep) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned* hist = lds->hist;
+  unsigned* uslot = lds->uslot;
+  SelCut cut = {0u, 0u, K, false};
+  unsigned prefix = 0u, mask = 0u, rank = K;     // the rank-th largest of the scores whose key matches prefix under mask
+#pragma unroll 1
+  for (int pass = 0; pass < 3; ++pass) {
+    const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
+    const unsigned dmask = pass == 2 ? 0x3ffu : 0x7ffu;
+    for (int i = tid; i < kSelBins; i += 256) hist[i] = 0u;
+    __syncthreads();
+    sweep([&](int j, float v) {
+      if (!row.eligible(j)) return;
+      const unsigned key = score_key(v);
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & dmask], 1u);
+    });
+    __syncthreads();
+    // thread t owns digits 2047 - 8 t down to 2040 - 8 t; an inclusive scan over the threads walks the digits downwards
+    const int top = kSelBins - 1 - 8 * tid;
+    unsigned c[8], mysum = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      c[i] = hist[top - i];
+      mysum += c[i];
+    }
+    unsigned incl = mysum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned y = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += y;
+    }
+    if (lane == 63) uslot[wave] = incl;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) incl += uslot[w];
+    unsigned above = incl - mysum;               // matching scores in the digits above this thread's
+    if (above < rank && rank <= incl) {          // exactly one thread: the counts below rank are monotone
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (above + c[i] >= rank) {
+          uslot[4] = (unsigned)(top - i);
+          uslot[5] = rank - above;
+          if (STOP) uslot[6] = above + c[i];     // matching scores down to and including this digit
+          break;
+        }
+        above += c[i];
+      }
+    }
+    __syncthreads();
+    // K - rank scores lie above the prefix group, uslot[6] more from this digit upwards inside it.  Uniform: every operand
+    // comes from LDS.
+    const unsigned from_here_up = STOP ? (K - rank) + uslot[6] : 0u;
+    prefix |= uslot[4] << shift;
+    mask |= dmask << shift;
+    rank = uslot[5];
+    if (STOP && pass < 2 && from_here_up <= STOP) {
+      cut.whole_digit = true;
+      cut.ncand = from_here_up;
+      break;
+    }
+  }
+  cut.T = prefix;
+  cut.ties = rank;
+  return cut;
+}
+
+// ---------------------------------------------------------------------------------------------- cohort statistics
 // One workgroup per row of a panel of scores [rows, ldp]: mean and population standard deviation of the K largest eligible
-// scores of the row (K = top_k, or all of them for top_k == 0, capped by the number of eligible columns; a column j is
-// eligible unless la[row] == lb[j]).  Selection is an exact radix select on score_key: three digit histograms in LDS
-// (ds_add_u32; integer counts commute) fix the key T of the K-th largest score and how many copies of it belong to the
-// top K; the sums then take every score above T and that many copies of T.  Mean and centred sum of squares are
-// accumulated in double, thread-strided and combined in a fixed order, and rounded once.
+// scores of the row (K = top_k, or all of them for top_k == 0, capped by the number of eligible columns).  radix_select fixes
+// the key T of the K-th largest score and how many copies of it belong to the top K; the sums then take every score above T
+// and that many copies of T.  Mean and centred sum of squares are accumulated in double, thread-strided and combined in a
+// fixed order, and rounded once.
 template <bool STAGE>
 __global__ __launch_bounds__(256) void cohort_select_kernel(const float* __restrict__ panel, int64_t ldp, int m,
                                                             const int32_t* __restrict__ la, const int32_t* __restrict__ lb,
                                                             int top_k, float* __restrict__ mean, float* __restrict__ stdv,
                                                             int32_t* __restrict__ count) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sel_raw[];
-  unsigned* hist = reinterpret_cast<unsigned*>(sel_raw);                 // [kSelBins]
-  double* dslot = reinterpret_cast<double*>(hist + kSelBins);            // [8]
-  unsigned* uslot = reinterpret_cast<unsigned*>(dslot + 8);              // [8]: 0-3 wave sums, 4 digit found, 5 rank left in it
-  float* stage = reinterpret_cast<float*>(uslot + 8);                    // [m] when STAGE
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  SelLds* lds = reinterpret_cast<SelLds*>(sel_raw);
+  const int tid = threadIdx.x;
   const int64_t r = blockIdx.x;
-  const float* src = panel + r * ldp;
-  if (STAGE) {
-    for (int j = tid; j < m; j += 256) stage[j] = src[j];
-    __syncthreads();
-  }
-  auto val = [&](int j) { return STAGE ? stage[j] : src[j]; };
-  const bool excl = la != nullptr;
-  const int32_t mine = excl ? la[r] : 0;
-  auto eligible = [&](int j) { return !excl || lb[j] != mine; };
-
-  unsigned elig = (unsigned)m;
-  if (excl) {
-    unsigned c = 0;
-    for (int j = tid; j < m; j += 256) c += lb[j] != mine ? 1u : 0u;
-    elig = block_sum(c, uslot);
-  }
-  const unsigned K = top_k > 0 && (unsigned)top_k < elig ? (unsigned)top_k : elig;
+  const SelRow<STAGE> row(lds, panel, ldp, m, la, lb);
+  const unsigned elig = row.elig;
+  const unsigned K = top_k > 0 && (unsigned)top_k < elig ? (unsigned)top_k : elig;      // top_k == 0: all of them
   if (K == 0) {                                  // uniform: nothing to take the statistics of
     if (tid == 0) {
       mean[r] = __builtin_nanf("");
@@ -524,80 +628,35 @@ __global__ __launch_bounds__(256) void cohort_select_kernel(const float* __restr
   }
 
   const bool all = K == elig;
-  unsigned T = 0u, ties = 0u;                    // key of the K-th largest score; copies of it inside the top K
+  SelCut cut = {};
   if (!all) {
-    unsigned prefix = 0u, mask = 0u, rank = K;   // the rank-th largest of the scores whose key matches prefix under mask
-#pragma unroll 1
-    for (int pass = 0; pass < 3; ++pass) {
-      const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
-      const unsigned dmask = pass == 2 ? 0x3ffu : 0x7ffu;
-      for (int i = tid; i < kSelBins; i += 256) hist[i] = 0u;
-      __syncthreads();
-      for (int j = tid; j < m; j += 256) {
-        if (!eligible(j)) continue;
-        const unsigned key = score_key(val(j));
-        if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & dmask], 1u);
-      }
-      __syncthreads();
-      // thread t owns digits 2047 - 8 t down to 2040 - 8 t; an inclusive scan over the threads walks the digits downwards
-      const int top = kSelBins - 1 - 8 * tid;
-      unsigned c[8], mysum = 0u;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        c[i] = hist[top - i];
-        mysum += c[i];
-      }
-      unsigned incl = mysum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-      }
-      if (lane == 63) uslot[wave] = incl;
-      __syncthreads();
-      for (int w = 0; w < wave; ++w) incl += uslot[w];
-      unsigned above = incl - mysum;             // matching scores in the digits above this thread's
-      if (above < rank && rank <= incl) {        // exactly one thread: the counts below rank are monotone
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          if (above + c[i] >= rank) {
-            uslot[4] = (unsigned)(top - i);
-            uslot[5] = rank - above;
-            break;
-          }
-          above += c[i];
-        }
-      }
-      __syncthreads();
-      prefix |= uslot[4] << shift;
-      mask |= dmask << shift;
-      rank = uslot[5];
-    }
-    T = prefix;
-    ties = rank;
+    cut = radix_select<0u>(lds, row, K, [&](auto tally) {
+      for (int j = tid; j < m; j += 256) tally(j, row.val(j));
+    });
   }
+  const unsigned T = cut.T, ties = cut.ties;
   const double tval = (double)score_unkey(T);
 
   double acc = 0.0;
   for (int j = tid; j < m; j += 256) {
-    if (!eligible(j)) continue;
-    const float v = val(j);
+    if (!row.eligible(j)) continue;
+    const float v = row.val(j);
     if (all || score_key(v) > T) acc += (double)v;
   }
-  double total = block_sum(acc, dslot);
+  double total = block_sum(acc, lds->dslot);
   if (!all) total += (double)ties * tval;
   const double mu = total / (double)K;
 
   acc = 0.0;
   for (int j = tid; j < m; j += 256) {
-    if (!eligible(j)) continue;
-    const float v = val(j);
+    if (!row.eligible(j)) continue;
+    const float v = row.val(j);
     if (all || score_key(v) > T) {
       const double dv = (double)v - mu;
       acc = fma(dv, dv, acc);
     }
   }
-  double ss = block_sum(acc, dslot + 4);
+  double ss = block_sum(acc, lds->dslot + 4);
   if (!all) ss += (double)ties * ((tval - mu) * (tval - mu));
   if (tid == 0) {
     mean[r] = (float)mu;
@@ -607,7 +666,6 @@ __global__ __launch_bounds__(256) void cohort_select_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------- top-K search
-constexpr int kTopkMax = 1024;                // keys of the LDS sort: 8 KB, the bytes of the digit histogram they take over
 constexpr int kTopkChunk = 128;               // keys one wave sorts in registers: two per lane
 
 // compare-exchange steps j = 64 .. 1 of the bitonic merges k = k_lo .. k_hi (powers of two, k_lo <= k_hi) on the 128 keys a
@@ -635,9 +693,9 @@ __device__ __forceinline__ void topk_sort_local(unsigned long long& x0, unsigned
 // One workgroup per row of a panel of scores [rows, ldp]: the K = min(top_k, eligible) largest eligible scores of the row and
 // their columns, by score descending and by column ascending among equal scores (a column j is eligible unless
 // la[row] == lb[j]); positions K .. top_k - 1 get -inf / -1.  Four steps:
-//  1. the radix select of cohort_select_kernel fixes the key T of the K-th largest score and how many copies of it (`ties`)
-//     belong to the top K.  It stops early when everything from the digit it has just fixed upwards is at most 1024 scores:
-//     those are then all candidates (`whole_digit`, more than K of them) and the sort picks the K best, ties included;
+//  1. radix_select fixes the key T of the K-th largest score and how many copies of it (`ties`) belong to the top K.  It stops
+//     early when everything from the digit it has just fixed upwards is at most 1024 scores: those are then all candidates
+//     (`whole_digit`, more than K of them) and the sort picks the K best, ties included;
 //  2. an ordered compaction: wave w owns the w-th quarter of the columns and walks it in column order, so a ballot and a count
 //     of the lower lanes (v_mbcnt) number the hits of a walk.  A first walk counts per wave, a prefix over the four counts
 //     gives every wave its base, a second walk writes the 64-bit key (score_key << 32 | ~column) of every score above T and
@@ -657,32 +715,17 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
                                                           const int32_t* __restrict__ la, const int32_t* __restrict__ lb,
                                                           int top_k, float* __restrict__ scores, int32_t* __restrict__ index,
                                                           int64_t ldo, int32_t* __restrict__ count, int vec) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char topk_raw[];
-  unsigned* hist = reinterpret_cast<unsigned*>(topk_raw);                          // [kSelBins], step 1
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(topk_raw);      // [kTopkMax], steps 2-4
-  static_assert(kTopkMax * sizeof(unsigned long long) <= kSelBins * sizeof(unsigned), "the keys reuse the histogram");
-  unsigned* uslot = hist + kSelBins + 16;                                          // [8], where kSelFixedBytes has them
-  float* stage = reinterpret_cast<float*>(uslot + 8);                              // [m] when STAGE
+  extern __shared__ __attribute__((aligned(16))) unsigned char sel_raw[];
+  SelLds* lds = reinterpret_cast<SelLds*>(sel_raw);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(lds->hist);     // [kTopkMax], steps 2-4
+  unsigned* uslot = lds->uslot;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t r = blockIdx.x;
-  const float* src = panel + r * ldp;
-  if (STAGE) {
-    for (int j = tid; j < m; j += 256) stage[j] = src[j];
-    __syncthreads();
-  }
-  auto val = [&](int j) { return STAGE ? stage[j] : src[j]; };
-  const bool excl = la != nullptr;
-  const int32_t mine = excl ? la[r] : 0;
-  auto eligible = [&](int j) { return !excl || lb[j] != mine; };
-
-  unsigned elig = (unsigned)m;
-  if (excl) {
-    unsigned c = 0;
-    for (int j = tid; j < m; j += 256) c += lb[j] != mine ? 1u : 0u;
-    elig = block_sum(c, uslot);
-  }
-  const unsigned K = (unsigned)top_k < elig ? (unsigned)top_k : elig;
+  const SelRow<STAGE> row(lds, panel, ldp, m, la, lb);
+  const float* src = row.src;
+  const unsigned elig = row.elig;
+  const unsigned K = (unsigned)top_k < elig ? (unsigned)top_k : elig;              // top_k >= 1
   float* out_s = scores + r * ldo;
   int32_t* out_i = index + r * ldo;
   if (tid == 0 && count) count[r] = (int32_t)K;
@@ -695,22 +738,9 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
   }
 
   const bool all = K == elig;
-  unsigned T = 0u, ties = 0u;                    // key of the K-th largest score; copies of it inside the top K
-  unsigned ncand = K;                            // keys that go into the sort
-  bool whole_digit = false;                      // the candidates are all scores with a key >= T, more than K of them
-  if (!all) {
-    unsigned prefix = 0u, mask = 0u, rank = K;   // the rank-th largest of the scores whose key matches prefix under mask
-#pragma unroll 1
-    for (int pass = 0; pass < 3; ++pass) {
-      const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
-      const unsigned dmask = pass == 2 ? 0x3ffu : 0x7ffu;
-      for (int i = tid; i < kSelBins; i += 256) hist[i] = 0u;
-      __syncthreads();
-      auto tally = [&](int j, float v) {
-        if (!eligible(j)) return;
-        const unsigned key = score_key(v);
-        if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & dmask], 1u);
-      };
+  SelCut cut = {0u, 0u, K, false};               // all: every eligible score goes into the sort
+  if (!all) {                                    // step 1
+    cut = radix_select<(unsigned)kTopkMax>(lds, row, K, [&](auto tally) {
       if (!STAGE && vec) {                       // a long row in global memory: four 16-byte loads in flight per thread
         const sf32x4* src4 = reinterpret_cast<const sf32x4*>(src);
         const int m4 = m >> 2;
@@ -732,57 +762,13 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
         }
         for (int j = 4 * m4 + tid; j < m; j += 256) tally(j, src[j]);
       } else {
-        for (int j = tid; j < m; j += 256) tally(j, val(j));
+        for (int j = tid; j < m; j += 256) tally(j, row.val(j));
       }
-      __syncthreads();
-      // thread t owns digits 2047 - 8 t down to 2040 - 8 t; an inclusive scan over the threads walks the digits downwards
-      const int top = kSelBins - 1 - 8 * tid;
-      unsigned c[8], mysum = 0u;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        c[i] = hist[top - i];
-        mysum += c[i];
-      }
-      unsigned incl = mysum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-      }
-      if (lane == 63) uslot[wave] = incl;
-      __syncthreads();
-      for (int w = 0; w < wave; ++w) incl += uslot[w];
-      unsigned above = incl - mysum;             // matching scores in the digits above this thread's
-      if (above < rank && rank <= incl) {        // exactly one thread: the counts below rank are monotone
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          if (above + c[i] >= rank) {
-            uslot[4] = (unsigned)(top - i);
-            uslot[5] = rank - above;
-            uslot[6] = above + c[i];             // matching scores down to and including this digit
-            break;
-          }
-          above += c[i];
-        }
-      }
-      __syncthreads();
-      // K - rank scores lie above the prefix group, uslot[6] more from this digit upwards inside it.  When all of them fit
-      // the sort there is nothing to refine: take every score from this digit upwards and let the sort find the K best
-      // (the usual case of a small K in a long row: one sweep instead of three).  Uniform: every operand comes from LDS.
-      const unsigned from_here_up = (K - rank) + uslot[6];
-      prefix |= uslot[4] << shift;
-      mask |= dmask << shift;
-      rank = uslot[5];
-      if (pass < 2 && from_here_up <= (unsigned)kTopkMax) {
-        whole_digit = true;
-        ncand = from_here_up;
-        break;
-      }
-    }
-    T = prefix;                                  // whole_digit: the lowest key of the digit (the bits below it are zero)
-    ties = rank;
+    });
     __syncthreads();                             // uslot and the histogram are rewritten below
   }
+  const unsigned T = cut.T, ties = cut.ties, ncand = cut.ncand;
+  const bool whole_digit = cut.whole_digit;
 
   // step 2: wave w owns columns [w * seg, (w + 1) * seg), seg a multiple of 1024.  A walk takes 64 columns at a time, one per
   // lane, or, for a long row in global memory, 1024 at a time as four 16-byte loads per lane (lane l holds columns
@@ -792,7 +778,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
   const int c_lo = (int)(wave * seg < m ? wave * seg : m), c_hi = (int)((wave + 1) * seg < m ? (wave + 1) * seg : m);
   auto classify = [&](int j, float v, bool& g, bool& e) {
     g = e = false;
-    if (j < c_hi && eligible(j)) {
+    if (j < c_hi && row.eligible(j)) {
       const unsigned key = score_key(v);
       g = all || (whole_digit ? key >= T : key > T);
       e = !all && !whole_digit && key == T;
@@ -850,7 +836,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
     for (int j0 = (!STAGE && vec) ? (c_lo > (c_hi & ~3) ? c_lo : (c_hi & ~3)) : c_lo; j0 < c_hi; j0 += 64) {
       bool g, e;
       const int j = j0 + lane;
-      const float v = j < c_hi ? val(j) : 0.f;
+      const float v = j < c_hi ? row.val(j) : 0.f;
       classify(j, v, g, e);
       const unsigned long long bg = __ballot(g), be = __ballot(e);
       if (write) place(j, v, g, e, below(bg), below(be));
@@ -910,7 +896,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
     int32_t c = -1;
     if (p < (int)K) {
       c = (int32_t)~(unsigned)keys[p];
-      s = val(c);
+      s = row.val(c);
     }
     out_s[p] = s;
     out_i[p] = c;
@@ -927,61 +913,78 @@ hipError_t launch_score_prepare_rows(const float* x, int64_t ldx, int64_t rows, 
   return hipGetLastError();
 }
 
-static void tile_counts(ScoreArgs& p) {
-  p.nMt = (p.n + SBM - 1) / SBM;
-  p.nNt = (p.m + SBN - 1) / SBN;
+// operands of a tile launch: rows a [n, d] against rows b [m, d]; everything an epilogue wants is left zero
+static ScoreArgs score_args(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d) {
+  ScoreArgs p = {};
+  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = d;
+  p.nMt = (n + SBM - 1) / SBM;
+  p.nNt = (m + SBN - 1) / SBN;
+  return p;
+}
+
+// the matrix epilogues: EPI_AFFINE when the operands ask for it, EPI_PLDA (`plda`: the biases of p, either may be null) or
+// EPI_MATRIX; up to 16 workgroups per CU walk the tiles
+static hipError_t launch_matrix_tiles(const ScoreArgs& p, bool plda, hipStream_t s) {
+  int cus = 0;
+  const hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+  const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
+  if (p.a_sub || p.b_offset) return launch_tiles_v<EPI_AFFINE>(p, grid, kOperandBytes, s);
+  if (plda) return launch_tiles_v<EPI_PLDA>(p, grid, kOperandBytes + kBiasBytes, s);
+  return launch_tiles_v<EPI_MATRIX>(p, grid, kOperandBytes, s);
+}
+
+// the histogram epilogues, over the cosine (PLDA false) or the biased score: counts in LDS while 2 * nbins of them fit
+template <bool PLDA>
+static hipError_t launch_histogram_tiles(const ScoreArgs& p, hipStream_t s) {
+  int cus = 0;
+  const hipError_t e = compute_units(&cus);
+  if (e != hipSuccess) return e;
+  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
+  const bool in_lds = p.nbins <= kScoreLdsBins;
+  const size_t smem = kOperandBytes + kLabelBytes + (PLDA ? kBiasBytes : 0) + (in_lds ? (size_t)2 * p.nbins * sizeof(unsigned) : 0);
+  const int per_cu = smem * 2 <= 160 * 1024 ? 2 : 1;
+  int64_t grid = (int64_t)cus * per_cu;
+  // a workgroup's LDS counters are 32 bits wide: at most 2^16 tiles of 2^14 scores each per workgroup
+  if (in_lds && (ntiles + grid - 1) / grid > 65536) grid = (ntiles + 65535) / 65536;
+  if (grid > ntiles) grid = ntiles;
+  if (in_lds) return launch_tiles_v<PLDA ? EPI_PLDA_HIST_LDS : EPI_HIST_LDS>(p, (unsigned)grid, smem, s);
+  return launch_tiles_v<PLDA ? EPI_PLDA_HIST_GLOBAL : EPI_HIST_GLOBAL>(p, (unsigned)grid, smem, s);
+}
+
+template <bool PLDA>
+static hipError_t launch_pairs(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
+                               const float* col_bias, int d, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
+                               hipStream_t s) {
+  if (npairs <= 0) return hipSuccess;
+  const bool vec = aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
+  const auto kernel = vec ? score_pairs_kernel<true, PLDA> : score_pairs_kernel<false, PLDA>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((npairs + 15) / 16)), dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out,
+                     row_bias, col_bias);
+  return hipGetLastError();
 }
 
 hipError_t launch_score_matrix(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d,
                                const float* a_sub, int b_offset, float* out, int64_t ldo, hipStream_t s) {
   if (n <= 0 || m <= 0) return hipSuccess;
-  ScoreArgs p = {};
-  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = d;
+  ScoreArgs p = score_args(a, lda, n, b, ldb, m, d);
   p.C = out; p.ldc = ldo; p.a_sub = a_sub; p.b_offset = b_offset;
-  tile_counts(p);
-  int cus = 0;
-  hipError_t e = compute_units(&cus);
-  if (e != hipSuccess) return e;
-  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
-  const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
-  if (a_sub || b_offset) return launch_tiles_v<EPI_AFFINE>(p, grid, kOperandBytes, s);
-  return launch_tiles_v<EPI_MATRIX>(p, grid, kOperandBytes, s);
+  return launch_matrix_tiles(p, false, s);
 }
 
 hipError_t launch_score_histogram(const float* a, int64_t lda, int n, const int32_t* la, const float* b, int64_t ldb, int m,
                                   const int32_t* lb, int d, int self, int nbins, unsigned long long* hs,
                                   unsigned long long* hd, hipStream_t s) {
   if (n <= 0 || m <= 0) return hipSuccess;
-  ScoreArgs p = {};
-  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = d;
+  ScoreArgs p = score_args(a, lda, n, b, ldb, m, d);
   p.la = la; p.lb = lb; p.self = self; p.nbins = nbins; p.hs = hs; p.hd = hd;
-  tile_counts(p);
-  int cus = 0;
-  hipError_t e = compute_units(&cus);
-  if (e != hipSuccess) return e;
-  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
-  const bool in_lds = nbins <= kScoreLdsBins;
-  const size_t smem = kOperandBytes + kLabelBytes + (in_lds ? (size_t)2 * nbins * sizeof(unsigned) : 0);
-  const int per_cu = smem * 2 <= 160 * 1024 ? 2 : 1;
-  int64_t grid = (int64_t)cus * per_cu;
-  // a workgroup's LDS counters are 32 bits wide: at most 2^16 tiles of 2^14 scores each per workgroup
-  if (in_lds && (ntiles + grid - 1) / grid > 65536) grid = (ntiles + 65535) / 65536;
-  if (grid > ntiles) grid = ntiles;
-  if (in_lds) return launch_tiles_v<EPI_HIST_LDS>(p, (unsigned)grid, smem, s);
-  return launch_tiles_v<EPI_HIST_GLOBAL>(p, (unsigned)grid, smem, s);
+  return launch_histogram_tiles<false>(p, s);
 }
 
 hipError_t launch_score_pairs(const float* a, int64_t lda, int n, const float* b, int64_t ldb, int m, int d, const int32_t* ia,
                               const int32_t* ib, int64_t npairs, float* out, hipStream_t s) {
-  if (npairs <= 0) return hipSuccess;
-  const bool vec = aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-  const dim3 grid((unsigned)((npairs + 15) / 16));
-  const float* none = nullptr;
-  if (vec)
-    hipLaunchKernelGGL((score_pairs_kernel<true, false>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out, none, none);
-  else
-    hipLaunchKernelGGL((score_pairs_kernel<false, false>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out, none, none);
-  return hipGetLastError();
+  return launch_pairs<false>(a, lda, n, nullptr, b, ldb, m, nullptr, d, ia, ib, npairs, out, s);
 }
 
 // ---------------------------------------------------------------------------------------------- PLDA launches
@@ -997,55 +1000,28 @@ hipError_t launch_plda_rows(const float* u, int64_t ldu, int64_t rows, int d, in
 hipError_t launch_plda_matrix(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
                               const float* col_bias, int k, float* out, int64_t ldo, hipStream_t s) {
   if (n <= 0 || m <= 0) return hipSuccess;
-  ScoreArgs p = {};
-  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
+  ScoreArgs p = score_args(a, lda, n, b, ldb, m, k);
   p.C = out; p.ldc = ldo; p.row_bias = row_bias; p.col_bias = col_bias;
-  tile_counts(p);
-  int cus = 0;
-  hipError_t e = compute_units(&cus);
-  if (e != hipSuccess) return e;
-  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
-  const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
-  return launch_tiles_v<EPI_PLDA>(p, grid, kOperandBytes + kBiasBytes, s);
+  return launch_matrix_tiles(p, true, s);
 }
 
 hipError_t launch_plda_histogram(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
                                  int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, double lo, double hi,
                                  int nbins, unsigned long long* hs, unsigned long long* hd, hipStream_t s) {
   if (n <= 0 || m <= 0) return hipSuccess;
-  ScoreArgs p = {};
-  p.A = a; p.lda = lda; p.n = n; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
+  ScoreArgs p = score_args(a, lda, n, b, ldb, m, k);
   p.la = la; p.lb = lb; p.self = 0; p.nbins = nbins; p.hs = hs; p.hd = hd;
   p.row_bias = row_bias; p.col_bias = col_bias; p.lo = lo; p.bin_scale = (double)nbins / (hi - lo);
-  tile_counts(p);
-  int cus = 0;
-  hipError_t e = compute_units(&cus);
-  if (e != hipSuccess) return e;
-  const int64_t ntiles = (int64_t)p.nMt * p.nNt;
-  const bool in_lds = nbins <= kScoreLdsBins;
-  const size_t smem = kOperandBytes + kLabelBytes + kBiasBytes + (in_lds ? (size_t)2 * nbins * sizeof(unsigned) : 0);
-  const int per_cu = smem * 2 <= 160 * 1024 ? 2 : 1;
-  int64_t grid = (int64_t)cus * per_cu;
-  if (in_lds && (ntiles + grid - 1) / grid > 65536) grid = (ntiles + 65535) / 65536;      // 32-bit LDS counters, as above
-  if (grid > ntiles) grid = ntiles;
-  if (in_lds) return launch_tiles_v<EPI_PLDA_HIST_LDS>(p, (unsigned)grid, smem, s);
-  return launch_tiles_v<EPI_PLDA_HIST_GLOBAL>(p, (unsigned)grid, smem, s);
+  return launch_histogram_tiles<true>(p, s);
 }
 
 hipError_t launch_plda_pairs(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
                              const float* col_bias, int k, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
                              hipStream_t s) {
-  if (npairs <= 0) return hipSuccess;
-  const bool vec = aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-  const dim3 grid((unsigned)((npairs + 15) / 16));
-  if (vec)
-    hipLaunchKernelGGL((score_pairs_kernel<true, true>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, k, ia, ib, npairs, out, row_bias, col_bias);
-  else
-    hipLaunchKernelGGL((score_pairs_kernel<false, true>), grid, dim3(256), 0, s, a, lda, n, b, ldb, m, k, ia, ib, npairs, out, row_bias, col_bias);
-  return hipGetLastError();
+  return launch_pairs<true>(a, lda, n, row_bias, b, ldb, m, col_bias, k, ia, ib, npairs, out, s);
 }
 
-// ---------------------------------------------------------------------------------------------- cohort launches
+// ---------------------------------------------------------------------------------------------- panel launches
 static int64_t cohort_panel_ld(int64_t m) { return m < 4 ? 4 : (m + 3) / 4 * 4; }
 
 int64_t cohort_stats_workspace_bytes(int64_t n, int64_t m) {
@@ -1053,96 +1029,61 @@ int64_t cohort_stats_workspace_bytes(int64_t n, int64_t m) {
   return (int64_t)SBM * cohort_panel_ld(m) * (int64_t)sizeof(float);
 }
 
-hipError_t launch_cohort_stats(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
-                               int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* mean,
-                               float* stdv, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s) {
+int64_t score_topk_workspace_bytes(int64_t n, int64_t m) { return cohort_stats_workspace_bytes(n, m); }
+
+// The panel walk of launch_cohort_stats and launch_score_topk: as many whole tile rows of scores as the workspace holds
+// are written as a panel [rows, ldp] (rows padded to 4 floats), by the epilogue xv_score_matrix / xv_plda_matrix would use,
+// so the panel holds the bits those calls would write; then select(panel, ldp, rows, r0, stage, sel_smem) launches one
+// workgroup per panel row on rows r0 .. r0 + rows - 1, with the row staged in LDS (`stage`) when it fits.
+template <typename Select>
+static hipError_t walk_panels(const float* a, int64_t lda, int n, const float* row_bias, const float* b, int64_t ldb, int m,
+                              const float* col_bias, int k, void* ws, int64_t ws_bytes, hipStream_t s, Select select) {
   if (n <= 0) return hipSuccess;
   const int64_t ldp = cohort_panel_ld(m);
   int64_t prows = ws_bytes / (ldp * (int64_t)sizeof(float)) / SBM * SBM;      // whole tile rows per panel
   const int64_t nceil = ((int64_t)n + SBM - 1) / SBM * SBM;
   if (prows > nceil) prows = nceil;
   if (prows < SBM) return hipErrorInvalidValue;                              // the caller checked ws_bytes
-  int cus = 0;
-  hipError_t e = compute_units(&cus);
-  if (e != hipSuccess) return e;
   float* panel = static_cast<float*>(ws);
   const bool stage = m <= kSelStageMax;
   const size_t sel_smem = kSelFixedBytes + (stage ? (size_t)m * sizeof(float) : 0);
   for (int64_t r0 = 0; r0 < n; r0 += prows) {
     const int rows = (int)(n - r0 < prows ? n - r0 : prows);
     if (m > 0) {
-      ScoreArgs p = {};
-      p.A = a + r0 * lda; p.lda = lda; p.n = rows; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
+      ScoreArgs p = score_args(a + r0 * lda, lda, rows, b, ldb, m, k);
       p.C = panel; p.ldc = ldp;
       p.row_bias = row_bias ? row_bias + r0 : nullptr; p.col_bias = col_bias;
-      tile_counts(p);
-      const int64_t ntiles = (int64_t)p.nMt * p.nNt;
-      const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
-      // the epilogues of xv_score_matrix / xv_plda_matrix: the panel holds the bits those calls would write
-      e = (row_bias || col_bias) ? launch_tiles_v<EPI_PLDA>(p, grid, kOperandBytes + kBiasBytes, s)
-                                 : launch_tiles_v<EPI_MATRIX>(p, grid, kOperandBytes, s);
+      const hipError_t e = launch_matrix_tiles(p, row_bias || col_bias, s);
       if (e != hipSuccess) return e;
     }
-    const int32_t* lar = la ? la + r0 : nullptr;
-    int32_t* cnt = count ? count + r0 : nullptr;
-    if (stage)
-      hipLaunchKernelGGL((cohort_select_kernel<true>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
-                         mean + r0, stdv + r0, cnt);
-    else
-      hipLaunchKernelGGL((cohort_select_kernel<false>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
-                         mean + r0, stdv + r0, cnt);
-    e = hipGetLastError();
+    select(panel, ldp, rows, r0, stage, sel_smem);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-// ---------------------------------------------------------------------------------------------- top-K launches
-int64_t score_topk_workspace_bytes(int64_t n, int64_t m) { return cohort_stats_workspace_bytes(n, m); }
+hipError_t launch_cohort_stats(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
+                               int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* mean,
+                               float* stdv, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s) {
+  return walk_panels(a, lda, n, row_bias, b, ldb, m, col_bias, k, ws, ws_bytes, s,
+                     [&](const float* panel, int64_t ldp, int rows, int64_t r0, bool stage, size_t sel_smem) {
+    const auto kernel = stage ? cohort_select_kernel<true> : cohort_select_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, la ? la + r0 : nullptr, lb, top_k,
+                       mean + r0, stdv + r0, count ? count + r0 : nullptr);
+  });
+}
 
 hipError_t launch_score_topk(const float* a, int64_t lda, int n, const float* row_bias, const int32_t* la, const float* b,
                              int64_t ldb, int m, const float* col_bias, const int32_t* lb, int k, int top_k, float* scores,
                              int32_t* index, int64_t ldo, int32_t* count, void* ws, int64_t ws_bytes, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  const int64_t ldp = cohort_panel_ld(m);
-  int64_t prows = ws_bytes / (ldp * (int64_t)sizeof(float)) / SBM * SBM;      // whole tile rows per panel
-  const int64_t nceil = ((int64_t)n + SBM - 1) / SBM * SBM;
-  if (prows > nceil) prows = nceil;
-  if (prows < SBM) return hipErrorInvalidValue;                              // the caller checked ws_bytes
-  int cus = 0;
-  hipError_t e = compute_units(&cus);
-  if (e != hipSuccess) return e;
-  float* panel = static_cast<float*>(ws);
-  const bool stage = m <= kSelStageMax;
-  const size_t sel_smem = kSelFixedBytes + (stage ? (size_t)m * sizeof(float) : 0);
   const int vec = aligned16(ws) ? 1 : 0;         // panel rows are padded to 4 floats: 16-byte loads when the base allows
-  for (int64_t r0 = 0; r0 < n; r0 += prows) {
-    const int rows = (int)(n - r0 < prows ? n - r0 : prows);
-    if (m > 0) {
-      ScoreArgs p = {};
-      p.A = a + r0 * lda; p.lda = lda; p.n = rows; p.B = b; p.ldb = ldb; p.m = m; p.d = k;
-      p.C = panel; p.ldc = ldp;
-      p.row_bias = row_bias ? row_bias + r0 : nullptr; p.col_bias = col_bias;
-      tile_counts(p);
-      const int64_t ntiles = (int64_t)p.nMt * p.nNt;
-      const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
-      // the epilogues of xv_score_matrix / xv_plda_matrix: the panel holds the bits those calls would write
-      e = (row_bias || col_bias) ? launch_tiles_v<EPI_PLDA>(p, grid, kOperandBytes + kBiasBytes, s)
-                                 : launch_tiles_v<EPI_MATRIX>(p, grid, kOperandBytes, s);
-      if (e != hipSuccess) return e;
-    }
-    const int32_t* lar = la ? la + r0 : nullptr;
-    int32_t* cnt = count ? count + r0 : nullptr;
-    if (stage)
-      hipLaunchKernelGGL((topk_select_kernel<true>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
-                         scores + r0 * ldo, index + r0 * ldo, ldo, cnt, vec);
-    else
-      hipLaunchKernelGGL((topk_select_kernel<false>), dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, lar, lb, top_k,
-                         scores + r0 * ldo, index + r0 * ldo, ldo, cnt, vec);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return walk_panels(a, lda, n, row_bias, b, ldb, m, col_bias, k, ws, ws_bytes, s,
+                     [&](const float* panel, int64_t ldp, int rows, int64_t r0, bool stage, size_t sel_smem) {
+    const auto kernel = stage ? topk_select_kernel<true> : topk_select_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(256), sel_smem, s, panel, ldp, m, la ? la + r0 : nullptr, lb, top_k,
+                       scores + r0 * ldo, index + r0 * ldo, ldo, count ? count + r0 : nullptr, vec);
+  });
 }
 
 }  // namespace xv

@@ -140,24 +140,38 @@ TOPK_WORKSPACE_PANELS = 4               # or this many panels when they are larg
 _topk_ws = {}                           # device -> uint8 tensor, kept between calls and grown on demand
 
 
-def topk_workspace_min_bytes(n, m, top_k=1):
-    """The least workspace for n rows against a gallery of m: one 128-row panel of m scores."""
-    need = int(_lib.load().xv_score_topk_workspace(int(n), int(m), int(top_k)))
+def _workspace_min_bytes(entry, n, m, top_k):
+    """The panel entry points' workspace query (`entry`: xv_cohort_stats_workspace or xv_score_topk_workspace)."""
+    need = int(getattr(_lib.load(), entry)(int(n), int(m), int(top_k)))
     if need < 0:
-        raise _lib.XvError(need, "xv_score_topk_workspace: bad dimensions")
+        raise _lib.XvError(need, "%s: bad dimensions" % entry)
     return need
 
 
-def _label_ids(labels_a, labels_b, n, m):
+def topk_workspace_min_bytes(n, m, top_k=1):
+    """The least workspace for n rows against a gallery of m: one 128-row panel of m scores."""
+    return _workspace_min_bytes("xv_score_topk_workspace", n, m, top_k)
+
+
+def _label_ids(labels_a, labels_b, n, m, name_a="labels_a", name_b="labels_b"):
+    """Exclusion labels of both sides (anything np.unique sorts) -> two int32 id arrays, or None, None."""
     if (labels_a is None) != (labels_b is None):
-        raise ValueError("labels_a and labels_b are given together or not at all")
+        raise ValueError("%s and %s are given together or not at all" % (name_a, name_b))
     if labels_a is None:
         return None, None
     la, lb = np.asarray(labels_a).reshape(-1), np.asarray(labels_b).reshape(-1)
     if la.shape[0] != n or lb.shape[0] != m:
-        raise ValueError("labels_a: %d for %d rows, labels_b: %d for %d rows" % (la.shape[0], n, lb.shape[0], m))
+        raise ValueError("%s: %d for %d rows, %s: %d for %d rows" % (name_a, la.shape[0], n, name_b, lb.shape[0], m))
     ids = np.unique(np.concatenate([la, lb]), return_inverse=True)[1].astype(np.int32)
     return np.ascontiguousarray(ids[:n]), np.ascontiguousarray(ids[n:])
+
+
+def _panel_args(torch, device, dev, row_bias, ids_a, col_bias, ids_b):
+    """What xv_cohort_stats and xv_score_topk take beside their operands: the id arrays uploaded to `dev` -> (row_bias,
+    labels_a, col_bias, labels_b), each a pointer or None, the current stream, and the uploads (to keep until the call)."""
+    held = [None if ids is None else torch.from_numpy(ids).to(dev) for ids in (ids_a, ids_b)]
+    rb, la, cb, lb = (None if t is None else _p(t) for t in (row_bias, held[0], col_bias, held[1]))
+    return rb, la, cb, lb, C.c_void_p(torch.cuda.current_stream(device).cuda_stream), held
 
 
 def _top_k(ad, lda, n, row_bias, bd, ldb, m, col_bias, d, k, ids_a, ids_b, device, as_tensor):
@@ -178,13 +192,9 @@ def _top_k(ad, lda, n, row_bias, bd, ldb, m, col_bias, d, k, ids_a, ids_b, devic
             ws = _topk_ws.get(device)
             if ws is None or ws.numel() < want:
                 _topk_ws[device] = ws = torch.empty((want,), dtype=torch.uint8, device=dev)
-            lad = None if ids_a is None else torch.from_numpy(ids_a).to(dev)
-            lbd = None if ids_b is None else torch.from_numpy(ids_b).to(dev)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.xv_score_topk(device, _p(ad), lda, n, None if row_bias is None else _p(row_bias),
-                                         None if lad is None else _p(lad), _p(bd), ldb, m,
-                                         None if col_bias is None else _p(col_bias), None if lbd is None else _p(lbd), d, k,
-                                         _p(scores), _p(indices), k, _p(count), _p(ws), ws.numel(), C.c_void_p(stream)))
+            rb, la, cb, lb, stream, held = _panel_args(torch, device, dev, row_bias, ids_a, col_bias, ids_b)
+            _lib.check(lib.xv_score_topk(device, _p(ad), lda, n, rb, la, _p(bd), ldb, m, cb, lb, d, k,
+                                         _p(scores), _p(indices), k, _p(count), _p(ws), ws.numel(), stream))
         if as_tensor:
             return TopK(scores, indices, count)
         return TopK(scores.cpu().numpy(), indices.cpu().numpy(), count.cpu().numpy())

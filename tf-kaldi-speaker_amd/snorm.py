@@ -18,7 +18,6 @@ Definitions (include/xvec_hip.h states the same):
 
 No CPU path: cohort_stats and plda_cohort_stats raise RuntimeError without a HIP device; normalize is host arithmetic."""
 import collections
-import ctypes as C
 
 import numpy as np
 
@@ -32,22 +31,11 @@ DEFAULT_WORKSPACE_BYTES = 64 << 20
 
 def workspace_min_bytes(n, m, top_k=0):
     """The least `workspace_bytes` for n rows against a cohort of m: one 128-row panel of m scores."""
-    need = int(_lib.load().xv_cohort_stats_workspace(int(n), int(m), int(top_k)))
-    if need < 0:
-        raise _lib.XvError(need, "xv_cohort_stats_workspace: bad dimensions")
-    return need
+    return scoring._workspace_min_bytes("xv_cohort_stats_workspace", n, m, top_k)
 
 
 def _label_ids(labels, cohort_labels, n, m):
-    if (labels is None) != (cohort_labels is None):
-        raise ValueError("labels and cohort_labels are given together or not at all")
-    if labels is None:
-        return None, None
-    la, lb = np.asarray(labels).reshape(-1), np.asarray(cohort_labels).reshape(-1)
-    if la.shape[0] != n or lb.shape[0] != m:
-        raise ValueError("labels: %d for %d rows, cohort_labels: %d for %d rows" % (la.shape[0], n, lb.shape[0], m))
-    ids = np.unique(np.concatenate([la, lb]), return_inverse=True)[1].astype(np.int32)
-    return np.ascontiguousarray(ids[:n]), np.ascontiguousarray(ids[n:])
+    return scoring._label_ids(labels, cohort_labels, n, m, "labels", "cohort_labels")
 
 
 def _stats(ad, lda, n, row_bias, bd, ldb, m, col_bias, k, top_k, ids_a, ids_b, workspace_bytes, device, as_tensor):
@@ -70,14 +58,10 @@ def _stats(ad, lda, n, row_bias, bd, ldb, m, col_bias, k, top_k, ids_a, ids_b, w
                 workspace_bytes = max(need, min((n + 127) // 128 * 128 * per_row, DEFAULT_WORKSPACE_BYTES // need * need))
             workspace_bytes = int(workspace_bytes)
             ws = torch.empty((max(workspace_bytes, 1),), dtype=torch.uint8, device=dev)
-            lad = None if ids_a is None else torch.from_numpy(ids_a).to(dev)
-            lbd = None if ids_b is None else torch.from_numpy(ids_b).to(dev)
-            stream = torch.cuda.current_stream(device).cuda_stream
             p = scoring._p
-            _lib.check(lib.xv_cohort_stats(device, p(ad), lda, n, None if row_bias is None else p(row_bias),
-                                           None if lad is None else p(lad), p(bd), ldb, m,
-                                           None if col_bias is None else p(col_bias), None if lbd is None else p(lbd), k, top_k,
-                                           p(mean), p(std), p(count), p(ws), workspace_bytes, C.c_void_p(stream)))
+            rb, la, cb, lb, stream, held = scoring._panel_args(torch, device, dev, row_bias, ids_a, col_bias, ids_b)
+            _lib.check(lib.xv_cohort_stats(device, p(ad), lda, n, rb, la, p(bd), ldb, m, cb, lb, k, top_k,
+                                           p(mean), p(std), p(count), p(ws), workspace_bytes, stream))
         if as_tensor:
             return CohortStats(mean, std, count)
         return CohortStats(mean.cpu().numpy(), std.cpu().numpy(), count.cpu().numpy())
