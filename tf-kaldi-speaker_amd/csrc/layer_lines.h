@@ -10,9 +10,9 @@
 //    the mask is the forward's.  gz = a * s_j (gz = a without batch norm).
 //  * The column sums of the two mask kernels (seg_mask_kernel, tc_mask_kernel): lane l of the wave that owns column j adds the
 //    rows i = l (mod 64) in ascending order to three doubles, a (gbeta), double(a) * (double(r_j) * (double(z) - double(mm_j)))
-//    (ggamma) and gz (gbias); wave_sum_f64, a fixed xor butterfly over the 64 lanes, closes a sum before its one rounding.  The
-//    two kernel bodies stay apart: which rows are live, gz^T and where the lane sums go differ, and so does what the compiler
-//    makes of them.
+//    (ggamma) and gz (gbias); wave_sum_f64 (csrc/wave_reduce.h), a fixed xor butterfly over the 64 lanes, closes a sum before
+//    its one rounding.  The two kernel bodies stay apart: which rows are live, gz^T and where the lane sums go differ, and so
+//    does what the compiler makes of them.
 //
 // Error bound (u = 2^-24; checked per element in tests/test_gpu_seg_grad.py and tests/test_gpu_tconv.py, restated in
 // ref_seg_grad.bounds).  |.| of the float64 oracle's values; Bz is the caller's bound of z_ij, n the rows summed; t = 2^-53
@@ -28,6 +28,7 @@
 //   gbias_j:   sum_i Bg + (u + t) sum_i |gz_ij|
 #pragma once
 
+#include "wave_reduce.h"
 #include "xv_kernels.h"
 
 namespace xv {
@@ -43,12 +44,6 @@ __device__ __forceinline__ float act_y(float h, int act) {
 }
 __device__ __forceinline__ float act_grad(float g, float h, int act) {
   return act == XV_SEG_ACT_NONE ? g : (h > 0.f ? g : (act == XV_SEG_ACT_RELU ? 0.f : __fmul_rn(0.2f, g)));
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 }  // namespace lines

@@ -13,17 +13,14 @@
 //    (w / sqrt(max(sum w^2, 1e-12)), the sum in double: a column of any fp32 magnitude neither overflows nor flushes, a
 //    zero column stays zero), left raw for softmax.  64 classes per workgroup through an LDS transpose: reads run along
 //    C, writes along E.
-//  * loss_rows_kernel: one wave per row.  ||x_i|| from the row scaled by the power of two of its largest element (exact,
-//    as row_prepare_kernel of csrc/score.hip) with the squares summed in double; the target product x_i . w_label, the
-//    cosine, phi and the target logit in double, rounded once.  A margin multiplies an error of the cosine by |phi'|
-//    (16 for m = 4, unbounded for the additive angle as |cos t| -> 1), so the one logit that goes through phi is not taken
-//    from the fp32 tile.  A label outside [0, C) is never followed: the row gets NaN and a flag word is raised, which
-//    xv_loss_classifier reads back BEFORE the tile kernel is launched and turns into XV_ERR_INVALID.
-//  * loss_tile_kernel: z = x . rows^T with v_mfma_f32_32x32x2_f32, the tile skeleton of score_tile_kernel (csrc/score.hip:
-//    128 x 128 per workgroup, 64 x 64 per wave, K = E taken whole in steps of 32, [row][32 + 4] floats in LDS,
-//    register-staged double buffering, zero-filled edges, groups of eight tile rows).  The epilogue writes the tile (+ bias)
-//    over the operand buffers as [128][144] floats and reduces every row with 16 lanes: lane s owns the columns
-//    s, s + 16, ... , s + 112.  Per (row, tile) it leaves four words in the workspace: the largest logit M with the target
+//  * loss_rows_kernel: one wave per row.  ||x_i||, the target product x_i . w_label, the cosine, phi and the target logit in
+//    double by the lines of csrc/loss_head.h (which the gradient shares), rounded once.  A margin multiplies an error of the
+//    cosine by |phi'| (16 for m = 4, unbounded for the additive angle as |cos t| -> 1), so the one logit that goes through phi
+//    is not taken from the fp32 tile.  A label outside [0, C) is never followed: the row gets NaN and a flag word is raised,
+//    which xv_loss_classifier reads back BEFORE the tile kernel is launched and turns into XV_ERR_INVALID.
+//  * loss_tile_kernel: z = x . rows^T, the exact-fp32 tile product of csrc/nt_gemm.h at 128 x 128 per workgroup, K = E taken
+//    whole, tiles walked in the order of ntg::nt_tile.  The epilogue writes the tile (+ bias) over the operand buffers as
+//    [128][144] floats and reduces every row with 16 lanes: lane s owns the columns s, s + 16, ... , s + 112.  Per (row, tile) it leaves four words in the workspace: the largest logit M with the target
 //    swapped in (only the tile that owns column labels[i] sees the swap), S = sum_c exp(z_c - M), the largest logit before
 //    the margin and its lowest column.  Columns >= C take no part.
 //  * loss_finish_kernel: one wave per row; lane l merges the tiles l, l + 64, ... in ascending order, then a fixed xor
@@ -44,61 +41,19 @@
 //           logf 2 ulp = 4 u |log S| with 0 <= log S <= ln C (the largest term is exp(0)); lse = M + log S and
 //           loss = lse - target one rounding each of at most u |lse| + u |loss|: 4 + 4 + 1 + 11 + 5 + ceil(T / 64) + 2 + 3 spare.
 //   loss:   the sum of the target and the lse bounds.
-#include <mutex>
-
-#include "xv_kernels.h"
+#include "loss_head.h"
+#include "nt_gemm.h"
 
 namespace xv {
 
-typedef float lf32x16 __attribute__((ext_vector_type(16)));
-typedef float lf32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int LBM = 128, LBN = 128, LBK = 32;
-constexpr int LLDT = LBK + 4;                 // padded LDS row (floats): conflict-free ds_read_b128, see csrc/gemm_f32.hip
-constexpr int LTILE_F = LBM * LLDT;           // floats per operand tile
-constexpr int LGROUP = 8;                     // tile rows per group of the tile order
+constexpr int LBM = 128, LBN = 128;           // the tile of a workgroup
 constexpr int LLDZ = 144;                     // row of the logit tile in LDS: 128 * 144 floats = the four operand tiles exactly
-constexpr size_t kLossOperandBytes = (size_t)4 * LTILE_F * sizeof(float);
+constexpr size_t kLossOperandBytes = ntg::nt_smem_bytes<LBM, LBN>();
 constexpr size_t kLossRowBytes = (size_t)LBM * (sizeof(int32_t) + sizeof(float));     // labels and targets of the tile
 constexpr int kLossHeaderBytes = 256;         // flag word in front of the partials
-static_assert(LBM * LLDZ == 4 * LTILE_F, "the logit tile reuses the operand buffers");
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) { return __builtin_bit_cast(float, dpp_i<CTRL>(__builtin_bit_cast(int, x))); }
-
-// reductions over the 16 lanes of a DPP row, the result in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1],
-// row_half_mirror, row_mirror (the order of dpp_row_sum16 in csrc/score.hip)
-__device__ __forceinline__ float row16_sum(float x) {
-  x += dpp_f<0xB1>(x);
-  x += dpp_f<0x4E>(x);
-  x += dpp_f<0x141>(x);
-  x += dpp_f<0x140>(x);
-  return x;
-}
-__device__ __forceinline__ float row16_max(float x) {
-  x = fmaxf(x, dpp_f<0xB1>(x));
-  x = fmaxf(x, dpp_f<0x4E>(x));
-  x = fmaxf(x, dpp_f<0x141>(x));
-  x = fmaxf(x, dpp_f<0x140>(x));
-  return x;
-}
-__device__ __forceinline__ int row16_min(int x) {
-  x = min(x, dpp_i<0xB1>(x));
-  x = min(x, dpp_i<0x4E>(x));
-  x = min(x, dpp_i<0x141>(x));
-  x = min(x, dpp_i<0x140>(x));
-  return x;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+static_assert(LBM * LLDZ * sizeof(float) == kLossOperandBytes, "the logit tile reuses the operand buffers");
 
 // ---------------------------------------------------------------------------------------------- class rows
 // kernel [E, ldk >= C] -> rows [C, ldr >= E]; 64 classes per workgroup, lane = class while reading, lane = e while writing
@@ -143,15 +98,6 @@ __global__ __launch_bounds__(256) void loss_classes_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------- rows
-struct LossHead {
-  int head;                 // XV_LOSS_*
-  int m;                    // asoftmax: 1, 2 or 4
-  double margin;            // additive margin
-  double cos_m, sin_m;      // additive angular margin: cos m, sin m and cos(pi - m), from the host in double
-  double cos_pi_m;
-  double fa;                // 1 / (1 + lambda); 0 switches the margin off (asoftmax m = 1, softmax)
-};
-
 __global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int E,
                                                         const int32_t* __restrict__ labels, const float* __restrict__ rows,
                                                         int64_t ldr, int64_t C, const float* __restrict__ bias, LossHead hp,
@@ -167,58 +113,12 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict_
     }
     return;
   }
-  const float* xr = x + r * ldx;
-  const float* wr = rows + (int64_t)lab * ldr;
-  float mx = 0.f;
-  double dot = 0.0;
-  for (int c = lane; c < E; c += 64) {
-    mx = fmaxf(mx, fabsf(xr[c]));
-    dot = fma((double)xr[c], (double)wr[c], dot);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  dot = wave_sum_f64(dot);
-  double t;
-  if (hp.head == XV_LOSS_SOFTMAX) {
-    t = dot + (bias ? (double)bias[lab] : 0.0);
-  } else {
-    double xn = 0.0;
-    if (mx > 0.f && mx <= 3.4028234e38f) {
-      const int e = ilogbf(mx);                       // row * 2^-e has its largest element in [1, 2): exact scaling
-      double ss = 0.0;
-      for (int c = lane; c < E; c += 64) {
-        const double v = (double)ldexpf(xr[c], -e);
-        ss = fma(v, v, ss);
-      }
-      xn = ldexp(sqrt(wave_sum_f64(ss)), e);
-    } else if (mx != 0.f) {
-      xn = (double)mx;                                // inf / nan rows: passed on
-    }
-    const double fn = xn > 1e-12 ? xn : 1e-12;        // tf.maximum(tf.norm(features, axis=1), eps)
-    double c = dot / fn;
-    c = c < -1.0 + 1e-12 ? -1.0 + 1e-12 : (c > 1.0 - 1e-12 ? 1.0 - 1e-12 : c);
-    double phi = c;
-    if (hp.head == XV_LOSS_ASOFTMAX) {
-      const double s0 = c > 0.0 ? 1.0 : (c < 0.0 ? -1.0 : 0.0);
-      const double c2 = c * c;
-      if (hp.m == 2) {
-        phi = 2.0 * s0 * c2 - 1.0;                    // model/loss.py:159
-      } else if (hp.m == 4) {                         // model/loss.py:161-166
-        const double q = 2.0 * c2 - 1.0;
-        const double s3 = (q > 0.0 ? 1.0 : (q < 0.0 ? -1.0 : 0.0)) * s0;
-        const double s4 = 2.0 * s0 + s3 - 3.0;
-        phi = s3 * (8.0 * c2 * c2 - 8.0 * c2 + 1.0) + s4;
-      }
-    } else if (hp.head == XV_LOSS_AMSOFTMAX) {
-      phi = c - hp.margin;                            // model/loss.py:254
-    } else {                                          // model/loss.py:343-352
-      const double s2 = 1.0 - c * c;
-      const double sn = sqrt(s2 > 1e-12 ? s2 : 1e-12);
-      const double cpm = c * hp.cos_m - sn * hp.sin_m;
-      phi = c > hp.cos_pi_m ? cpm : -cpm - 2.0;
-    }
-    t = hp.fa == 0.0 ? dot : (1.0 - hp.fa) * dot + hp.fa * (phi * fn);
-  }
+  const HeadRow row = head_row(x + r * ldx, rows + (int64_t)lab * ldr, E, lane, hp.fa != 0.0);     // csrc/loss_head.h
+  double t = row.dot;
+  if (hp.head == XV_LOSS_SOFTMAX)
+    t = row.dot + (bias ? (double)bias[lab] : 0.0);
+  else if (hp.fa != 0.0)
+    t = head_target(hp, row, head_phi(hp, row.c, nullptr));
   if (lane == 0) target[r] = (float)t;
 }
 
@@ -237,120 +137,39 @@ struct LossArgs {
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void loss_tile_kernel(LossArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                    // [2][LBM][LLDT]
-  float* Bs = smem + 2 * LTILE_F;      // [2][LBN][LLDT]
-  float* Z = smem;                     // [LBM][LLDZ], the epilogue's view of the same floats
-  int32_t* lab = reinterpret_cast<int32_t*>(smem + 4 * LTILE_F);          // [LBM]
+  float* Z = smem;                     // [LBM][LLDZ], the epilogue's view of the operand tiles
+  int32_t* lab = reinterpret_cast<int32_t*>(smem + LBM * LLDZ);           // [LBM]
   float* tgt = reinterpret_cast<float*>(lab + LBM);                       // [LBM]
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r32 = lane & 31, h = lane >> 5;
-  const int c4 = tid & 7, lr = tid >> 3;          // staging map: thread -> (row lr + 32*i, float4 column c4)
-  const int nk = (p.d + LBK - 1) / LBK;
-
   const int64_t ntiles = (int64_t)p.nMt * p.nNt;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    // groups of LGROUP tile rows, walked column by column
-    const int64_t per_group = (int64_t)LGROUP * p.nNt;
-    const int g = (int)(t / per_group);
-    const int gm = min(LGROUP, p.nMt - g * LGROUP);
-    const int64_t tg = t - g * per_group;
-    const int nt = (int)(tg / gm);
-    const int mt = g * LGROUP + (int)(tg - (int64_t)nt * gm);
-    const int m0 = mt * LBM, n0 = nt * LBN;
-
-    lf32x4 ra[4], rb[4];
-    auto load_rows = [&](const float* base, int64_t ld, int row0, int nrows, int kt, lf32x4 (&r)[4]) {
-      const int k = kt * LBK + c4 * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = row0 + lr + 32 * i;
-        lf32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row < nrows && k < p.d) {
-          const float* src = base + (int64_t)row * ld + k;
-          if (VEC && k + 4 <= p.d) {
-            v = *reinterpret_cast<const lf32x4*>(src);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (k + e < p.d) v[e] = src[e];
-          }
-        }
-        r[i] = v;
-      }
-    };
-    auto load_tiles = [&](int kt) {
-      load_rows(p.A, p.lda, m0, p.n, kt, ra);
-      load_rows(p.B, p.ldb, n0, p.m, kt, rb);
-    };
-    auto store_tiles = [&](int buf) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = lr + 32 * i;
-        *reinterpret_cast<lf32x4*>(As + buf * LTILE_F + row * LLDT + c4 * 4) = ra[i];
-        *reinterpret_cast<lf32x4*>(Bs + buf * LTILE_F + row * LLDT + c4 * 4) = rb[i];
-      }
-    };
-
-    lf32x16 acc[2][2];                 // acc[ai][bi]: 32 A rows x 32 B rows
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    int mt, nt;
+    ntg::nt_tile(t, p.nMt, p.nNt, mt, nt);
+    const ntg::NtPos<LBM, LBN> at(mt, nt);
+    const int m0 = at.m0, n0 = at.n0;
 
     if (tid < LBM) {
       const bool ok = m0 + tid < p.n;
       lab[tid] = ok ? p.labels[m0 + tid] : -1;
       tgt[tid] = ok ? p.target[m0 + tid] : 0.f;
     }
-    load_tiles(0);
-    store_tiles(0);
-    __syncthreads();
 
-    const float* a_base = As + (wm * 64 + r32) * LLDT + 4 * h;
-    const float* b_base = Bs + (wn * 64 + r32) * LLDT + 4 * h;
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) load_tiles(kt + 1);
-      const float* ap = a_base + cur * LTILE_F;
-      const float* bp = b_base + cur * LTILE_F;
-#pragma unroll
-      for (int q = 0; q < LBK / 8; ++q) {
-        // the k index of an MFMA is a summation label only: lane (r, h) feeds k = 8q + 4h + j of both operands
-        const lf32x4 a0 = *reinterpret_cast<const lf32x4*>(ap + q * 8);
-        const lf32x4 a1 = *reinterpret_cast<const lf32x4*>(ap + 32 * LLDT + q * 8);
-        const lf32x4 b0 = *reinterpret_cast<const lf32x4*>(bp + q * 8);
-        const lf32x4 b1 = *reinterpret_cast<const lf32x4*>(bp + 32 * LLDT + q * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b0[j], acc[0][0], 0, 0, 0);
-          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b1[j], acc[0][1], 0, 0, 0);
-          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b0[j], acc[1][0], 0, 0, 0);
-          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b1[j], acc[1][1], 0, 0, 0);
-        }
-      }
-      if (kt + 1 < nk) store_tiles(cur ^ 1);
-      __syncthreads();
-    }
+    ntg::gf32x16 acc[2][2];            // acc[ai][bi]: 32 A rows x 32 B rows
+    ntg::nt_acc_start(acc, at);
+    // its first barrier publishes the labels and targets too
+    ntg::nt_mainloop<LBM, LBN, VEC>(p.A, p.lda, p.n, p.B, p.ldb, p.m, p.d, m0, n0, acc, smem);
 
-    // The operand tiles are dead (the loop ends on a barrier): the logits go over them.  Accumulator layout: element e of
-    // lane (r32, h) is D[8 * (e / 4) + 4 * h + e % 4][r32] (A row, B row).
+    // The operand tiles are dead (the loop ends on a barrier): the logits go over them.
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi) {
-      const int jl = wn * 64 + bi * 32 + r32;
+      const int jl = at.lcol(bi);
       const int gj = n0 + jl;
       const float b = (p.bias && gj < p.m) ? p.bias[gj] : 0.f;
 #pragma unroll
       for (int ai = 0; ai < 2; ++ai)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int il = wm * 64 + ai * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
-          Z[il * LLDZ + jl] = acc[ai][bi][e] + b;
-        }
+        for (int e = 0; e < 16; ++e) Z[at.lrow(ai, e) * LLDZ + jl] = acc[ai][bi][e] + b;
     }
     __syncthreads();
 
@@ -432,27 +251,6 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restric
   }
 }
 
-bool loss_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <bool VEC>
-hipError_t launch_loss_tiles_v(const LossArgs& a, unsigned grid, size_t smem, hipStream_t s) {
-  static std::mutex mu;            // per-device attribute; any thread may make the first launch on a device
-  static bool set_for[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!set_for[dev & 63]) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(loss_tile_kernel<VEC>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return e;
-      set_for[dev & 63] = true;
-    }
-  }
-  hipLaunchKernelGGL((loss_tile_kernel<VEC>), dim3(grid), dim3(256), smem, s, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,
@@ -470,14 +268,7 @@ int64_t loss_workspace_bytes(int64_t n, int64_t C) {
 hipError_t launch_loss_rows(const float* x, int64_t ldx, int64_t n, int E, const int32_t* labels, const float* rows, int64_t ldr,
                             int64_t C, const float* bias, int head, int m, double margin, double fa, float* target, void* ws,
                             hipStream_t s) {
-  LossHead hp = {};
-  hp.head = head;
-  hp.m = m;
-  hp.margin = margin;
-  hp.cos_m = cos(margin);
-  hp.sin_m = sin(margin);
-  hp.cos_pi_m = cos(3.14159265358979323846 - margin);
-  hp.fa = (head == XV_LOSS_SOFTMAX || (head == XV_LOSS_ASOFTMAX && m == 1)) ? 0.0 : fa;
+  const LossHead hp = loss_head(head, m, margin, fa, 0.0);
   int* flag = static_cast<int*>(ws);
   hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
   if (e != hipSuccess) return e;
@@ -497,15 +288,14 @@ hipError_t launch_loss_tiles(const float* x, int64_t ldx, int n, int E, const in
   const int64_t cells = (int64_t)n * p.nNt;
   float* base = reinterpret_cast<float*>(static_cast<char*>(ws) + kLossHeaderBytes);
   p.pm = base; p.ps = base + cells; p.rv = base + 2 * cells; p.ri = reinterpret_cast<int32_t*>(base + 3 * cells);
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int cus = 0;
+  hipError_t e = compute_units(&cus);
   if (e != hipSuccess) return e;
   const int64_t ntiles = (int64_t)p.nMt * p.nNt;
-  const unsigned grid = (unsigned)(ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16);
+  const int64_t grid = ntiles < (int64_t)cus * 16 ? ntiles : (int64_t)cus * 16;
   const size_t smem = kLossOperandBytes + kLossRowBytes;
-  const bool vec = loss_aligned16(x) && loss_aligned16(rows) && ldx % 4 == 0 && ldr % 4 == 0;
-  e = vec ? launch_loss_tiles_v<true>(p, grid, smem, s) : launch_loss_tiles_v<false>(p, grid, smem, s);
+  e = ntg::nt_vec(x, ldx, rows, ldr) ? ntg::nt_launch<loss_tile_kernel<true>>(smem, grid, p, s)
+                                     : ntg::nt_launch<loss_tile_kernel<false>>(smem, grid, p, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(loss_finish_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, p.pm, p.ps, p.rv, p.ri, (int64_t)n, p.nNt,
                      target, loss, lse, top1);

@@ -11,13 +11,11 @@
 //    xv_loss_classifier.  The target goes to the workspace first and is copied out after the label check, so that a bad label
 //    leaves every output untouched.
 //  * grad_label_kernel, one wave per row: the label's entry G_il and the coefficient r_i / ||x_i|| in double from the stored
-//    rows, as loss_rows_kernel evaluates the target: the margin multiplies an error of the cosine by |phi'|, so this one entry
+//    rows, by the lines loss_rows_kernel evaluates the target with (csrc/loss_head.h): the margin multiplies an error of the cosine by |phi'|, so this one entry
 //    does not come from the fp32 tile.
 //  * per PANEL of P rows (P a multiple of 32, at most 1024, as many as the workspace holds), in ascending row order:
-//      - nt_gemm_kernel<EPI_G>: z = x . w^T again with v_mfma_f32_32x32x2_f32 (the tile skeleton of loss_tile_kernel: K in
-//        steps of 32, [row][32 + 4] floats in LDS, register-staged double buffering, zero-filled edges; it lives in
-//        csrc/nt_gemm.h, which csrc/seg_grad.hip shares), G_ic = s expf(z_ic -
-//        lse_i), the entry at column l_i swapped for G_il by the tile that owns it; written as G [P, C] and G^T [C, P];
+//      - nt_gemm_kernel<EPI_G>: z = x . w^T again (the exact-fp32 tile product of csrc/nt_gemm.h), G_ic = s expf(z_ic - lse_i),
+//        the entry at column l_i swapped for G_il by the tile that owns it; written as G [P, C] and G^T [C, P];
 //      - grad_bias: one wave per class, lane l adds the rows i = l (mod 64) of the batch in ascending order to a double that
 //        lives in the workspace between the panels; a fixed butterfly over the 64 lanes after the last panel;
 //      - nt_gemm_kernel<EPI_X>: grad_x_panel = G . (w^T)^T, K = C over a transposed copy of the rows, 64 x 64 tiles (a
@@ -50,6 +48,7 @@
 //   grad_bias_c:    sum_i |dG_ic| + u |grad_bias_c|                                 (double sum, rounded once)
 //   grad_rows_ce:   softmax: a_ce + u |grad_rows_ce|.  Angular: with D = sum_e |w^_ce| a_ce the error of w^_c . gw_c,
 //                   (a_ce + |w^_ce| D) / sqrt(q_c) + 2 u |grad_rows_ce|; below the floor a_ce / 1e-6 + u |grad_rows_ce|.
+#include "loss_head.h"
 #include "nt_gemm.h"
 
 namespace xv {
@@ -62,12 +61,6 @@ namespace {
 
 constexpr int kMaxPanel = 1024;
 constexpr int kPanelStep = 32;                // a panel is a whole number of K steps of the gw product
-
-__device__ __forceinline__ double gwave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------- normalised rows
 // 16 classes per wave, 4 lanes per class: lane k of a class sums e = k, k + 4, ... (the order of loss_classes_kernel)
@@ -94,87 +87,29 @@ __global__ __launch_bounds__(256) void grad_normalize_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------- the label's entry
-struct GradHead {
-  int head, m;
-  double margin, cos_m, sin_m, cos_pi_m, fa;    // fa = 0 switches the margin off (softmax, asoftmax m = 1)
-  double s;                                     // grad_scale
-};
-
 __global__ __launch_bounds__(256) void grad_label_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int E,
                                                          const int32_t* __restrict__ labels, const float* __restrict__ rows,
-                                                         int64_t ldr, const float* __restrict__ bias, GradHead hp,
+                                                         int64_t ldr, const float* __restrict__ bias, LossHead hp,
                                                          const float* __restrict__ lse, float* __restrict__ gl,
                                                          double* __restrict__ coef) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n) return;
   const int32_t lab = labels[r];                  // checked by the forward before this launch
-  const float* xr = x + r * ldx;
-  const float* wr = rows + (int64_t)lab * ldr;
-  float mx = 0.f;
-  double dot = 0.0;
-  for (int c = lane; c < E; c += 64) {
-    mx = fmaxf(mx, fabsf(xr[c]));
-    dot = fma((double)xr[c], (double)wr[c], dot);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  dot = gwave_sum_f64(dot);
+  const HeadRow row = head_row(x + r * ldx, rows + (int64_t)lab * ldr, E, lane, hp.fa != 0.0);     // csrc/loss_head.h
   const double l = (double)lse[r];
   double g, rc = 0.0;
   if (hp.fa == 0.0) {
-    const double t = dot + ((hp.head == XV_LOSS_SOFTMAX && bias) ? (double)bias[lab] : 0.0);
+    const double t = row.dot + ((hp.head == XV_LOSS_SOFTMAX && bias) ? (double)bias[lab] : 0.0);
     g = hp.s * (exp(t - l) - 1.0);
   } else {
-    double xn = 0.0;
-    if (mx > 0.f && mx <= 3.4028234e38f) {
-      const int e = ilogbf(mx);
-      double ss = 0.0;
-      for (int c = lane; c < E; c += 64) {
-        const double v = (double)ldexpf(xr[c], -e);
-        ss = fma(v, v, ss);
-      }
-      xn = ldexp(sqrt(gwave_sum_f64(ss)), e);
-    } else if (mx != 0.f) {
-      xn = (double)mx;
-    }
-    const double fn = xn > 1e-12 ? xn : 1e-12;
-    const double craw = dot / fn;
-    const double lo = -1.0 + 1e-12, hi = 1.0 - 1e-12;
-    const double inside = (craw >= lo && craw <= hi) ? 1.0 : 0.0;      // tf.clip_by_value passes the gradient inside [lo, hi]
-    const double c = craw < lo ? lo : (craw > hi ? hi : craw);
-    double phi = c, dphi = 1.0;
-    if (hp.head == XV_LOSS_ASOFTMAX) {
-      const double s0 = c > 0.0 ? 1.0 : (c < 0.0 ? -1.0 : 0.0);
-      const double c2 = c * c;
-      if (hp.m == 2) {
-        phi = 2.0 * s0 * c2 - 1.0;
-        dphi = 4.0 * fabs(c);
-      } else if (hp.m == 4) {
-        const double qq = 2.0 * c2 - 1.0;
-        const double s3 = (qq > 0.0 ? 1.0 : (qq < 0.0 ? -1.0 : 0.0)) * s0;
-        const double s4 = 2.0 * s0 + s3 - 3.0;
-        phi = s3 * (8.0 * c2 * c2 - 8.0 * c2 + 1.0) + s4;
-        dphi = s3 * (32.0 * c2 * c - 16.0 * c);
-      }
-    } else if (hp.head == XV_LOSS_AMSOFTMAX) {
-      phi = c - hp.margin;
-    } else {
-      const double s2 = 1.0 - c * c;
-      const double sn = sqrt(s2 > 1e-12 ? s2 : 1e-12);
-      const double dsn = s2 > 1e-12 ? -c / sn : 0.0;
-      const double cpm = c * hp.cos_m - sn * hp.sin_m;
-      const double dcpm = hp.cos_m - dsn * hp.sin_m;
-      const bool first = c > hp.cos_pi_m;
-      phi = first ? cpm : -cpm - 2.0;
-      dphi = first ? dcpm : -dcpm;
-    }
-    dphi *= inside;
-    const double t = (1.0 - hp.fa) * dot + hp.fa * (phi * fn);
-    const double d = hp.s * (exp(t - l) - 1.0);
+    double dphi;
+    const double phi = head_phi(hp, row.c, &dphi);
+    dphi *= row.craw == row.c ? 1.0 : 0.0;        // tf.clip_by_value passes the gradient inside the clip range only
+    const double d = hp.s * (exp(head_target(hp, row, phi) - l) - 1.0);
     g = d * ((1.0 - hp.fa) + hp.fa * dphi);
-    const double rr = d * hp.fa * (phi - dphi * craw);
-    rc = xn > 1e-12 ? rr / xn : 0.0;
+    const double rr = d * hp.fa * (phi - dphi * row.craw);
+    rc = row.xn > 1e-12 ? rr / row.xn : 0.0;
   }
   if (lane == 0) {
     gl[r] = (float)g;
@@ -201,46 +136,25 @@ struct NtArgs {
 
 template <int BM, int BN, bool VEC, int EPI>
 __global__ __launch_bounds__(256, 2) void nt_gemm_kernel(NtArgs p) {
-  constexpr int WM = BM / 2, WN = BN / 2;            // per wave
-  constexpr int AI = WM / 32, BI = WN / 32;
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  const ntg::NtPos<BM, BN> at((int)(blockIdx.x % (unsigned)p.nMt), (int)(blockIdx.x / (unsigned)p.nMt));
 
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r32 = lane & 31, h = lane >> 5;
-  const int mt = (int)(blockIdx.x % (unsigned)p.nMt), nt = (int)(blockIdx.x / (unsigned)p.nMt);
-  const int m0 = mt * BM, n0 = nt * BN;
-
-  // accumulator layout: element e of lane (r32, h) is D[8 * (e / 4) + 4 * h + e % 4][r32] (A row, B row)
-  gf32x16 acc[AI][BI];
-#pragma unroll
-  for (int ai = 0; ai < AI; ++ai)
-#pragma unroll
-    for (int bi = 0; bi < BI; ++bi)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float v = 0.f;
-        if (EPI == EPI_ACC && !p.first) {       // the chain over the rows goes on from where the last panel left it
-          const int gi = m0 + wm * WM + ai * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
-          const int gj = n0 + wn * WN + bi * 32 + r32;
-          if (gi < p.M && gj < p.N) v = p.out[(int64_t)gi * p.ldo + gj];
-        }
-        acc[ai][bi][e] = v;
-      }
-
-  ntg::nt_mainloop<BM, BN, VEC>(p.A, p.lda, p.M, p.B, p.ldb, p.N, p.K, m0, n0, acc, smem);      // csrc/nt_gemm.h
+  // EPI_ACC: the chain over the rows goes on from where the last panel left it
+  gf32x16 acc[at.AI][at.BI];
+  ntg::nt_acc_start(acc, at, EPI == EPI_ACC && !p.first, p.out, p.ldo, p.M, p.N);
+  ntg::nt_mainloop<BM, BN, VEC>(p.A, p.lda, p.M, p.B, p.ldb, p.N, p.K, at.m0, at.n0, acc, smem);
 
 #pragma unroll
-  for (int bi = 0; bi < BI; ++bi) {
-    const int gj = n0 + wn * WN + bi * 32 + r32;
+  for (int bi = 0; bi < at.BI; ++bi) {
+    const int gj = at.col(bi);
     const bool jok = gj < p.N;
     float bj = 0.f;
     if (EPI == EPI_G) bj = (p.bias && jok) ? p.bias[gj] : 0.f;
 #pragma unroll
-    for (int ai = 0; ai < AI; ++ai)
+    for (int ai = 0; ai < at.AI; ++ai)
 #pragma unroll
       for (int e4 = 0; e4 < 4; ++e4) {
-        const int gi0 = m0 + wm * WM + ai * 32 + 8 * e4 + 4 * h;
+        const int gi0 = at.row(ai, 4 * e4);
         if (EPI == EPI_G) {
           gf32x4 g4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -285,7 +199,7 @@ __global__ __launch_bounds__(256) void grad_bias_kernel(const float* __restrict_
     gb[c * 64 + lane] = a;
     return;
   }
-  a = gwave_sum_f64(a);
+  a = wave_sum_f64(a);
   if (lane == 0) grad_bias[c] = (float)a;
 }
 
@@ -305,18 +219,14 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const float* __restric
   const double inv = 1.0 / sqrt(qc);
   double dot = 0.0;
   for (int e = lane; e < E; e += 64) dot = fma((double)w[e] * inv, (double)g[e], dot);
-  dot = gwave_sum_f64(dot);
+  dot = wave_sum_f64(dot);
   for (int e = lane; e < E; e += 64) g[e] = (float)(((double)g[e] - ((double)w[e] * inv) * dot) * inv);
 }
 
 template <int BM, int BN, bool VEC, int EPI>
 hipError_t launch_nt(const NtArgs& a, hipStream_t s) {
-  static std::mutex mu;            // per-device attribute; any thread may make the first launch on a device
-  static bool set_for[64] = {};
-  return ntg::nt_launch(nt_gemm_kernel<BM, BN, VEC, EPI>, ntg::nt_smem_bytes<BM, BN>(), mu, set_for, (int64_t)a.nMt * a.nNt, a, s);
+  return ntg::nt_launch<nt_gemm_kernel<BM, BN, VEC, EPI>>(ntg::nt_smem_bytes<BM, BN>(), (int64_t)a.nMt * a.nNt, a, s);
 }
-
-bool grad_aligned16(const void* p) { return ntg::aligned16(p); }
 
 struct GradLayout {
   int64_t ldh, ldt;                 // row of w^ [C, ldh] and of (w^)^T [E, ldt], floats
@@ -392,15 +302,7 @@ hipError_t launch_loss_grad_rest(const float* x, int64_t ldx, int n, int E, cons
   e = hipMemcpyAsync(target, tgt, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) return e;
 
-  GradHead hp = {};
-  hp.head = head;
-  hp.m = m;
-  hp.margin = margin;
-  hp.cos_m = cos(margin);
-  hp.sin_m = sin(margin);
-  hp.cos_pi_m = cos(3.14159265358979323846 - margin);
-  hp.fa = (head == XV_LOSS_SOFTMAX || (head == XV_LOSS_ASOFTMAX && m == 1)) ? 0.0 : fa;
-  hp.s = grad_scale;
+  const LossHead hp = loss_head(head, m, margin, fa, grad_scale);
   hipLaunchKernelGGL(grad_label_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, ldx, (int64_t)n, E, labels, use, ldu, bias,
                      hp, lse, gl, coef);
   if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -421,8 +323,7 @@ hipError_t launch_loss_grad_rest(const float* x, int64_t ldx, int n, int E, cons
     a.nMt = (pn + 127) / 128; a.nNt = (C + 127) / 128;
     a.bias = bias; a.labels = labels + r0; a.lse = lse + r0; a.gl = gl + r0; a.sf = (float)grad_scale;
     a.G = G; a.ldg = L.ldt; a.GT = GT; a.ldgt = P;
-    const bool vec = grad_aligned16(xp) && grad_aligned16(use) && ldx % 4 == 0 && ldu % 4 == 0;
-    e = vec ? launch_nt<128, 128, true, EPI_G>(a, s) : launch_nt<128, 128, false, EPI_G>(a, s);
+    e = ntg::nt_vec(xp, ldx, use, ldu) ? launch_nt<128, 128, true, EPI_G>(a, s) : launch_nt<128, 128, false, EPI_G>(a, s);
     if (e != hipSuccess) return e;
     if (grad_bias) {
       hipLaunchKernelGGL(grad_bias_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, GT, P, pn, r0, (int64_t)C, r0 == 0 ? 1 : 0,

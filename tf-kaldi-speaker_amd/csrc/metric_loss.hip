@@ -45,6 +45,7 @@
 #include <mutex>
 #include <vector>
 
+#include "wave_reduce.h"
 #include "xv_kernels.h"
 
 // Every fused multiply-add of this file is written as fma(): where the rules round a product before it is used (u = x s,
@@ -359,13 +360,6 @@ __global__ __launch_bounds__(kThreads) void panel_kernel(MetricArgs g) {
   }
 }
 
-// sum over the 64 lanes, the same bits in every lane (a + b == b + a)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
@@ -449,7 +443,7 @@ __global__ __launch_bounds__(kThreads) void ge2e_kernel(MetricArgs g) {
         const double v = csum[(int64_t)c * d + t];
         pp = fma(v, v, pp);
       }
-      pp = wave_sum(pp);
+      pp = wave_sum_f64(pp);
       if (lane == 0) cscale[c] = 1.0 / sqrt(fmax(pp, kEps));
     }
     __syncthreads();
@@ -504,13 +498,13 @@ __global__ __launch_bounds__(kThreads) void ge2e_kernel(MetricArgs g) {
         const double wv = own[t] - (double)xi[t] * si;
         pp = fma(wv, wv, pp);
       }
-      const double es = 1.0 / sqrt(fmax(wave_sum(pp), kEps));
+      const double es = 1.0 / sqrt(fmax(wave_sum_f64(pp), kEps));
       pp = 0.0;
       for (int t = lane; t < d; t += 64) {
         const double u = (double)xi[t] * si;
         pp = fma(u, (own[t] - u) * es, pp);
       }
-      const double z_own = g.w * wave_sum(pp) + g.b;
+      const double z_own = g.w * wave_sum_f64(pp) + g.b;
 
       // lane c & 63 keeps the running state of class c
       double lm = -inf, ls = 0.0;          // online log-sum-exp
@@ -531,7 +525,7 @@ __global__ __launch_bounds__(kThreads) void ge2e_kernel(MetricArgs g) {
         if (c != c0) sig = fmax(sig, sigmoid(z));
       }
       const double m = wave_max(lm);
-      const double total = wave_sum(lm > -inf ? ls * exp(lm - m) : 0.0);
+      const double total = wave_sum_f64(lm > -inf ? ls * exp(lm - m) : 0.0);
       const double top = wave_max(best);
       int cand = best == top ? best_c : kMaxRows;       // the earliest class among equals
 #pragma unroll

@@ -39,6 +39,7 @@
 //   |gx^ - gx| <= u |a| + 3 u |b d| + u (|a| + |b d|) + O(u^2) <= u (2 |a| + 4 |b d|)(1 + 2^-20) + 2^-149,
 // where 1 + 2^-20 covers the products of two errors (at most 6 u (|a| + |b d|) u-terms) and 2^-149 a result that the fma
 // rounds into the subnormal range.  A floored channel has b = 0 exactly and gx = a^ bit for bit.
+#include "wave_reduce.h"
 #include "xv_common.h"
 
 namespace xv {
@@ -264,8 +265,6 @@ __global__ __launch_bounds__(256) void stat_pool_bwd_kernel(PoolBwdArgs p) {
   }
 }
 
-bool pg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 hipError_t launch_stat_pool_forward(const float* x, int64_t ldx, int C, const int32_t* offsets, int64_t batch, int64_t total_rows,
@@ -273,7 +272,7 @@ hipError_t launch_stat_pool_forward(const float* x, int64_t ldx, int C, const in
   if (batch <= 0) return hipSuccess;
   const int nCb = (C + kPgChannels - 1) / kPgChannels;
   const dim3 grid((unsigned)(batch * nCb));
-  if (pg_aligned16(x) && ldx % 4 == 0 && C % 4 == 0)
+  if (aligned16(x) && ldx % 4 == 0 && C % 4 == 0)
     hipLaunchKernelGGL(stat_pool_fwd_kernel<true>, grid, dim3(256), 0, s, x, ldx, C, nCb, offsets, total_rows, pooled, ldp, var, ldv);
   else
     hipLaunchKernelGGL(stat_pool_fwd_kernel<false>, grid, dim3(256), 0, s, x, ldx, C, nCb, offsets, total_rows, pooled, ldp, var, ldv);
@@ -285,7 +284,7 @@ hipError_t launch_stat_pool_backward(const float* gp, int64_t ldgp, const float*
                                      int64_t ldv, float* gx, int64_t ldgx, hipStream_t s) {
   if (batch <= 0 || total_rows <= 0) return hipSuccess;
   PoolBwdArgs a = {gp, ldgp, x, ldx, C, offsets, batch, total_rows, pooled, ldp, var, ldv, gx, ldgx};
-  const bool vec = pg_aligned16(x) && pg_aligned16(gx) && ldx % 4 == 0 && ldgx % 4 == 0 && C % 4 == 0;
+  const bool vec = aligned16(x) && aligned16(gx) && ldx % 4 == 0 && ldgx % 4 == 0 && C % 4 == 0;
   const int per = 64 * (vec ? 4 : 1);
   const dim3 grid((unsigned)((total_rows + 4 * kPgRows - 1) / (4 * kPgRows)), (unsigned)((C + per - 1) / per));
   if (vec)

@@ -19,11 +19,9 @@
 //
 //  * row_prepare_kernel: one wave per row; y = x - mean, then y / sqrt(sum y^2 + eps).  The sum of squares is taken of
 //    the row scaled by the power of two of its largest element (exact), so rows of any magnitude neither overflow nor flush.
-//  * score_tile_kernel: C = A * B^T over prepared rows with v_mfma_f32_32x32x2_f32, the tile shape and LDS layout of
-//    csrc/gemm_f32.hip (128 x 128 per workgroup, 64 x 64 per wave, K tiles of 32 in [row][32 + 4] floats, register-staged
-//    double buffering), K = d taken whole.  Unlike the layer GEMM nothing is pre-packed: the loaders zero-fill the edges of
-//    n, m and d themselves.  A workgroup walks tiles with a stride of the grid; tiles are ordered in groups of eight
-//    tile rows so that the workgroups in flight share 8 A panels and ~64 B panels.  Epilogues (compile time):
+//  * score_tile_kernel: C = A * B^T over prepared rows, the exact-fp32 tile product of csrc/nt_gemm.h at 128 x 128 per
+//    workgroup, K = d taken whole.  A workgroup walks tiles with a stride of the grid, in the order of ntg::nt_tile.
+//    Epilogues (compile time):
 //      EPI_MATRIX       fp32 [n, m] with a leading dimension
 //      EPI_AFFINE       the same with a vector subtracted from the A rows at load and column d of B added as an offset
 //                       (ivector-subtract-global-mean + transform-vec of the prepare step)
@@ -59,22 +57,17 @@
 // cohort_select_kernel then sums what lies above the K-th score in one sweep and takes the centred squares in one more, both
 // in double and in a fixed order.  topk_select_kernel lets the select stop as soon as the candidates fit its sort, compacts
 // the hits into LDS in column order and sorts (score, column) keys with a bitonic network.
-#include <mutex>
-
-#include "xv_kernels.h"
+#include "nt_gemm.h"
 
 namespace xv {
 
-typedef float sf32x16 __attribute__((ext_vector_type(16)));
-typedef float sf32x4 __attribute__((ext_vector_type(4)));
+using ntg::gf32x4;
 
 namespace {
 
-constexpr int SBM = 128, SBN = 128, SBK = 32;
-constexpr int SLDT = SBK + 4;                 // padded LDS row (floats): conflict-free ds_read_b128, see csrc/gemm_f32.hip
-constexpr int STILE_F = SBM * SLDT;           // floats per operand tile
-constexpr int SGROUP = 8;                     // tile rows per group of the tile order
-constexpr size_t kOperandBytes = (size_t)4 * STILE_F * sizeof(float);
+constexpr int SBM = 128, SBN = 128;           // the tile of a workgroup
+constexpr size_t kOperandBytes = ntg::nt_smem_bytes<SBM, SBN>();
+constexpr int kOperandFloats = (int)(kOperandBytes / sizeof(float));
 constexpr int kScoreLdsBins = 8192;           // largest bin count whose two uint32 histograms stay in LDS (64 KB) beside the operand tiles
 constexpr size_t kLabelBytes = (size_t)(SBM + SBN) * sizeof(int32_t);
 
@@ -85,14 +78,6 @@ enum { EPI_MATRIX = 0, EPI_AFFINE = 1, EPI_HIST_LDS = 2, EPI_HIST_GLOBAL = 3, EP
 constexpr bool epi_hist(int e) { return e == EPI_HIST_LDS || e == EPI_HIST_GLOBAL || e == EPI_PLDA_HIST_LDS || e == EPI_PLDA_HIST_GLOBAL; }
 constexpr bool epi_hist_lds(int e) { return e == EPI_HIST_LDS || e == EPI_PLDA_HIST_LDS; }
 constexpr bool epi_plda(int e) { return e == EPI_PLDA || e == EPI_PLDA_HIST_LDS || e == EPI_PLDA_HIST_GLOBAL; }
-
-__device__ __forceinline__ float dpp_row_sum16(float x) {       // sum over the 16 lanes of a DPP row, in every lane
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));   // row_mirror
-  return x;
-}
 
 // ---------------------------------------------------------------------------------------------- prepare
 __global__ __launch_bounds__(256) void row_prepare_kernel(const float* __restrict__ x, int64_t ldx, int64_t rows, int dim,
@@ -155,20 +140,13 @@ struct ScoreArgs {
 template <int EPI, bool VEC>
 __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                    // [2][SBM][SLDT]
-  float* Bs = smem + 2 * STILE_F;      // [2][SBN][SLDT]
-  int32_t* lab = reinterpret_cast<int32_t*>(smem + 4 * STILE_F);          // [SBM + SBN] labels of the tile
+  int32_t* lab = reinterpret_cast<int32_t*>(smem + kOperandFloats);       // [SBM + SBN] labels of the tile
   unsigned* hist = reinterpret_cast<unsigned*>(lab + SBM + SBN);          // EPI_HIST_LDS: [2][nbins]
   // PLDA: [SBM + SBN] biases of the tile, behind whatever the epilogue keeps in front of them
-  float* bias = EPI == EPI_PLDA ? smem + 4 * STILE_F
+  float* bias = EPI == EPI_PLDA ? smem + kOperandFloats
                                 : reinterpret_cast<float*>(hist + (EPI == EPI_PLDA_HIST_LDS ? 2 * p.nbins : 0));
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r32 = lane & 31, h = lane >> 5;
-  const int c4 = tid & 7, lr = tid >> 3;          // staging map: thread -> (row lr + 32*i, float4 column c4)
-  const int nk = (p.d + SBK - 1) / SBK;
   const float half_bins = 0.5f * (float)p.nbins;
 
   if (epi_hist_lds(EPI)) {
@@ -178,60 +156,11 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
 
   const int64_t ntiles = (int64_t)p.nMt * p.nNt;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    // groups of SGROUP tile rows, walked column by column
-    const int64_t per_group = (int64_t)SGROUP * p.nNt;
-    const int g = (int)(t / per_group);
-    const int gm = min(SGROUP, p.nMt - g * SGROUP);
-    const int64_t tg = t - g * per_group;
-    const int nt = (int)(tg / gm);
-    const int mt = g * SGROUP + (int)(tg - (int64_t)nt * gm);
+    int mt, nt;
+    ntg::nt_tile(t, p.nMt, p.nNt, mt, nt);
     if (epi_hist(EPI) && p.self && nt < mt) continue;   // strictly below the diagonal (uniform)
-    const int m0 = mt * SBM, n0 = nt * SBN;
-
-    sf32x4 ra[4], rb[4];
-    auto load_rows = [&](const float* base, int64_t ld, int row0, int nrows, int kt, sf32x4 (&r)[4], const float* sub) {
-      const int k = kt * SBK + c4 * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = row0 + lr + 32 * i;
-        sf32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row < nrows && k < p.d) {
-          const float* src = base + (int64_t)row * ld + k;
-          if (VEC && k + 4 <= p.d) {
-            v = *reinterpret_cast<const sf32x4*>(src);
-            if (EPI == EPI_AFFINE && sub) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] -= sub[k + e];
-            }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (k + e < p.d) v[e] = (EPI == EPI_AFFINE && sub) ? src[e] - sub[k + e] : src[e];
-          }
-        }
-        r[i] = v;
-      }
-    };
-    auto load_tiles = [&](int kt) {
-      load_rows(p.A, p.lda, m0, p.n, kt, ra, p.a_sub);
-      load_rows(p.B, p.ldb, n0, p.m, kt, rb, nullptr);
-    };
-    auto store_tiles = [&](int buf) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = lr + 32 * i;
-        *reinterpret_cast<sf32x4*>(As + buf * STILE_F + row * SLDT + c4 * 4) = ra[i];
-        *reinterpret_cast<sf32x4*>(Bs + buf * STILE_F + row * SLDT + c4 * 4) = rb[i];
-      }
-    };
-
-    sf32x16 acc[2][2];                 // acc[ai][bi]: 32 A rows x 32 B rows
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    const ntg::NtPos<SBM, SBN> at(mt, nt);
+    const int m0 = at.m0, n0 = at.n0;
 
     if (epi_hist(EPI) && !epi_plda(EPI)) {
       const int row = tid < SBM ? m0 + tid : n0 + tid - SBM;
@@ -246,40 +175,15 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
       bias[tid] = src && ok ? src[row] : 0.f;
       if (epi_hist(EPI)) lab[tid] = ok ? (rowside ? p.la : p.lb)[row] : 0;
     }
-    load_tiles(0);
-    store_tiles(0);
-    __syncthreads();
 
-    const float* a_base = As + (wm * 64 + r32) * SLDT + 4 * h;
-    const float* b_base = Bs + (wn * 64 + r32) * SLDT + 4 * h;
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) load_tiles(kt + 1);
-      const float* ap = a_base + cur * STILE_F;
-      const float* bp = b_base + cur * STILE_F;
-#pragma unroll
-      for (int q = 0; q < SBK / 8; ++q) {
-        // the k index of an MFMA is a summation label only: lane (r, h) feeds k = 8q + 4h + j of both operands
-        const sf32x4 a0 = *reinterpret_cast<const sf32x4*>(ap + q * 8);
-        const sf32x4 a1 = *reinterpret_cast<const sf32x4*>(ap + 32 * SLDT + q * 8);
-        const sf32x4 b0 = *reinterpret_cast<const sf32x4*>(bp + q * 8);
-        const sf32x4 b1 = *reinterpret_cast<const sf32x4*>(bp + 32 * SLDT + q * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b0[j], acc[0][0], 0, 0, 0);
-          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b1[j], acc[0][1], 0, 0, 0);
-          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b0[j], acc[1][0], 0, 0, 0);
-          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b1[j], acc[1][1], 0, 0, 0);
-        }
-      }
-      if (kt + 1 < nk) store_tiles(cur ^ 1);
-      __syncthreads();
-    }
+    ntg::gf32x16 acc[2][2];            // acc[ai][bi]: 32 A rows x 32 B rows
+    ntg::nt_acc_start(acc, at);
+    // its first barrier publishes the labels / biases too
+    ntg::nt_mainloop<SBM, SBN, VEC, EPI == EPI_AFFINE>(p.A, p.lda, p.n, p.B, p.ldb, p.m, p.d, m0, n0, acc, smem, p.a_sub);
 
-    // accumulator layout: element e of lane (r32, h) is D[8 * (e / 4) + 4 * h + e % 4][r32] (A row, B row)
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi) {
-      const int jl = wn * 64 + bi * 32 + r32;
+      const int jl = at.lcol(bi);
       const int gj = n0 + jl;
       if (gj >= p.m) continue;
       float offs = 0.f;
@@ -292,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
       for (int ai = 0; ai < 2; ++ai)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int il = wm * 64 + ai * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
+          const int il = at.lrow(ai, e);
           const int gi = m0 + il;
           if (gi >= p.n) continue;
           float s = acc[ai][bi][e];
@@ -331,38 +235,10 @@ __global__ __launch_bounds__(256, 2) void score_tile_kernel(ScoreArgs p) {
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <int EPI, bool VEC>
-hipError_t launch_tiles(const ScoreArgs& a, unsigned grid, size_t smem, hipStream_t s) {
-  static std::mutex mu;            // per-device attribute; any thread may make the first launch on a device
-  static size_t set_for[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (set_for[dev & 63] < smem) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(score_tile_kernel<EPI, VEC>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return e;
-      set_for[dev & 63] = smem;
-    }
-  }
-  hipLaunchKernelGGL((score_tile_kernel<EPI, VEC>), dim3(grid), dim3(256), smem, s, a);
-  return hipGetLastError();
-}
-
 template <int EPI>
 hipError_t launch_tiles_v(const ScoreArgs& a, unsigned grid, size_t smem, hipStream_t s) {
-  const bool vec = aligned16(a.A) && aligned16(a.B) && a.lda % 4 == 0 && a.ldb % 4 == 0;
-  return vec ? launch_tiles<EPI, true>(a, grid, smem, s) : launch_tiles<EPI, false>(a, grid, smem, s);
-}
-
-hipError_t compute_units(int* cus) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  return hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return ntg::nt_vec(a.A, a.lda, a.B, a.ldb) ? ntg::nt_launch<score_tile_kernel<EPI, true>>(smem, grid, a, s)
+                                             : ntg::nt_launch<score_tile_kernel<EPI, false>>(smem, grid, a, s);
 }
 
 // ---------------------------------------------------------------------------------------------- pairs
@@ -383,8 +259,8 @@ __global__ __launch_bounds__(256) void score_pairs_kernel(const float* __restric
     const float* y = b + (int64_t)j * ldb;
     for (int c = sub * 4; c < d; c += 64) {
       if (VEC && c + 4 <= d) {
-        const sf32x4 u = *reinterpret_cast<const sf32x4*>(x + c);
-        const sf32x4 v = *reinterpret_cast<const sf32x4*>(y + c);
+        const gf32x4 u = *reinterpret_cast<const gf32x4*>(x + c);
+        const gf32x4 v = *reinterpret_cast<const gf32x4*>(y + c);
         s0 = fmaf(u[0], v[0], s0);
         s1 = fmaf(u[1], v[1], s1);
         s2 = fmaf(u[2], v[2], s2);
@@ -397,19 +273,13 @@ __global__ __launch_bounds__(256) void score_pairs_kernel(const float* __restric
       }
     }
   }
-  float s = dpp_row_sum16((s0 + s1) + (s2 + s3));            // every lane of the wave takes part
+  float s = row16_sum((s0 + s1) + (s2 + s3));            // every lane of the wave takes part
   if (PLDA && ok) s = (s + row_bias[i]) + (col_bias ? col_bias[j] : 0.f);
   if (have && sub == 0) out[k] = ok ? s : __builtin_nanf("");  // an index the host let through is marked, never followed
 }
 
 // ---------------------------------------------------------------------------------------------- PLDA rows
 constexpr int PT_INV = 0, PT_P = 1, PT_Q = 2, PT_W = 3;      // components of a per-n table [4][d] (doubles)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // norm: 0 none, 1 Kaldi's psi-weighted length normalisation (inv table), 2 simple (sqrt(d) / ||u||).
 // side: 0 enrolment (second half of the packed row = W), 1 test (second half = y^2).  Any output may be null; rows == u is allowed.
@@ -432,7 +302,7 @@ __global__ __launch_bounds__(256) void plda_rows_kernel(const float* u, int64_t 
       const double v = (double)ur[c];
       ss = fma(v * v, norm == 1 ? tab[PT_INV * d + c] : 1.0, ss);
     }
-    ss = wave_sum(ss);
+    ss = wave_sum_f64(ss);
     // a zero row stays zero; a row with inf / nan is passed through
     scale = ss > 0.0 ? (ss <= 1.7976931348623157e308 ? sqrt((double)d / ss) : 1.0) : (ss == 0.0 ? 0.0 : 1.0);
   }
@@ -447,7 +317,7 @@ __global__ __launch_bounds__(256) void plda_rows_kernel(const float* u, int64_t 
       if (pack_second) packed[r * ldp + d + c] = side == 0 ? (float)tab[PT_W * d + c] : (float)y2;
     }
   }
-  acc = wave_sum(acc);
+  acc = wave_sum_f64(acc);
   if (bias && lane == 0) bias[r] = (float)((logdet ? logdet[k] : 0.0) + acc);
 }
 
@@ -742,14 +612,14 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
   if (!all) {                                    // step 1
     cut = radix_select<(unsigned)kTopkMax>(lds, row, K, [&](auto tally) {
       if (!STAGE && vec) {                       // a long row in global memory: four 16-byte loads in flight per thread
-        const sf32x4* src4 = reinterpret_cast<const sf32x4*>(src);
+        const gf32x4* src4 = reinterpret_cast<const gf32x4*>(src);
         const int m4 = m >> 2;
         for (int q0 = 0; q0 < m4; q0 += 1024) {
-          sf32x4 v[4];
+          gf32x4 v[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const int q = q0 + u * 256 + tid;
-            v[u] = q < m4 ? src4[q] : sf32x4{0.f, 0.f, 0.f, 0.f};
+            v[u] = q < m4 ? src4[q] : gf32x4{0.f, 0.f, 0.f, 0.f};
           }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
@@ -800,11 +670,11 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
     if (!STAGE && vec) {
       const int a_hi = c_hi & ~3;                // c_lo is a multiple of 4; the last m % 4 columns are walked one by one
       for (int j0 = c_lo; j0 < a_hi; j0 += 1024) {
-        sf32x4 v[4];
+        gf32x4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int j = j0 + u * 256 + 4 * lane;
-          v[u] = j < a_hi ? *reinterpret_cast<const sf32x4*>(src + j) : sf32x4{0.f, 0.f, 0.f, 0.f};
+          v[u] = j < a_hi ? *reinterpret_cast<const gf32x4*>(src + j) : gf32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -905,6 +775,13 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
 
 }  // namespace
 
+hipError_t compute_units(int* cus) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  return hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+}
+
 hipError_t launch_score_prepare_rows(const float* x, int64_t ldx, int64_t rows, int dim, const float* mean, int normalize,
                                      float eps, float* y, int64_t ldy, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
@@ -958,8 +835,7 @@ static hipError_t launch_pairs(const float* a, int64_t lda, int n, const float* 
                                const float* col_bias, int d, const int32_t* ia, const int32_t* ib, int64_t npairs, float* out,
                                hipStream_t s) {
   if (npairs <= 0) return hipSuccess;
-  const bool vec = aligned16(a) && aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-  const auto kernel = vec ? score_pairs_kernel<true, PLDA> : score_pairs_kernel<false, PLDA>;
+  const auto kernel = ntg::nt_vec(a, lda, b, ldb) ? score_pairs_kernel<true, PLDA> : score_pairs_kernel<false, PLDA>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)((npairs + 15) / 16)), dim3(256), 0, s, a, lda, n, b, ldb, m, d, ia, ib, npairs, out,
                      row_bias, col_bias);
   return hipGetLastError();

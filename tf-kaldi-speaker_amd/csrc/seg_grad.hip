@@ -61,17 +61,9 @@ __global__ __launch_bounds__(256, 2) void seg_gemm_kernel(SegGemmArgs p) {
   const int mt = (int)(blockIdx.x % (unsigned)p.nMt), nt = (int)(blockIdx.x / (unsigned)p.nMt);
   const ntg::NtPos<64, 64> at(mt, nt);
 
+  // EPI_ACC: the chain over the rows goes on from where the last panel left it
   gf32x16 acc[1][1];
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    float v = 0.f;
-    if (EPI == EPI_ACC && !p.first) {           // the chain over the rows goes on from where the last panel left it
-      const int gi = at.row(0, e), gj = at.col(0);
-      if (gi < p.M && gj < p.N) v = p.out[(int64_t)gi * p.ldo + gj];
-    }
-    acc[0][0][e] = v;
-  }
-
+  ntg::nt_acc_start(acc, at, EPI == EPI_ACC && !p.first, p.out, p.ldo, p.M, p.N);
   ntg::nt_mainloop<64, 64, VEC>(p.A, p.lda, p.M, p.B, p.ldb, p.N, p.K, at.m0, at.n0, acc, smem);
 
   const int gj = at.col(0);
@@ -102,9 +94,7 @@ __global__ __launch_bounds__(256, 2) void seg_gemm_kernel(SegGemmArgs p) {
 
 template <bool VEC, int EPI>
 hipError_t launch_seg_gemm(const SegGemmArgs& a, hipStream_t s) {
-  static std::mutex mu;            // per-device attribute; any thread may make the first launch on a device
-  static bool set_for[64] = {};
-  return ntg::nt_launch(seg_gemm_kernel<VEC, EPI>, ntg::nt_smem_bytes<64, 64>(), mu, set_for, (int64_t)a.nMt * a.nNt, a, s);
+  return ntg::nt_launch<seg_gemm_kernel<VEC, EPI>>(ntg::nt_smem_bytes<64, 64>(), (int64_t)a.nMt * a.nNt, a, s);
 }
 
 // ---------------------------------------------------------------------------------------------- mask, gz, gz^T, column sums
@@ -203,7 +193,7 @@ __global__ __launch_bounds__(256) void seg_mask_kernel(SegMaskArgs p) {
       p.part[((int64_t)2 * p.N + j) * 64 + lane] = sz[c];
       continue;
     }
-    const double a = lines::wave_sum_f64(sa[c]), g = lines::wave_sum_f64(sg[c]), z = lines::wave_sum_f64(sz[c]);
+    const double a = wave_sum_f64(sa[c]), g = wave_sum_f64(sg[c]), z = wave_sum_f64(sz[c]);
     if (lane == 0) {
       if (bn) {
         p.gbeta[j] = (float)a;
@@ -250,7 +240,7 @@ hipError_t launch_seg_forward(const float* x, int64_t ldx, int n, int K, const f
   a.nMt = (n + 63) / 64; a.nNt = (N + 63) / 64;
   a.bias = bias; a.gamma = gamma; a.beta = beta; a.mm = mm; a.mv = mv; a.act = act;
   a.z = z; a.ldz = ldz; a.y = y; a.ldy = ldy;
-  const bool vec = ntg::aligned16(x) && ntg::aligned16(w) && ldx % 4 == 0 && ldw % 4 == 0;
+  const bool vec = aligned16(x) && aligned16(w) && ldx % 4 == 0 && ldw % 4 == 0;
   return vec ? launch_seg_gemm<true, EPI_FWD>(a, s) : launch_seg_gemm<false, EPI_FWD>(a, s);
 }
 

@@ -446,7 +446,7 @@ __global__ __launch_bounds__(256) void tc_mask_kernel(TcMaskArgs p) {
   for (int c = 0; c < CW; ++c) {
     const int j = j0 + CW * wave + c;
     if (j >= p.N) continue;                                       // uniform over the wave
-    const double a = lines::wave_sum_f64(sa[c]), g = lines::wave_sum_f64(sg[c]), z = lines::wave_sum_f64(sz[c]);
+    const double a = wave_sum_f64(sa[c]), g = wave_sum_f64(sg[c]), z = wave_sum_f64(sz[c]);
     if (lane == 0) {
       p.part[((int64_t)0 * p.N + j) * p.slices + blockIdx.y] = a;
       p.part[((int64_t)1 * p.N + j) * p.slices + blockIdx.y] = g;
@@ -554,7 +554,7 @@ hipError_t launch_tconv_forward(const float* x, int64_t ldx, int C, int W, const
   a.nMt = (int)((total_out + 63) / 64); a.nNt = (N + 63) / 64;
   a.bias = bias; a.gamma = gamma; a.beta = beta; a.mm = mm; a.mv = mv; a.act = act;
   a.z = z; a.ldz = ldz; a.y = y; a.ldy = ldy;
-  const bool vec = ntg::aligned16(x) && ldx % 4 == 0 && C % 4 == 0 && ntg::aligned16(w) && ldw % 4 == 0;
+  const bool vec = aligned16(x) && ldx % 4 == 0 && C % 4 == 0 && aligned16(w) && ldw % 4 == 0;
   return launch_tc_gemm<TC_FWD>(a, vec, 1, s);
 }
 
@@ -586,7 +586,7 @@ hipError_t launch_tconv_backward(const float* gy, int64_t ldgy, const float* x, 
                      gamma ? 1 : 0, gbeta, ggamma, gbias);
   if ((e = hipGetLastError()) != hipSuccess) return e;
 
-  const bool vec_x = ntg::aligned16(x) && ldx % 4 == 0 && C % 4 == 0;
+  const bool vec_x = aligned16(x) && ldx % 4 == 0 && C % 4 == 0;
   TcGemmArgs a = {};
   a.x = x; a.ldx = ldx; a.C = C; a.W = W; a.w = w; a.ldw = ldw; a.N = N;
   a.rowmap = rowmap; a.total_out = total_out; a.info = info; a.total_in = total_in;
@@ -607,7 +607,7 @@ hipError_t launch_tconv_backward(const float* gy, int64_t ldgy, const float* x, 
     TcGemmArgs b = a;
     b.nMt = (int)((total_in + 63) / 64); b.nNt = (C + 63) / 64;
     b.out = gx; b.ldo = ldgx;
-    const bool vec_w = ntg::aligned16(w) && ldw % 4 == 0 && C % 4 == 0;
+    const bool vec_w = aligned16(w) && ldw % 4 == 0 && C % 4 == 0;
     if ((e = launch_tc_gemm<TC_GX>(b, vec_w, 1, s)) != hipSuccess) return e;
   }
   return hipSuccess;

@@ -31,6 +31,7 @@
 #include <mutex>
 #include <vector>
 
+#include "wave_reduce.h"
 #include "xv_kernels.h"
 
 namespace xv {
@@ -83,12 +84,6 @@ struct VbxShared {
 __device__ inline double wave_max(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
@@ -149,13 +144,13 @@ __device__ void vbx_forward(const double* logp, double* lfw, double* lse, int T,
     if (live && t + 1 < T) nxt = logp[(int64_t)(t + 1) * S + j];
     const double m0 = finite_or_zero(wave_max(cur));
     const double e = exp(cur - m0);
-    const double tot = wave_sum(e);
+    const double tot = wave_sum_f64(e);
     if (j == 0) lse[t - 1] = m0 + log(tot);
     cur = live ? (lp + m0) + log(fma(loop, e, w * tot)) : -INFINITY;
     if (live) lfw[(int64_t)t * S + j] = cur;
   }
   const double m0 = finite_or_zero(wave_max(cur));
-  const double tll = m0 + log(wave_sum(exp(cur - m0)));
+  const double tll = m0 + log(wave_sum_f64(exp(cur - m0)));
   if (j == 0) {
     lse[T - 1] = tll;
     sh.tll = tll;
@@ -176,7 +171,7 @@ __device__ void vbx_backward(const double* logp, double* lbw, int T, int S, doub
     const double v = live ? lp + cur : -INFINITY;
     const double m0 = finite_or_zero(wave_max(v));
     const double b = exp(v - m0);
-    const double c = wave_sum(pi_j * b);
+    const double c = wave_sum_f64(pi_j * b);
     cur = m0 + log(fma(loop, b, (1.0 - loop) * c));
     if (live) lbw[(int64_t)t * S + j] = cur;
   }
@@ -335,7 +330,7 @@ __global__ __launch_bounds__(kVbxThreads) void vbx_kernel(VbxArgs a) {
         const double sum = (sh.part[0][lane] + sh.part[1][lane]) + (sh.part[2][lane] + sh.part[3][lane]);
         v = exp((lfw[lane] + lbw[lane]) - tll) + ((1.0 - a.loop) * sh.pi[lane]) * sum;
       }
-      const double total = wave_sum(v);
+      const double total = wave_sum_f64(v);
       sh.pi[lane] = v / total;
       if (lane == 0) {
         double e = 0.0;

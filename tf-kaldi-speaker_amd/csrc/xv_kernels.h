@@ -246,6 +246,7 @@ hipError_t launch_speaker_mean(const float* x, int64_t ldx, int dim, const int32
                                int64_t num_spk, float* out, int64_t ldo, hipStream_t s);
 
 // cosine scoring (csrc/score.hip): egs/voxceleb/v1/run.sh:362-365,404-408 and misc/utils.py:307-346
+hipError_t compute_units(int* cus);     // of the current device: sizes the grids of the persistent tile kernels
 // y = x - mean (mean may be null), then y / sqrt(sum y^2 + eps) when `normalize`; in place (y == x) is allowed
 hipError_t launch_score_prepare_rows(const float* x, int64_t ldx, int64_t rows, int dim, const float* mean, int normalize,
                                      float eps, float* y, int64_t ldy, hipStream_t s);
