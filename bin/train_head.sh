@@ -11,6 +11,7 @@ keep_head=false
 segment_layers=false
 frame_layers=false
 conv_layers=false
+batch_norm=
 
 if [ -f path.sh ]; then . ./path.sh; fi
 if [ -f parse_options.sh ] || command -v parse_options.sh >/dev/null 2>&1; then
@@ -39,6 +40,9 @@ if [ $# != 6 ]; then
   echo "                           # (run the head alone first, then --segment-layers, then this)"
   echo "  --conv-layers <false>    # train every frame-level layer, the multi-tap convolutions included; implies the other two"
   echo "                           # (the fourth run, after --frame-layers)"
+  echo "  --batch-norm <moving>    # moving: inference-mode batch norm, the moving statistics stay constant; batch: the"
+  echo "                           # statistics of the batch and moving-average updates in the trained layers (needs one of"
+  echo "                           # --segment-layers, --frame-layers, --conv-layers)"
   echo ""
   exit 100
 fi
@@ -52,6 +56,7 @@ if $keep_head; then opts="$opts --keep-head"; fi
 if $segment_layers; then opts="$opts --segment-layers"; fi
 if $frame_layers; then opts="$opts --frame-layers"; fi
 if $conv_layers; then opts="$opts --conv-layers"; fi
+if [ -n "$batch_norm" ]; then opts="$opts --batch-norm $batch_norm"; fi
 
 here=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export PYTHONPATH=$here:$PYTHONPATH

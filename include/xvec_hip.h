@@ -849,6 +849,56 @@ int xv_tconv_backward(int device, const float* gy_dev, int64_t ldgy, const float
                       const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx, float* gw_dev,
                       float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- batch norm in TRAINING mode behind the stored product z of a trained layer (csrc/bn_batch.hip): the batch statistics, h
+ * and y, the moving-average update (tf.layers.batch_normalization(training=True) with the UPDATE_OPS of model/trainer.py:501-527)
+ * and the gradient through the statistics.  z_dev [n, ldz] (N = out_dim columns) is what xv_seg_forward / xv_tconv_forward store
+ * when they are called without batch norm and with XV_SEG_ACT_NONE.  The backward produces no gbias, gw or gx: the caller hands
+ * gz as gy to xv_seg_backward / xv_tconv_backward, called with the four batch-norm pointers null and XV_SEG_ACT_NONE, whose mask
+ * kernels pass it through (gbias_j = sum_i gz_ij, gw and gx by their own rules).
+ * **Parity unpinned** against TensorFlow's own kernels (none at hand); pinned instead to torch.nn.functional.batch_norm(training
+ *   =True, eps=1e-3) in float64, forward, autograd and running statistics (tests/test_bn_batch_host.py).
+ * Forward (float32 in and out; gamma, beta [N]; act one of XV_SEG_ACT_*; every step behind v is a line of csrc/layer_lines.h):
+ *   S1_j = sum_i double(z_ij),  mu_j = float(S1_j / n);   S2_j = sum_i (double(z_ij) - double(mu_j))^2,  v_j = float(S2_j / n)
+ *   (two sweeps, the second about the rounded mean; the biased variance);
+ *   r_j = float(1 / sqrt(double(v_j) + 1e-3)),  s_j = gamma_j * r_j,  h_ij = fma(s_j, z_ij - mu_j, beta_j),  y_ij = act(h_ij)
+ *   -> y_dev [n, ldy], batch_mean_dev [N] = mu, batch_var_dev [N] = v.
+ *   d = float(1.0 - momentum),  f = float(double(n) / double(max(n - 1, 1))),  v'_j = bessel ? v_j * f : v_j;
+ *   moving_mean_j     <- moving_mean_j     - (moving_mean_j     - mu_j) * d
+ *   moving_variance_j <- moving_variance_j - (moving_variance_j - v'_j) * d      in place, each operation rounded to float32 on
+ *   its own (tf assign_moving_average, zero_debias off).  moving_mean_dev and moving_var_dev: both or neither.
+ *   bessel: tf.layers.batch_normalization takes the fused kernel for a rank-4 input, and the fused kernel hands the moving
+ *   variance the Bessel-corrected batch variance (n / (n - 1)); a rank-2 or rank-3 input takes tf.nn.moments and the biased one.
+ *   The normalisation itself uses the biased variance either way.  The caller knows the rank (tf_kaldi_speaker_amd.tail_train).
+ * Backward (gy_dev [n, ldgy]; batch_mean_dev and batch_var_dev as the forward returned them):
+ *   h as in the forward (the same bits),  a_ij = gy_ij act'(h_ij),  xh_ij = double(r_j) * (double(z_ij) - double(mu_j)),
+ *   A_j = sum_i double(a_ij),  G_j = sum_i double(a_ij) * xh_ij,  gbeta_j = float(A_j),  ggamma_j = float(G_j),
+ *   gz_ij = float(double(s_j) * (double(a_ij) - A_j / n - xh_ij * G_j / n))       (one rounding, from the unrounded sums)
+ *   -> gz_dev [n, ldgz], ggamma_dev [N], gbeta_dev [N].
+ * Order of every column sum (that of xv_tconv_backward's): slices of max(1024, ceil64(ceil(n / 64))) rows, within a slice 64
+ *   interleaved partial sums (lane l takes the rows i = l mod 64, ascending) closed by a fixed butterfly, the slices in ascending
+ *   order in double, rounded once.  A function of n alone; no floating-point atomics.
+ * Properties (tests/test_gpu_bn_batch.py): every output is bit-identical on every repeat, for every legal ws_bytes and whatever
+ *   the workspace and the outputs held before.  Every access is a scalar float32 one, so any 4-byte aligned pointer and any
+ *   leading dimension >= out_dim give the bits of the contiguous layout.  The per-element error bound is derived in the header of
+ *   csrc/bn_batch.hip (r amplifies the error of v where v is far below 1e-3 or comparable to it; the bound carries |dr/dv|).
+ *   Both calls only enqueue work and never wait.
+ * 1 <= out_dim <= 4096, n <= 2^24: XV_ERR_UNSUPPORTED beyond.  n < 1, out_dim < 1, a leading dimension below out_dim, momentum
+ *   outside [0, 1] or NaN, an unknown activation, a missing pointer, one moving vector without the other: XV_ERR_INVALID.  Every
+ *   check comes before the first launch: a refused call writes nothing.
+ * Workspace (16-byte aligned; XV_ERR_WORKSPACE below the least size): the slice sums and the unrounded column sums, 32 N slices +
+ *   16 N bytes, each rounded up to 256.  Nothing is panelled, so xv_bn_batch_workspace equals xv_bn_batch_workspace_min and a
+ *   larger workspace is not used.  Both are 0 for n < 1 or out_dim < 1. */
+int64_t xv_bn_batch_workspace(int64_t n, int out_dim);
+int64_t xv_bn_batch_workspace_min(int64_t n, int out_dim);
+int xv_bn_batch_forward(int device, const float* z_dev, int64_t ldz, int64_t n, int out_dim, const float* gamma_dev,
+                        const float* beta_dev, int act, double momentum, int bessel, float* moving_mean_dev, float* moving_var_dev,
+                        float* y_dev, int64_t ldy, float* batch_mean_dev, float* batch_var_dev, void* ws_dev, int64_t ws_bytes,
+                        void* stream);
+int xv_bn_batch_backward(int device, const float* gy_dev, int64_t ldgy, const float* z_dev, int64_t ldz, int64_t n, int out_dim,
+                         const float* batch_mean_dev, const float* batch_var_dev, const float* gamma_dev, const float* beta_dev,
+                         int act, float* gz_dev, int64_t ldgz, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes,
+                         void* stream);
+
 /* ---- metric-learning loss heads on the GPU (csrc/metric_loss.hip): what validation needs for a checkpoint trained with
  * `semihard_triplet_loss` (model/loss.py:387-527) or `angular_triplet_loss` (:530-663; validated with `e2e_valid_loss`,
  * :666-734, model/trainer.py:424-427).  Pinned to the reference's float64 numpy twins (model/test_utils.py:21-86, 118-154,

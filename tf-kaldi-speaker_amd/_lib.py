@@ -48,6 +48,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_seg_workspace", "xv_seg_workspace_min", "xv_seg_forward", "xv_seg_backward",
            "xv_stat_pool_forward", "xv_stat_pool_backward",
            "xv_tconv_workspace", "xv_tconv_workspace_min", "xv_tconv_forward_workspace", "xv_tconv_forward", "xv_tconv_backward",
+           "xv_bn_batch_workspace", "xv_bn_batch_workspace_min", "xv_bn_batch_forward", "xv_bn_batch_backward",
            "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss",
            "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
            "xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse",
@@ -239,6 +240,12 @@ def load():
                                      vp, i64, vp]
     lib.xv_tconv_backward.argtypes = [i32, vp, i64, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i32,
                                       vp, i64, vp, vp, vp, vp, vp, i64, vp]
+    lib.xv_bn_batch_workspace.argtypes = [i64, i32]
+    lib.xv_bn_batch_workspace.restype = i64
+    lib.xv_bn_batch_workspace_min.argtypes = [i64, i32]
+    lib.xv_bn_batch_workspace_min.restype = i64
+    lib.xv_bn_batch_forward.argtypes = [i32, vp, i64, i64, i32, vp, vp, i32, C.c_double, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp]
+    lib.xv_bn_batch_backward.argtypes = [i32, vp, i64, vp, i64, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, i64, vp]
     lib.xv_metric_loss_workspace.argtypes = [i64, vp, i32, i32]
     lib.xv_metric_loss_workspace.restype = i64
     lib.xv_metric_loss_slot_bytes.argtypes = [i32, i32, i32]
@@ -280,7 +287,7 @@ def load():
     for n in EXPORTS:
         if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
                      "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_opt_workspace", "xv_seg_workspace", "xv_seg_workspace_min", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_vbx_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
+                     "xv_loss_workspace", "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_opt_workspace", "xv_seg_workspace", "xv_seg_workspace_min", "xv_bn_batch_workspace", "xv_bn_batch_workspace_min", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_vbx_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
             getattr(lib, n).restype = i32
     _lib = lib
     return lib

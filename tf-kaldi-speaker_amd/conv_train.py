@@ -14,7 +14,9 @@ layers are TConvLayers (a tail_train.Layer on xv_tconv_*), and takes its step fr
 the two segment layers, one xv_loss_classifier_grad, the segment layers backward, StatPool.backward, the frame layers backward
 in reverse (no gx for the first), one xv_opt_step per tensor.  Trained: every kernel (the convolutions' in the shape the
 checkpoint had, rank 4 or 3) and bias, gamma and beta of every batch norm, the head.  NOT trained: the moving statistics.
-Batch norm runs in INFERENCE mode and the pooling floor mask is a constant: **parity unpinned**, as for tail_train.py.
+Batch norm runs in INFERENCE mode and the pooling floor mask is a constant: **parity unpinned**, as for tail_train.py.  With
+batch_norm="batch" every layer normalises with the statistics of the batch (all output rows of all utterances), the gradient
+goes through them and the moving statistics move (tail_train.Layer's batch_stats; bessel for the rank-4 kernels only).
 
 `weight_l2_regularizer` goes on every kernel, the convolutions' included (model/tdnn.py: every layer takes kernel_regularizer);
 the head keeps the rule of head_train.optimizer_config, the clip is per tensor, Adam's step count is shared.
@@ -106,19 +108,20 @@ def rows_to_kernel(rows, shape):
 class TConvLayer(tail_train.Layer):
     """One frame-level layer on packed utterances: w holds kernel_to_rows of the TensorFlow kernel, whose shape is kept."""
 
-    def __init__(self, kernel, bias, bn, act, device=0, num_slots=0):
+    def __init__(self, kernel, bias, bn, act, device=0, num_slots=0, batch_stats=False, momentum=0.99, bessel=False):
         rows, self.taps, self.channels = kernel_to_rows(kernel)
         self.shape = tuple(np.shape(kernel))
         if tuple(np.shape(bias)) != (int(rows.shape[0]),):
             raise ValueError("bias [%d] expected, got %s" % (int(rows.shape[0]), np.shape(bias)))
-        tail_train.Layer.__init__(self, rows, bias, bn, act, device, num_slots)
+        tail_train.Layer.__init__(self, rows, bias, bn, act, device, num_slots, batch_stats, momentum, bessel)
         self._off = None
         self._sizes = (0, 0, 0)
         self._covers = False
 
-    def forward(self, x, offsets):
+    def forward(self, x, offsets, training=True):
         """x [rows, C] on the device, float32 contiguous; offsets [B + 1] host integers of its rows -> (y [total_out, N] packed
-        from row 0, the output offsets); x, z and the offsets are kept for backward()."""
+        from row 0, the output offsets); x, z and the offsets are kept for backward().  With batch_stats, training chooses
+        between the statistics of the batch (all output rows of all utterances) and the moving ones."""
         torch = self._torch
         if x.dim() != 2 or int(x.shape[1]) != self.channels or x.dtype != torch.float32 or not x.is_contiguous():
             raise ValueError("x: expected a contiguous float32 [rows, %d], got %s" % (self.channels, tuple(x.shape)))
@@ -128,18 +131,23 @@ class TConvLayer(tail_train.Layer):
             raise ValueError("offsets must ascend from >= 0 to at most the %d rows of x" % rows)
         out_off = out_offsets(host, self.taps)
         batch, total_in, total_out = host.size - 1, int(host[-1] - host[0]), int(out_off[-1])
+        stats = self._use_batch(training, total_out)
         with torch.cuda.device(self.device):
             off = torch.from_numpy(host.astype(np.int32)).to(x.device)
             z = torch.empty((max(total_out, 1), self.out_dim), dtype=torch.float32, device=x.device)
-            y = torch.empty((max(total_out, 1), self.out_dim), dtype=torch.float32, device=x.device)
+            y = (self._scratch_y(total_out, x.device) if stats
+                 else torch.empty((max(total_out, 1), self.out_dim), dtype=torch.float32, device=x.device))
             if total_out:
                 ws = self._workspace(int(self._lib.xv_tconv_forward_workspace(batch, total_out)), x.device)
-                bn = self.bn or [None] * 4
+                bn = [None] * 4 if stats else self.bn or [None] * 4
                 stream = torch.cuda.current_stream(self.device).cuda_stream
                 _lib.check(self._lib.xv_tconv_forward(self.device, _p(x), self.channels, self.channels, self.taps, _p(off), batch,
                                                       total_in, total_out, _p(self.w), self.ldw, self.out_dim, _p(self.b), _p(bn[0]),
-                                                      _p(bn[1]), _p(bn[2]), _p(bn[3]), self.act, _p(z), self.out_dim, _p(y),
-                                                      self.out_dim, _p(ws), ws.numel(), C.c_void_p(stream)))
+                                                      _p(bn[1]), _p(bn[2]), _p(bn[3]), _lib.XV_SEG_ACT_NONE if stats else self.act,
+                                                      _p(z), self.out_dim, _p(y), self.out_dim, _p(ws), ws.numel(),
+                                                      C.c_void_p(stream)))
+                if stats:
+                    y = self._bn_forward(z, total_out, stream)
         self._x, self._z, self._off, self._sizes = x, z, off, (batch, total_in, total_out)
         self._covers = batch > 0 and int(host[0]) == 0 and int(host[-1]) == rows
         return y[:total_out], out_off
@@ -165,6 +173,14 @@ class TConvLayer(tail_train.Layer):
                                  x.device)
             bn = self.bn or [None] * 4
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if self._batch:                  # through the statistics first; the operator then passes gz through its mask
+                gz = self._bn_backward(gy, z, total_out, stream)
+                _lib.check(self._lib.xv_tconv_backward(self.device, _p(gz), self.out_dim, _p(x), self.channels, self.channels,
+                                                       self.taps, _p(self._off), batch, total_in, total_out, _p(z), self.out_dim,
+                                                       _p(self.w), self.ldw, self.out_dim, None, None, None, None,
+                                                       _lib.XV_SEG_ACT_NONE, _p(gx), self.channels, _p(self.gw), _p(self.gb), None,
+                                                       None, _p(ws), ws.numel(), C.c_void_p(stream)))
+                return gx
             _lib.check(self._lib.xv_tconv_backward(self.device, _p(gy), self.out_dim, _p(x), self.channels, self.channels, self.taps,
                                                    _p(self._off), batch, total_in, total_out, _p(z), self.out_dim, _p(self.w), self.ldw,
                                                    self.out_dim, _p(bn[0]), _p(bn[1]), _p(bn[2]), _p(bn[3]), self.act, _p(gx),
@@ -186,12 +202,12 @@ class ConvTrainer(frame_train.StackedTrainer):
     _CHAIN = "%s takes %d channels, %s gives %d"
     _INPUT = ("feats_dev", "")
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None):
-        frame_train.StackedTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias)
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
+        frame_train.StackedTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias, batch_norm)
         self.context = sum(layer.taps - 1 for layer in self.frame_layers)
 
     def _layer(self, spec, kernel, bias, bn, device, num_slots):
-        layer = TConvLayer(kernel, bias, bn, spec.act, device, num_slots)
+        layer = TConvLayer(kernel, bias, bn, spec.act, device, num_slots, **self._stats(kernel))
         if layer.taps != spec.taps:
             raise ValueError("%s: a kernel of %d taps expected, got shape %s" % (spec.kernel, spec.taps, layer.shape))
         return layer
@@ -205,8 +221,8 @@ class ConvTrainer(frame_train.StackedTrainer):
             raise ValueError("every utterance needs more than the %d frames of context" % self.context)
         return off
 
-    def _walk(self, x, off, mark):
+    def _walk(self, x, off, mark, training=True):
         for i, layer in enumerate(self.frame_layers):
-            x, off = layer.forward(x.contiguous(), off)
+            x, off = tail_train.layer_forward(layer, training, x.contiguous(), off)
             mark("frame_forward/%d" % i)
         return x, off

@@ -655,6 +655,58 @@ int xv_tconv_backward(int device, const float* gy_dev, int64_t ldgy, const float
   });
 }
 
+// batch norm in training mode on a stored product z (include/xvec_hip.h, csrc/bn_batch.hip)
+int64_t xv_bn_batch_workspace(int64_t n, int out_dim) { return bn_batch_workspace_bytes(n, out_dim); }
+
+int64_t xv_bn_batch_workspace_min(int64_t n, int out_dim) { return bn_batch_workspace_bytes(n, out_dim); }
+
+namespace {
+
+// the checks the two batch-statistics calls share; `op` names the caller in the message
+int bn_batch_check(const char* op, int64_t n, int out_dim, int64_t ldz, int64_t ldo, int act) {
+  if (out_dim > 4096 || n > (1 << 24))
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: out_dim <= 4096, n <= 2^24, got %d, %lld", op, out_dim, (long long)n);
+  if (n < 1 || out_dim < 1 || ldz < out_dim || ldo < out_dim) return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
+  if (act < XV_SEG_ACT_NONE || act > XV_SEG_ACT_LRELU) return fail(nullptr, XV_ERR_INVALID, "%s: unknown activation %d", op, act);
+  return XV_OK;
+}
+
+}  // namespace
+
+int xv_bn_batch_forward(int device, const float* z_dev, int64_t ldz, int64_t n, int out_dim, const float* gamma_dev,
+                        const float* beta_dev, int act, double momentum, int bessel, float* moving_mean_dev, float* moving_var_dev,
+                        float* y_dev, int64_t ldy, float* batch_mean_dev, float* batch_var_dev, void* ws_dev, int64_t ws_bytes,
+                        void* stream) {
+  if (!z_dev || !gamma_dev || !beta_dev || !y_dev || !batch_mean_dev || !batch_var_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_bn_batch_forward: null pointer");
+  if ((moving_mean_dev != nullptr) != (moving_var_dev != nullptr))
+    return fail(nullptr, XV_ERR_INVALID, "xv_bn_batch_forward: moving_mean and moving_variance, or neither");
+  int rc = bn_batch_check("xv_bn_batch_forward", n, out_dim, ldz, ldy, act);
+  if (rc != XV_OK) return rc;
+  if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(nullptr, XV_ERR_INVALID, "xv_bn_batch_forward: 0 <= momentum <= 1");
+  if ((rc = layer_ws_check("xv_bn_batch_forward", ws_dev, ws_bytes, bn_batch_workspace_bytes(n, out_dim))) != XV_OK) return rc;
+  return with_device(device, "xv_bn_batch_forward", [&] {
+    return launch_bn_batch_forward(z_dev, ldz, n, out_dim, gamma_dev, beta_dev, act, momentum, bessel ? 1 : 0, moving_mean_dev,
+                                   moving_var_dev, y_dev, ldy, batch_mean_dev, batch_var_dev, ws_dev, to_stream(stream));
+  });
+}
+
+int xv_bn_batch_backward(int device, const float* gy_dev, int64_t ldgy, const float* z_dev, int64_t ldz, int64_t n, int out_dim,
+                         const float* batch_mean_dev, const float* batch_var_dev, const float* gamma_dev, const float* beta_dev,
+                         int act, float* gz_dev, int64_t ldgz, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes,
+                         void* stream) {
+  if (!gy_dev || !z_dev || !batch_mean_dev || !batch_var_dev || !gamma_dev || !beta_dev || !gz_dev || !ggamma_dev || !gbeta_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_bn_batch_backward: null pointer");
+  int rc = bn_batch_check("xv_bn_batch_backward", n, out_dim, ldz, ldgz, act);
+  if (rc != XV_OK) return rc;
+  if (ldgy < out_dim) return fail(nullptr, XV_ERR_INVALID, "xv_bn_batch_backward: bad dimensions");
+  if ((rc = layer_ws_check("xv_bn_batch_backward", ws_dev, ws_bytes, bn_batch_workspace_bytes(n, out_dim))) != XV_OK) return rc;
+  return with_device(device, "xv_bn_batch_backward", [&] {
+    return launch_bn_batch_backward(gy_dev, ldgy, z_dev, ldz, n, out_dim, batch_mean_dev, batch_var_dev, gamma_dev, beta_dev, act,
+                                    gz_dev, ldgz, ggamma_dev, gbeta_dev, ws_dev, to_stream(stream));
+  });
+}
+
 int xv_plda_prepare(int device, const float* x_dev, int64_t ldx, int64_t n, int d_in, const float* transform_dev, int64_t ldt,
                     int d, int norm, int side, int pack_second, const double* tables_dev, const double* logdet_dev,
                     int num_tables, const int32_t* table_index_dev, float* rows_dev, int64_t ldr, float* packed_dev, int64_t ldp,

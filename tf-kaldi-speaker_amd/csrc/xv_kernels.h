@@ -389,6 +389,16 @@ hipError_t launch_tconv_backward(const float* gy, int64_t ldgy, const float* x, 
                                  float* gx, int64_t ldgx, float* gw, float* gbias, float* ggamma, float* gbeta, void* ws,
                                  hipStream_t s);
 
+// batch norm in training mode on the stored product z [n, N] of a trained layer: batch statistics, y, the moving averages in place
+// (mm, mv: both or null), and the gradient through the statistics (csrc/bn_batch.hip, csrc/layer_lines.h)
+int64_t bn_batch_workspace_bytes(int64_t n, int N);
+hipError_t launch_bn_batch_forward(const float* z, int64_t ldz, int64_t n, int N, const float* gamma, const float* beta, int act,
+                                   double momentum, int bessel, float* mm, float* mv, float* y, int64_t ldy, float* mean, float* var,
+                                   void* ws, hipStream_t s);
+hipError_t launch_bn_batch_backward(const float* gy, int64_t ldgy, const float* z, int64_t ldz, int64_t n, int N, const float* mean,
+                                    const float* var, const float* gamma, const float* beta, int act, float* gz, int64_t ldgz,
+                                    float* ggamma, float* gbeta, void* ws, hipStream_t s);
+
 // statistics pooling of the caller's own packed rows and its gradient (csrc/pool_grad.hip); offsets [batch + 1] on the device,
 // total_rows a host bound that sizes the backward's grid and clamps what an offset can reach
 hipError_t launch_stat_pool_forward(const float* x, int64_t ldx, int C, const int32_t* offsets, int64_t batch, int64_t total_rows,

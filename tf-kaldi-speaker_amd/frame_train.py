@@ -16,7 +16,8 @@ A step is: SegLayer.forward per frame layer on the packed rows, StatPool.forward
 xv_loss_classifier_grad, the segment layers backward (now with gx for the first), StatPool.backward, the frame layers backward
 (no gx for the first), one xv_opt_step per tensor.  Trained: every dense kernel and bias, gamma and beta of every batch norm
 behind the frozen node, the head.  NOT trained: the moving statistics.  Batch norm runs in INFERENCE mode and the pooling floor
-mask is a constant: **parity unpinned**, as for tail_train.py.
+mask is a constant: **parity unpinned**, as for tail_train.py.  batch_norm="batch" switches the layers trained here to the
+statistics of the batch and moving-average updates, as tail_train.py describes; the frozen forward stays as it is.
 
 `weight_l2_regularizer` goes on every dense kernel, the frame layers' included (model/tdnn.py: every layer takes
 kernel_regularizer); the head keeps the rule of head_train.optimizer_config, the clip is per tensor, Adam's step count is shared.
@@ -166,17 +167,22 @@ class StatPool(object):
 class StackedTrainer(object):
     """Frame layers -> StatPool -> a tail_train.TailTrainer (the two segment-level layers and the head), all built from the
     checkpoint's variables, and THE step through them (TailTrainer._step).  A subclass says what its frame layers are: its
-    module's three functions, _layer, _width, _walk, and its own words in _CHAIN and _INPUT."""
+    module's three functions, _layer, _width, _walk, and its own words in _CHAIN and _INPUT.
+
+    batch_norm="moving" (the default) or "batch", as tail_train.TailTrainer takes it and for every layer this trainer trains
+    (what lies in front of a FrameTrainer, the frozen forward, is not touched): tail_train.batch_stats_options gives each frame
+    layer its momentum and, by the rank of its own kernel, bessel.  forward() is the inference path in both modes."""
 
     _check = _specs = _l2 = None        # the module's check_supported, frame_variables and l2_assignment, as staticmethods
     _CHAIN = None       # "%s ... %d ..., %s ... %d": a layer's kernel and input width, the layer before and its output width
     _INPUT = None       # (the argument's name in the messages, what follows "must be a device tensor")
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None):
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
         self._check(params)
         self.params = params
+        self.batch_norm = batch_norm
         self.frame_specs = self._specs(params)
-        self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias)
+        self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias, batch_norm)
         num_slots = len(self.tail.layers[0].slots["kernel"])
         self.frame_layers = [self._layer(spec, *tail_train.layer_weights(spec, weights), device, num_slots) for spec in self.frame_specs]
         for a, b, sa, sb in zip(self.frame_layers[:-1], self.frame_layers[1:], self.frame_specs[:-1], self.frame_specs[1:]):
@@ -198,8 +204,12 @@ class StackedTrainer(object):
         self.num_steps = 0                                                   # adam's t, shared by every tensor
 
     def _layer(self, spec, kernel, bias, bn, device, num_slots):
-        """The frame layer of `spec` from the checkpoint's kernel, bias and batch-norm vectors."""
+        """The frame layer of `spec` from the checkpoint's kernel, bias and batch-norm vectors (with self._stats(kernel))."""
         raise NotImplementedError
+
+    def _stats(self, kernel):
+        """The batch-statistics keywords of the layer with this TensorFlow kernel."""
+        return tail_train.batch_stats_options(self.params, self.batch_norm, kernel)
 
     def _width(self, layer):
         """The columns a row of the layer's input has."""
@@ -209,7 +219,7 @@ class StackedTrainer(object):
         """The offsets as _walk takes them, checked as far as the subclass checks them."""
         return offsets
 
-    def _walk(self, x, offsets, mark):
+    def _walk(self, x, offsets, mark, training=True):
         """x through every frame layer, mark("frame_forward/<i>") behind layer i -> (the last layer's rows, their offsets)."""
         raise NotImplementedError
 
@@ -226,14 +236,14 @@ class StackedTrainer(object):
             raise ValueError("%s: expected float32 [rows, %d], got %s" % (name, self.in_dim, tuple(x_dev.shape)))
         return x_dev.contiguous()
 
-    def _forward(self, x_dev, offsets, mark=tail_train._no_mark):
+    def _forward(self, x_dev, offsets, mark=tail_train._no_mark, training=True):
         x, offsets = self._packed(x_dev), self._offsets(offsets)
         mark("start")
-        x, offsets = self._walk(x, offsets, mark)
+        x, offsets = self._walk(x, offsets, mark, training)
         mark("frame_forward")
         pooled = self.pool.forward(x.contiguous(), offsets)
         mark("pool_forward")
-        y = self.tail._forward(pooled.contiguous())
+        y = self.tail._forward(pooled.contiguous(), training)
         mark("segment_forward")
         return y
 
@@ -249,9 +259,9 @@ class StackedTrainer(object):
 
     def forward(self, x_dev, offsets):
         """x_dev [rows, in_dim] on the device (packed rows), offsets [B + 1] of its rows -> the `output` endpoint [B, embed_dim]
-        on the device, with the current weights."""
+        on the device, with the current weights and, in every batch_norm mode, the current moving statistics (inference)."""
         with self._torch.cuda.device(self.device):
-            return self._forward(x_dev, offsets)
+            return self._forward(x_dev, offsets, training=False)
 
     def step(self, x_dev, offsets, labels, learning_rate, global_step=0, mark=None):
         """One training step on a batch of packed rows: forward through the frame layers, the pooling and the segment layers,
@@ -284,13 +294,13 @@ class FrameTrainer(StackedTrainer):
         k = np.asarray(kernel, dtype=np.float32)
         if k.ndim != 2:
             raise ValueError("%s: a dense kernel [cin, cout] expected, got shape %s" % (spec.kernel, k.shape))
-        return tail_train.SegLayer(k, bias, bn, spec.act, device, num_slots)
+        return tail_train.SegLayer(k, bias, bn, spec.act, device, num_slots, **self._stats(k))
 
     def _width(self, layer):
         return layer.in_dim
 
-    def _walk(self, x, offsets, mark):
+    def _walk(self, x, offsets, mark, training=True):
         for i, layer in enumerate(self.frame_layers):
-            x = layer.forward(x)
+            x = tail_train.layer_forward(layer, training, x)
             mark("frame_forward/%d" % i)
         return x, offsets

@@ -228,6 +228,10 @@ def read_learning_rate_file(path):
 
 
 # ---------------------------------------------------------------------------------------------- the driver
+BATCH_NORM_ALONE = ("--batch-norm batch needs --segment-layers, --frame-layers or --conv-layers: the head has no batch norm, and "
+                    "everything in front of it is frozen")
+
+
 def _frame_step(trainer, head, feats, labels, lr, step):
     """One FrameTrainer step on the batch feats [B, T, dim]: the frozen forward to trainer.embeddings (a frame-level node) hands
     its packed rows over on the device; utterance b owns out_rows / B of them (T less the node's context)."""
@@ -263,7 +267,7 @@ def _conv_step(trainer, head, feats, labels, lr, step):
 
 
 def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_model_dir, weights=None, seed=0, keep_head=False,
-               precision=None, log=None, segment_layers=False, frame_layers=False, conv_layers=False):
+               precision=None, log=None, segment_layers=False, frame_layers=False, conv_layers=False, batch_norm="moving"):
     """Train the head of `trainer` (a Trainer built for "predict" with the pre-trained weights loaded; its params name the head,
     the optimizer and the schedule) on train_dir and write <out_model_dir>/nnet after every epoch of num_steps_per_epoch steps:
     model-<step>.npz (model_io.save_model: every variable of `weights` unchanged plus the new softmax/output/kernel and bias),
@@ -281,7 +285,15 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     multi-tap convolutions included, on the packed features, in exact fp32 whatever `precision` says.  The checkpoints then hold
     the new convolution kernels in the shape the input had, and biases, gamma and beta; the moving statistics and every other
     variable are unchanged.
+    batch_norm="batch" (with any of the three; alone it is refused, the head has no batch norm) runs the batch norms of the
+    trained layers in training mode (tail_train.batch_stats_options): the checkpoints then also hold their moving_mean and
+    moving_variance, and the validation after each epoch, the unchanged Trainer.valid on the written checkpoint, normalises with
+    them.  The default "moving" changes nothing.
     -> [(epoch, step, valid loss, eer, learning rate)]."""
+    if batch_norm not in ("moving", "batch"):
+        raise ValueError("batch_norm must be moving or batch, got %r" % (batch_norm,))
+    if batch_norm == "batch" and not (segment_layers or frame_layers or conv_layers):
+        raise ValueError(BATCH_NORM_ALONE)
     from . import scoring
     from . import valid as valid_mod
     from .trainer import Trainer
@@ -327,11 +339,11 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
             if k is not None and tuple(k.shape) == (embed_dim, num_classes):
                 kernel, bias = np.asarray(k), weights.get(model_io.SOFTMAX_BIAS)
         if conv_layers:
-            head = conv_train.ConvTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
+            head = conv_train.ConvTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
         elif frame_layers:
-            head = frame_train.FrameTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
+            head = frame_train.FrameTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
         elif segment_layers:
-            head = tail_train.TailTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias)
+            head = tail_train.TailTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
         else:
             head = HeadTrainer(params, embed_dim, num_classes, trainer._device_index, seed, kernel, bias)
         frozen = {k: v for k, v in weights.items() if k not in (model_io.SOFTMAX_KERNEL, model_io.SOFTMAX_BIAS)}

@@ -9,7 +9,10 @@ extended TDNN) with their CURRENT weights, one xv_loss_classifier_grad for the l
 layers (csrc/seg_grad.hip), one xv_opt_step per tensor.  Trained: the two dense kernels and biases, gamma and beta of their
 batch norms, the head.  NOT trained: the moving statistics.  Batch norm runs in INFERENCE mode (the reference feeds
 is_training=True and normalises with batch statistics): the layers are trained on exactly the function extraction and
-validation evaluate, as head_train.py does: **parity unpinned**.
+validation evaluate, as head_train.py does: **parity unpinned**.  That is the default, batch_norm="moving".  With
+batch_norm="batch" the trained layers take the reference's mode (Layer's batch_stats: the statistics of the batch, the gradient
+through them, moving-average updates by xv_bn_batch_forward / xv_bn_batch_backward, csrc/bn_batch.hip; batch_stats_options says
+which layer takes which momentum and variance), pinned to torch instead of TensorFlow.
 
 `weight_l2_regularizer` goes on the two dense kernels only (tf.layers.dense(kernel_regularizer=...), model/tdnn.py:137-160),
 the head keeps the rule of head_train.optimizer_config, the clip is per tensor (model/trainer.py:529-533), Adam's step count
@@ -92,6 +95,33 @@ def l2_assignment(params):
     return out
 
 
+BATCH_NORM_MODES = ("moving", "batch")
+
+
+def batch_stats_options(params, batch_norm, kernel=None):
+    """The keywords a trained Layer takes for the trainers' batch_norm mode.  "moving" (the default of every trainer): none,
+    today's inference-mode batch norm with constant moving statistics.  "batch": batch_stats, momentum =
+    params.batchnorm_momentum (0.99 when absent, as every nnet_conf of the reference sets it) and bessel, by the rank of the
+    tensor the layer's batch norm sees in model/tdnn.py: tf.layers.batch_normalization takes the fused kernel for a rank-4
+    input only, and the fused kernel moves moving_variance towards the Bessel-corrected batch variance.
+      * rank-4 convolution kernels ([1, W, C, N]: tf.layers.conv2d of `tdnn`, model/tdnn.py:38-91): the input is [b, 1, l, N],
+        bessel is true;
+      * that network's 1-tap dense frame layers tdnn4 and tdnn5: model/tdnn.py:94 squeezes the tensor to [b, l, 512] BEFORE
+        tdnn4_dense, so their batch norms see rank 3 and bessel is false (the rank of the layer's OWN kernel decides, not the
+        network's);
+      * rank-3 kernels (tf.layers.conv1d of the extended TDNN, model/tdnn.py:371-539, whose expand_dims is commented out) and all
+        its dense layers: rank 3, false;
+      * the segment layers behind the pooling: rank 2, false.
+    `kernel` is the layer's TensorFlow kernel (None for a segment layer)."""
+    if batch_norm not in BATCH_NORM_MODES:
+        raise ValueError("batch_norm must be one of %s, got %r" % (", ".join(BATCH_NORM_MODES), batch_norm))
+    if batch_norm == "moving":
+        return {}
+    momentum = _dict(params).get("batchnorm_momentum")
+    return dict(batch_stats=True, momentum=0.99 if momentum is None else float(momentum),
+                bessel=kernel is not None and np.ndim(kernel) == 4)
+
+
 def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -99,13 +129,23 @@ def _p(t):
 class Layer(object):
     """What every trained layer keeps on the device: the rows [N, ldw] of the weights (ldw = the width K rounded up to 4, the
     padding stays zero), the bias, the four batch-norm vectors or None, their gradients, the optimizer slots and a workspace
-    that only grows.  SegLayer (dense, xv_seg_*) and conv_train.TConvLayer (packed utterances, xv_tconv_*) add the operator."""
+    that only grows.  SegLayer (dense, xv_seg_*) and conv_train.TConvLayer (packed utterances, xv_tconv_*) add the operator.
 
-    def __init__(self, rows, bias, bn, act, device=0, num_slots=0):
+    batch_stats (with a batch norm; without one it changes nothing): forward() normalises with the statistics of the batch and
+    moves moving_mean and moving_variance (bn[2], bn[3]) in place, backward() goes through the statistics
+    (xv_bn_batch_forward / xv_bn_batch_backward, csrc/bn_batch.hip).  The layer's operator then runs without batch norm and
+    with XV_SEG_ACT_NONE: forward for z (its y goes to a scratch buffer the layer keeps), backward on gz for gbias, gw and gx.
+    momentum and bessel are those of include/xvec_hip.h.  forward(.., training=False) is today's inference path with the
+    current moving statistics."""
+
+    def __init__(self, rows, bias, bn, act, device=0, num_slots=0, batch_stats=False, momentum=0.99, bessel=False):
         torch = losses._need_device()
         self.out_dim, self.in_dim = int(rows.shape[0]), int(rows.shape[1])
         self.ldw = (self.in_dim + 3) // 4 * 4
         self.act, self.device = int(act), int(device)
+        self.batch_stats, self.momentum, self.bessel = bool(batch_stats) and bn is not None, float(momentum), bool(bessel)
+        if self.batch_stats and not 0.0 <= self.momentum <= 1.0:
+            raise ValueError("momentum must lie in [0, 1], got %r" % (momentum,))
         self._torch, self._lib = torch, _lib.load()
         dev = "cuda:%d" % self.device
         with torch.cuda.device(self.device):
@@ -123,6 +163,8 @@ class Layer(object):
             self.gbeta = None if self.bn is None else torch.zeros_like(self.b)
             self.slots = {name: [torch.zeros_like(t) for _ in range(num_slots)] for name, t, _ in self.trained()}
         self._x = self._z = self._ws = None
+        self._scratch = self._bn_ws = self._mean = self._var = None
+        self._batch = False                                                    # the last forward used the batch statistics
 
     def trained(self):
         """[(name, parameter, gradient)] in the order the optimizer takes them."""
@@ -142,30 +184,78 @@ class Layer(object):
             self._ws = self._torch.empty(max(need, 16), dtype=self._torch.uint8, device=device)
         return self._ws
 
+    def _use_batch(self, training, rows):
+        """Whether this forward takes the batch statistics; they need a row."""
+        self._batch = bool(training) and self.batch_stats
+        if self._batch and rows < 1:
+            raise ValueError("batch statistics need at least one row")
+        return self._batch
+
+    def _scratch_y(self, rows, device):
+        """The y the operator writes when it is called for z alone: a buffer that only grows, never read."""
+        if self._scratch is None or self._scratch.shape[0] < rows:
+            self._scratch = self._torch.empty((rows, self.out_dim), dtype=self._torch.float32, device=device)
+        return self._scratch
+
+    def _bn_workspace(self, rows, device):
+        need = int(self._lib.xv_bn_batch_workspace(rows, self.out_dim))
+        if self._bn_ws is None or self._bn_ws.numel() < need:
+            self._bn_ws = self._torch.empty(max(need, 16), dtype=self._torch.uint8, device=device)
+        return self._bn_ws
+
+    def _bn_forward(self, z, rows, stream):
+        """z [rows, N] (the layer's product, no batch norm, no activation) -> y [rows, N] by the batch statistics, which are kept
+        for _bn_backward; moving_mean and moving_variance move in place."""
+        torch = self._torch
+        y = torch.empty((rows, self.out_dim), dtype=torch.float32, device=z.device)
+        self._mean = torch.empty((self.out_dim,), dtype=torch.float32, device=z.device)
+        self._var = torch.empty((self.out_dim,), dtype=torch.float32, device=z.device)
+        ws = self._bn_workspace(rows, z.device)
+        _lib.check(self._lib.xv_bn_batch_forward(self.device, _p(z), self.out_dim, rows, self.out_dim, _p(self.bn[0]), _p(self.bn[1]),
+                                                 self.act, self.momentum, int(self.bessel), _p(self.bn[2]), _p(self.bn[3]), _p(y),
+                                                 self.out_dim, _p(self._mean), _p(self._var), _p(ws), ws.numel(), C.c_void_p(stream)))
+        return y
+
+    def _bn_backward(self, gy, z, rows, stream):
+        """gy [rows, N] -> gz [rows, N], the gradient at the layer's product; ggamma and gbeta are written."""
+        torch = self._torch
+        gz = torch.empty((rows, self.out_dim), dtype=torch.float32, device=z.device)
+        ws = self._bn_workspace(rows, z.device)
+        _lib.check(self._lib.xv_bn_batch_backward(self.device, _p(gy), self.out_dim, _p(z), self.out_dim, rows, self.out_dim,
+                                                  _p(self._mean), _p(self._var), _p(self.bn[0]), _p(self.bn[1]), self.act, _p(gz),
+                                                  self.out_dim, _p(self.ggamma), _p(self.gbeta), _p(ws), ws.numel(),
+                                                  C.c_void_p(stream)))
+        return gz
+
 
 class SegLayer(Layer):
     """A dense layer: w holds the transpose of the TensorFlow kernel [K, N]."""
 
-    def __init__(self, kernel, bias, bn, act, device=0, num_slots=0):
+    def __init__(self, kernel, bias, bn, act, device=0, num_slots=0, batch_stats=False, momentum=0.99, bessel=False):
         kernel = np.asarray(kernel, dtype=np.float32)
         if kernel.ndim != 2 or tuple(np.shape(bias)) != (kernel.shape[1],):
             raise ValueError("kernel [K, N] and bias [N] expected, got %s and %s" % (kernel.shape, np.shape(bias)))
-        Layer.__init__(self, kernel.T, bias, bn, act, device, num_slots)
+        Layer.__init__(self, kernel.T, bias, bn, act, device, num_slots, batch_stats, momentum, bessel)
 
-    def forward(self, x):
-        """x [n, K] on the device, float32 contiguous -> y [n, N]; x and z are kept for backward()."""
+    def forward(self, x, training=True):
+        """x [n, K] on the device, float32 contiguous -> y [n, N]; x and z are kept for backward().  With batch_stats, training
+        chooses between the statistics of the batch and the moving ones; without, it changes nothing."""
         torch = self._torch
         n = int(x.shape[0])
         if tuple(x.shape) != (n, self.in_dim):
             raise ValueError("x: expected [n, %d], got shape %s" % (self.in_dim, tuple(x.shape)))
+        batch = self._use_batch(training, n)
         with torch.cuda.device(self.device):
             z = torch.empty((max(n, 1), self.out_dim), dtype=torch.float32, device=x.device)
-            y = torch.empty((max(n, 1), self.out_dim), dtype=torch.float32, device=x.device)
-            bn = self.bn or [None] * 4
+            y = self._scratch_y(n, x.device) if batch else torch.empty((max(n, 1), self.out_dim), dtype=torch.float32, device=x.device)
+            bn = [None] * 4 if batch else self.bn or [None] * 4
             stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(self._lib.xv_seg_forward(self.device, _p(x), self.in_dim, n, self.in_dim, _p(self.w), self.ldw, self.out_dim,
-                                                _p(self.b), _p(bn[0]), _p(bn[1]), _p(bn[2]), _p(bn[3]), self.act, _p(z), self.out_dim,
+                                                _p(self.b), _p(bn[0]), _p(bn[1]), _p(bn[2]), _p(bn[3]),
+                                                _lib.XV_SEG_ACT_NONE if batch else self.act, _p(z), self.out_dim,
                                                 _p(y), self.out_dim, C.c_void_p(stream)))
+            if batch:
+                y = self._bn_forward(z, n, stream)
         self._x, self._z = x, z
         return y[:n]
 
@@ -183,6 +273,13 @@ class SegLayer(Layer):
             ws = self._workspace(int(self._lib.xv_seg_workspace(n, self.in_dim, self.out_dim)), x.device)
             bn = self.bn or [None] * 4
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if self._batch:                  # through the statistics first; the operator then passes gz through its mask
+                gz = self._bn_backward(gy, z, n, stream)
+                _lib.check(self._lib.xv_seg_backward(self.device, _p(gz), self.out_dim, _p(x), self.in_dim, _p(z), self.out_dim, n,
+                                                     self.in_dim, _p(self.w), self.ldw, self.out_dim, None, None, None, None,
+                                                     _lib.XV_SEG_ACT_NONE, _p(gx), self.in_dim, _p(self.gw), _p(self.gb), None, None,
+                                                     _p(ws), ws.numel(), C.c_void_p(stream)))
+                return gx
             _lib.check(self._lib.xv_seg_backward(self.device, _p(gy), self.out_dim, _p(x), self.in_dim, _p(z), self.out_dim, n,
                                                  self.in_dim, _p(self.w), self.ldw, self.out_dim, _p(bn[0]), _p(bn[1]), _p(bn[2]),
                                                  _p(bn[3]), self.act, _p(gx), self.in_dim, _p(self.gw), _p(self.gb), _p(self.ggamma),
@@ -192,6 +289,12 @@ class SegLayer(Layer):
     def kernel(self):
         """The TensorFlow kernel [K, N], float32 numpy."""
         return np.ascontiguousarray(self.w[:, :self.in_dim].t().cpu().numpy())
+
+
+def layer_forward(layer, training, *args):
+    """layer.forward(*args), the call the trainers have always made; only a layer with batch_stats is ever told training=False
+    (the inference path of the trainers' forward())."""
+    return layer.forward(*args) if training or not layer.batch_stats else layer.forward(*args, training=False)
 
 
 def layer_weights(spec, weights):
@@ -212,14 +315,15 @@ def layer_tensors(specs, layers):
 
 
 def layer_variables(specs, layers):
-    """name -> float32 numpy of the layers' trained variables under their TensorFlow names (layer.kernel() gives the kernel)."""
+    """name -> float32 numpy of the layers' trained variables under their TensorFlow names (layer.kernel() gives the kernel);
+    of a layer with batch_stats also the moving statistics its forward passes have moved."""
     out = collections.OrderedDict()
     for spec, layer in zip(specs, layers):
         out[spec.kernel] = layer.kernel()
         out[spec.bias] = layer.b.cpu().numpy().copy()
         if spec.bn:
-            out[spec.bn + "/gamma"] = layer.bn[0].cpu().numpy().copy()
-            out[spec.bn + "/beta"] = layer.bn[1].cpu().numpy().copy()
+            for k, name in enumerate(_BN if layer.batch_stats else _BN[:2]):
+                out[spec.bn + "/" + name] = layer.bn[k].cpu().numpy().copy()
     return out
 
 
@@ -228,15 +332,23 @@ def _no_mark(stage):
 
 
 class TailTrainer(object):
-    """The two segment-level layers, built from the checkpoint's variables, and a head_train.HeadTrainer behind them."""
+    """The two segment-level layers, built from the checkpoint's variables, and a head_train.HeadTrainer behind them.
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None):
+    batch_norm="moving" (the default) is inference-mode batch norm with constant moving statistics; "batch" is the reference's
+    training mode (batch_stats_options): step() normalises with the statistics of the batch, differentiates through them and
+    moves the moving statistics, which variables() then returns as well; forward() (the `output` endpoint) stays the inference
+    path, with the CURRENT moving statistics.  trained_names(), l2_assignment() and tensors() do not change: the moving
+    statistics are no optimizer tensors.  **Parity unpinned** against TensorFlow, pinned to torch (include/xvec_hip.h)."""
+
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
         check_supported(params)
         self.params = params
+        self.batch_norm = batch_norm
+        stats = batch_stats_options(params, batch_norm)
         self.specs = segment_variables(params)
         kind = head_train.optimizer_config(params)[0]
         num_slots = {_lib.XV_OPT_SGD: 0, _lib.XV_OPT_MOMENTUM: 1, _lib.XV_OPT_ADAM: 2}[kind]
-        self.layers = [SegLayer(*layer_weights(spec, weights), spec.act, device, num_slots) for spec in self.specs]
+        self.layers = [SegLayer(*layer_weights(spec, weights), spec.act, device, num_slots, **stats) for spec in self.specs]
         if self.layers[1].in_dim != self.layers[0].out_dim:
             raise ValueError("%s has %d rows, %s %d columns" % (self.specs[1].kernel, self.layers[1].in_dim, self.specs[0].kernel,
                                                                   self.layers[0].out_dim))
@@ -267,13 +379,14 @@ class TailTrainer(object):
         return out
 
     def forward(self, pooled):
-        """pooled [n, pool_dim] -> the `output` endpoint [n, embed_dim] on the device, with the current weights."""
+        """pooled [n, pool_dim] -> the `output` endpoint [n, embed_dim] on the device, with the current weights and, in every
+        batch_norm mode, the current moving statistics (inference)."""
         torch = self._torch
         with torch.cuda.device(self.device):
-            return self._forward(losses._f32(pooled, self.device, torch))
+            return self._forward(losses._f32(pooled, self.device, torch), False)
 
-    def _forward(self, x):
-        return self.layers[1].forward(self.layers[0].forward(x))
+    def _forward(self, x, training=True):
+        return layer_forward(self.layers[1], training, layer_forward(self.layers[0], training, x))
 
     def _backward(self, gy, want_gx):
         return self.layers[0].backward(self.layers[1].backward(gy, True), want_gx)

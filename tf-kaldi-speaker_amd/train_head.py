@@ -2,7 +2,7 @@
 egs/voxceleb/v1/nnet/lib/finetune.py, with its positional arguments.
 
     python -m tf_kaldi_speaker_amd.train_head [--gpu N] [--checkpoint C] [--config new.json] [--seed S] [--precision P]
-                                              [--keep-head] [--segment-layers] [--frame-layers] [--conv-layers] pretrain_model train_dir train_spklist valid_dir valid_spklist
+                                              [--keep-head] [--segment-layers] [--frame-layers] [--conv-layers] [--batch-norm {moving,batch}] pretrain_model train_dir train_spklist valid_dir valid_spklist
                                               finetune_model
 
 `--config` names the configuration of the NEW model (loss_func, margins, optimizer, learning-rate schedule, batch shape); without
@@ -14,7 +14,9 @@ multi-tap convolution and the pooling node, through the gradient of statistics p
 three runs: the head first, then `--segment-layers --keep-head` on the directory the first run wrote, then
 `--frame-layers --keep-head` on the directory of the second.  `--conv-layers` (which implies the other two) trains every
 frame-level layer, the multi-tap convolutions included, on the packed features (conv_train.py): a fourth run, on the directory
-of the third.
+of the third.  `--batch-norm batch` (with any of the three) runs the batch norms of the trained layers in training mode, as
+the reference does: the statistics of the batch, the gradient through them, moving-average updates that the checkpoints then
+hold (tail_train.batch_stats_options); the default `moving` keeps the moving statistics constant.
 One line per epoch: `epoch <e> step <s> loss <valid loss> eer <eer> lr <rate>`."""
 import argparse
 import os
@@ -41,6 +43,10 @@ def build_parser():
     parser.add_argument("--conv-layers", action="store_true", help="Train every frame-level layer, the multi-tap convolutions "
                         "(tdnn1 .. tdnn3; tdnn1 .. tdnn7 of the extended TDNN) included: nothing stays frozen but the moving "
                         "statistics; implies --frame-layers and --segment-layers.")
+    parser.add_argument("--batch-norm", choices=("moving", "batch"), default="moving", help="Batch norm of the trained layers: "
+                        "moving = inference mode, the moving statistics stay as the checkpoint has them (default); batch = the "
+                        "statistics of the batch, moving-average updates with params.batchnorm_momentum; needs --segment-layers, "
+                        "--frame-layers or --conv-layers (the head has no batch norm).")
     parser.add_argument("--verbose", action="store_true", help="One line per step.")
     parser.add_argument("pretrain_model", type=str, help="The pre-trained model directory.")
     parser.add_argument("train_dir", type=str, help="The data directory of the training set.")
@@ -52,7 +58,11 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    from . import head_train
+    if args.batch_norm == "batch" and not (args.segment_layers or args.frame_layers or args.conv_layers):
+        parser.error(head_train.BATCH_NORM_ALONE)
     nnet_dir = os.path.join(args.pretrain_model, "nnet")
     config_json = args.config or os.path.join(nnet_dir, "config.json")
     if not os.path.isfile(config_json):
@@ -65,7 +75,6 @@ def main(argv=None):
     weights, _ = model_io.load_weights(nnet_dir, name=args.checkpoint or None)
     if weights is None:
         sys.exit("[ERROR] Cannot find checkpoint in %s." % nnet_dir)
-    from . import head_train
     from .trainer import Trainer
     trainer = Trainer(params, args.pretrain_model, dim, single_cpu=True, device=args.gpu if args.gpu >= 0 else None,
                       precision=args.precision or None)
@@ -76,7 +85,8 @@ def main(argv=None):
                                     args.finetune_model, weights=weights, seed=seed, keep_head=args.keep_head,
                                     precision=args.precision or None, log=print if args.verbose else None,
                                     segment_layers=args.segment_layers or args.frame_layers or args.conv_layers,
-                                    frame_layers=args.frame_layers or args.conv_layers, conv_layers=args.conv_layers)
+                                    frame_layers=args.frame_layers or args.conv_layers, conv_layers=args.conv_layers,
+                                    batch_norm=args.batch_norm)
     for epoch, step, loss, eer, lr in history:
         print("epoch %d step %d loss %f eer %f lr %.8f" % (epoch, step, loss, eer, lr))
     trainer.close()
