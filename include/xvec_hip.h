@@ -793,6 +793,69 @@ int xv_stat_pool_backward(int device, const float* gp_dev, int64_t ldgp, const f
                           const int32_t* offsets_dev, int64_t batch, int64_t total_rows, const float* pooled_dev, int64_t ldp,
                           const float* var_dev, int64_t ldv, float* gx_dev, int64_t ldgx, void* stream);
 
+/* ---- self-attentive pooling of the caller's own packed rows, forward and backward (csrc/att_pool_grad.hip; model/pooling.py:
+ * 150-218): the sibling of xv_stat_pool_* for pooling_type self_attention, everything behind the key and value networks (which on
+ * packed frames are xv_seg_forward / xv_seg_backward).  **Parity unpinned** against TensorFlow; pinned to torch.autograd in
+ * float64 of the einsum formulation (tests/test_att_pool_host.py).
+ * Layout, as xv_stat_pool_*: utterance b owns the rows offsets[b] .. offsets[b + 1]) of key_dev [*, ldk] (Dk = key_dim columns) and
+ *   of value_dev [*, ldv] (Dv = value_dim columns); offsets_dev [batch + 1] is int32 on the device, ascends, offsets[0] >= 0;
+ *   total_rows >= offsets[batch] is a host value that sizes grids and the workspace and nothing else.  H = heads.  query_dev
+ *   [H, ldq] has dq columns, dq = Dk / H with split_key, else Dk; dv = Dv / H with split_value, else Dv.  Head h reads the key
+ *   columns h dq + d when the key is split, else d, and the value columns likewise.  scale is 1 / sqrt(dq) rounded to float32 for
+ *   att_use_scale, else 1.  weights_dev [*, ldw], H columns, in the row numbering of the inputs; pooled_dev [batch, ldp] = [mean |
+ *   std], 2 P wide, P = H dv, column h dv + d (head-major, as combine_last_two_dimensions gives it); var_dev [batch, ldvar], P
+ *   wide, the weighted variance BEFORE the floor.  gp_dev [batch, ldgp] is the gradient with respect to pooled; gkey_dev [*,
+ *   ldgk], gvalue_dev [*, ldgv] have the row numbering of the inputs, gquery_dev [H, ldgq] the shape of the query.  Rows no
+ *   utterance owns and columns beyond the widths are never read or written.
+ * Forward, per utterance of n frames:
+ *   s[t,h] = fl(scale * S), S = sum_d key q in float32: lane l of a wave one fma chain over d = l, l + 64, ... from 0, then an xor
+ *   butterfly of float32 additions, distances 32 down to 1: a function of dq alone;
+ *   w[t,h] = float(exp(double(s) - double(max_t s)) / Z), Z = sum_t exp(..) in double (256 interleaved partial sums in ascending
+ *   frame order, then a binary tree, strides 128 down to 1), rounded to float32 ONCE;
+ *   m = sum_t w v, acc = fma(w, v, acc), and var = sum_t w (v - m)^2 about the COMPUTED mean, d = fl(v - m), acc = fma(w, fl(d d),
+ *   acc), both in the order of xv_stat_pool_forward: 16 partial sums, partial s the frames s, s + 16, ... ascending from 0, then
+ *   the binary tree over the 16, neighbours first.  No division.  std = sqrtf(var <= 1e-12f ? 1e-12f : var).  n = 0: m = 0, var =
+ *   0, std = sqrtf(1e-12f), nothing is written for rows.
+ * Backward:  live = var > 1e-12f read from var_dev (the floor mask is a constant to TensorFlow); gvar = live ? fl(gs / (2 std)) :
+ *   0; gm = gp[p], gs = gp[P + p].
+ *   gvalue[t,(h),d] = sum_h fma(w, fma(2 gvar, fl(v - m), gm), .) from 0, heads ascending (one head when the value is split);
+ *   gw[t,h] = sum_d (gm v + gvar (v - m)^2) and c[h] = sum_d (gm m + gvar var) in double, in ONE order (lane l the columns l, l +
+ *   64, ..., two fmas per column, then the xor butterfly), so that they cancel bit for bit for n = 1;
+ *   gscore[t,h] = float(double(w) (gw - c)), rounded once;  gkey[t,(h),d] = sum_h fma(fl(scale gscore), q, .) from 0, heads
+ *   ascending (one head when the key is split);
+ *   gquery[h,d] = float(double(scale) sum_b sum_t double(gscore) double(key)): per utterance the 16 partial sums and the tree of
+ *   the moments in double, then the utterances in ascending order in double.  The term of d var / d m multiplies sum_t w (v - m) =
+ *   0 and is dropped.  gquery of a batch without frames is 0.
+ *   The per-element bound of every output is derived in the header of csrc/att_pool_grad.hip and restated in
+ *   tests/helpers/ref_att_pool.py: against the float64 rule at the same float32 inputs and the float32 w, m, std, var the forward
+ *   wrote.
+ * Properties (tests/test_gpu_att_pool.py): no floating-point atomics; every output has the same bits on every repeat, for every
+ *   legal ws_bytes, for any total_rows, for every pitch and any 4-byte aligned base (every access is a 4-byte one), and whatever
+ *   the outputs and the workspace held before.  weights, pooled, var, gvalue and gkey of an utterance are a pure function of its
+ *   own rows, the query and its own gradient row; gquery depends on the order of the utterances only through the order of its
+ *   last sum.  Both calls only enqueue work and never wait.
+ * 1 <= heads <= 16, 1 <= key_dim, value_dim <= 4096, total_rows <= 2^24, batch <= 2^20: XV_ERR_UNSUPPORTED beyond.  A split
+ *   dimension that heads does not divide, a leading dimension below its width (ldp, ldgp < 2 P), a missing pointer, a negative
+ *   batch or total_rows: XV_ERR_INVALID before any launch.  batch = 0: XV_OK, nothing touched.
+ * Workspace of the backward (16-byte aligned; XV_ERR_WORKSPACE below the least size): c, gvar, gscore [total_rows, H], a running
+ *   sum and the gquery partials of a panel of utterances; xv_att_pool_workspace_min holds one utterance per panel,
+ *   xv_att_pool_workspace the whole batch, anything between is legal.  Both are 0 for batch = 0 and an xv_status for shapes the
+ *   calls refuse. */
+int64_t xv_att_pool_workspace(int64_t batch, int64_t total_rows, int heads, int key_dim, int value_dim, int split_key,
+                              int split_value);
+int64_t xv_att_pool_workspace_min(int64_t batch, int64_t total_rows, int heads, int key_dim, int value_dim, int split_key,
+                                  int split_value);
+int xv_att_pool_forward(int device, const float* key_dev, int64_t ldk, int key_dim, const float* value_dev, int64_t ldv, int value_dim,
+                        const float* query_dev, int64_t ldq, int heads, int split_key, int split_value, float scale,
+                        const int32_t* offsets_dev, int64_t batch, int64_t total_rows, float* weights_dev, int64_t ldw,
+                        float* pooled_dev, int64_t ldp, float* var_dev, int64_t ldvar, void* stream);
+int xv_att_pool_backward(int device, const float* gp_dev, int64_t ldgp, const float* key_dev, int64_t ldk, int key_dim,
+                         const float* value_dev, int64_t ldv, int value_dim, const float* query_dev, int64_t ldq, int heads,
+                         int split_key, int split_value, float scale, const int32_t* offsets_dev, int64_t batch, int64_t total_rows,
+                         const float* weights_dev, int64_t ldw, const float* pooled_dev, int64_t ldp, const float* var_dev,
+                         int64_t ldvar, float* gkey_dev, int64_t ldgk, float* gvalue_dev, int64_t ldgv, float* gquery_dev,
+                         int64_t ldgq, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- one frame-level layer on packed utterances with its CURRENT weights, forward and backward (csrc/tconv_grad.hip): a W-tap
  * temporal convolution (tf.layers.conv2d(.., (1, W)) / tf.layers.conv1d(.., W) of model/tdnn.py: VALID, stride 1, no dilation) +
  * batch norm in INFERENCE mode + activation.  It is what training tdnn1 .. tdnn3 (tdnn1 .. tdnn7 of the extended TDNN) needs;

@@ -47,6 +47,7 @@ EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_op
            "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_loss_classifier_grad", "xv_opt_workspace", "xv_opt_step",
            "xv_seg_workspace", "xv_seg_workspace_min", "xv_seg_forward", "xv_seg_backward",
            "xv_stat_pool_forward", "xv_stat_pool_backward",
+           "xv_att_pool_workspace", "xv_att_pool_workspace_min", "xv_att_pool_forward", "xv_att_pool_backward",
            "xv_tconv_workspace", "xv_tconv_workspace_min", "xv_tconv_forward_workspace", "xv_tconv_forward", "xv_tconv_backward",
            "xv_bn_batch_workspace", "xv_bn_batch_workspace_min", "xv_bn_batch_forward", "xv_bn_batch_backward",
            "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss",
@@ -230,6 +231,14 @@ def load():
                                     vp, i64, vp]
     lib.xv_stat_pool_forward.argtypes = [i32, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp]
     lib.xv_stat_pool_backward.argtypes = [i32, vp, i64, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp]
+    lib.xv_att_pool_workspace.argtypes = [i64, i64, i32, i32, i32, i32, i32]
+    lib.xv_att_pool_workspace.restype = i64
+    lib.xv_att_pool_workspace_min.argtypes = [i64, i64, i32, i32, i32, i32, i32]
+    lib.xv_att_pool_workspace_min.restype = i64
+    lib.xv_att_pool_forward.argtypes = [i32, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, C.c_float, vp, i64, i64, vp, i64, vp, i64,
+                                        vp, i64, vp]
+    lib.xv_att_pool_backward.argtypes = [i32, vp, i64, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, C.c_float, vp, i64, i64, vp, i64,
+                                         vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     lib.xv_tconv_workspace.argtypes = [i64, i64, i64, i32, i32, i32]
     lib.xv_tconv_workspace.restype = i64
     lib.xv_tconv_workspace_min.argtypes = [i64, i64, i64, i32, i32, i32]

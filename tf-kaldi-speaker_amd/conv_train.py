@@ -221,8 +221,10 @@ class ConvTrainer(frame_train.StackedTrainer):
             raise ValueError("every utterance needs more than the %d frames of context" % self.context)
         return off
 
-    def _walk(self, x, off, mark, training=True):
+    def _walk(self, x, off, mark, training=True, keep=None):
         for i, layer in enumerate(self.frame_layers):
             x, off = tail_train.layer_forward(layer, training, x.contiguous(), off)
+            if keep is not None:
+                keep[i] = (x, off)
             mark("frame_forward/%d" % i)
         return x, off

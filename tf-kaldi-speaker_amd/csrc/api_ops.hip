@@ -582,6 +582,96 @@ int xv_stat_pool_backward(int device, const float* gp_dev, int64_t ldgp, const f
   });
 }
 
+namespace {
+
+// the shapes of one attentive-pooling call: per-head widths and the pooled width, or the status that refuses them
+struct AttShape { int dq, dv, P; };
+
+int att_pool_check(const char* op, int heads, int key_dim, int value_dim, int split_key, int split_value, int64_t batch,
+                   int64_t total_rows, int64_t ldk, int64_t ldv, int64_t ldq, int64_t ldw, int64_t ldp, int64_t ldvar, AttShape* sh) {
+  if (heads < 1 || heads > 16 || key_dim < 1 || key_dim > 4096 || value_dim < 1 || value_dim > 4096 || total_rows > (1 << 24) ||
+      batch > (1 << 20))
+    return fail(nullptr, XV_ERR_UNSUPPORTED,
+                "%s: 1 <= heads <= 16, 1 <= key_dim, value_dim <= 4096, total_rows <= 2^24, batch <= 2^20, got %d, %d, %d, %lld, %lld",
+                op, heads, key_dim, value_dim, (long long)total_rows, (long long)batch);
+  if ((split_key && key_dim % heads != 0) || (split_value && value_dim % heads != 0))
+    return fail(nullptr, XV_ERR_INVALID, "%s: a split dimension must be a multiple of heads", op);
+  sh->dq = split_key ? key_dim / heads : key_dim;
+  sh->dv = split_value ? value_dim / heads : value_dim;
+  sh->P = heads * sh->dv;
+  if (batch < 0 || total_rows < 0 || ldk < key_dim || ldv < value_dim || ldq < sh->dq || ldw < heads || ldp < 2 * (int64_t)sh->P ||
+      ldvar < sh->P)
+    return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
+  return XV_OK;
+}
+
+int64_t att_pool_ws(int64_t batch, int64_t total_rows, int heads, int key_dim, int value_dim, int split_key, int split_value,
+                    bool least) {
+  AttShape sh;
+  const int rc = att_pool_check("xv_att_pool_workspace", heads, key_dim, value_dim, split_key, split_value, batch, total_rows, key_dim,
+                                value_dim, key_dim, heads, (int64_t)1 << 40, (int64_t)1 << 40, &sh);
+  if (rc != XV_OK) return rc;
+  return att_pool_workspace_bytes(batch, total_rows, heads, sh.dq, sh.P, least ? 1 : batch);
+}
+
+}  // namespace
+
+// self-attentive pooling of the caller's packed rows, and its gradient (include/xvec_hip.h, csrc/att_pool_grad.hip)
+int64_t xv_att_pool_workspace(int64_t batch, int64_t total_rows, int heads, int key_dim, int value_dim, int split_key,
+                              int split_value) {
+  return att_pool_ws(batch, total_rows, heads, key_dim, value_dim, split_key, split_value, false);
+}
+
+int64_t xv_att_pool_workspace_min(int64_t batch, int64_t total_rows, int heads, int key_dim, int value_dim, int split_key,
+                                  int split_value) {
+  return att_pool_ws(batch, total_rows, heads, key_dim, value_dim, split_key, split_value, true);
+}
+
+int xv_att_pool_forward(int device, const float* key_dev, int64_t ldk, int key_dim, const float* value_dev, int64_t ldv, int value_dim,
+                        const float* query_dev, int64_t ldq, int heads, int split_key, int split_value, float scale,
+                        const int32_t* offsets_dev, int64_t batch, int64_t total_rows, float* weights_dev, int64_t ldw,
+                        float* pooled_dev, int64_t ldp, float* var_dev, int64_t ldvar, void* stream) {
+  AttShape sh;
+  const int rc = att_pool_check("xv_att_pool_forward", heads, key_dim, value_dim, split_key, split_value, batch, total_rows, ldk, ldv,
+                                ldq, ldw, ldp, ldvar, &sh);
+  if (rc != XV_OK) return rc;
+  if (batch == 0) return XV_OK;
+  if (!key_dev || !value_dev || !query_dev || !offsets_dev || !weights_dev || !pooled_dev || !var_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_att_pool_forward: null pointer");
+  return with_device(device, "xv_att_pool_forward", [&] {
+    return launch_att_pool_forward(key_dev, ldk, sh.dq, split_key != 0, value_dev, ldv, sh.dv, split_value != 0, query_dev, ldq, heads,
+                                   scale, offsets_dev, batch, total_rows, weights_dev, ldw, pooled_dev, ldp, var_dev, ldvar,
+                                   to_stream(stream));
+  });
+}
+
+int xv_att_pool_backward(int device, const float* gp_dev, int64_t ldgp, const float* key_dev, int64_t ldk, int key_dim,
+                         const float* value_dev, int64_t ldv, int value_dim, const float* query_dev, int64_t ldq, int heads,
+                         int split_key, int split_value, float scale, const int32_t* offsets_dev, int64_t batch, int64_t total_rows,
+                         const float* weights_dev, int64_t ldw, const float* pooled_dev, int64_t ldp, const float* var_dev,
+                         int64_t ldvar, float* gkey_dev, int64_t ldgk, float* gvalue_dev, int64_t ldgv, float* gquery_dev,
+                         int64_t ldgq, void* ws_dev, int64_t ws_bytes, void* stream) {
+  AttShape sh;
+  int rc = att_pool_check("xv_att_pool_backward", heads, key_dim, value_dim, split_key, split_value, batch, total_rows, ldk, ldv, ldq,
+                          ldw, ldp, ldvar, &sh);
+  if (rc != XV_OK) return rc;
+  if (ldgp < 2 * (int64_t)sh.P || ldgk < key_dim || ldgv < value_dim || ldgq < sh.dq)
+    return fail(nullptr, XV_ERR_INVALID, "xv_att_pool_backward: bad dimensions");
+  if (batch == 0) return XV_OK;
+  if (!gp_dev || !key_dev || !value_dev || !query_dev || !offsets_dev || !weights_dev || !pooled_dev || !var_dev || !gkey_dev ||
+      !gvalue_dev || !gquery_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_att_pool_backward: null pointer");
+  if ((rc = layer_ws_check("xv_att_pool_backward", ws_dev, ws_bytes,
+                           att_pool_workspace_bytes(batch, total_rows, heads, sh.dq, sh.P, 1))) != XV_OK)
+    return rc;
+  return with_device(device, "xv_att_pool_backward", [&] {
+    return launch_att_pool_backward(gp_dev, ldgp, key_dev, ldk, sh.dq, split_key != 0, value_dev, ldv, sh.dv, split_value != 0,
+                                    query_dev, ldq, heads, scale, offsets_dev, batch, total_rows, weights_dev, ldw, pooled_dev, ldp,
+                                    var_dev, ldvar, gkey_dev, ldgk, gvalue_dev, ldgv, gquery_dev, ldgq, ws_dev, ws_bytes,
+                                    to_stream(stream));
+  });
+}
+
 // a frame-level layer on packed utterances: W-tap temporal convolution + batch norm + activation (include/xvec_hip.h,
 // csrc/tconv_grad.hip)
 int64_t xv_tconv_workspace(int64_t batch, int64_t total_in, int64_t total_out, int taps, int channels, int out_dim) {

@@ -407,6 +407,20 @@ hipError_t launch_stat_pool_backward(const float* gp, int64_t ldgp, const float*
                                      int64_t batch, int64_t total_rows, const float* pooled, int64_t ldp, const float* var,
                                      int64_t ldv, float* gx, int64_t ldgx, hipStream_t s);
 
+// self-attentive pooling of the caller's own packed rows and its gradient (csrc/att_pool_grad.hip); dq and dv are the per-head
+// widths, P = H dv; `panel` utterances of gquery partial sums fit the workspace (1 .. batch)
+int64_t att_pool_workspace_bytes(int64_t batch, int64_t total_rows, int H, int dq, int P, int64_t panel);
+hipError_t launch_att_pool_forward(const float* key, int64_t ldk, int dq, int split_k, const float* value, int64_t ldv, int dv,
+                                   int split_v, const float* query, int64_t ldq, int H, float scale, const int32_t* offsets,
+                                   int64_t batch, int64_t total_rows, float* w, int64_t ldw, float* pooled, int64_t ldp, float* var,
+                                   int64_t ldvar, hipStream_t s);
+hipError_t launch_att_pool_backward(const float* gp, int64_t ldgp, const float* key, int64_t ldk, int dq, int split_k,
+                                    const float* value, int64_t ldv, int dv, int split_v, const float* query, int64_t ldq, int H,
+                                    float scale, const int32_t* offsets, int64_t batch, int64_t total_rows, const float* w,
+                                    int64_t ldw, const float* pooled, int64_t ldp, const float* var, int64_t ldvar, float* gkey,
+                                    int64_t ldgk, float* gvalue, int64_t ldgv, float* gquery, int64_t ldgq, void* ws, int64_t ws_bytes,
+                                    hipStream_t s);
+
 // back-end training statistics (csrc/backend.hip): G = sum_r w_r (x_r - c)(x_r - c)^T in double (c, w may be null), both
 // triangles of g [d, d]; ws holds gram_f64_workspace_bytes(n, d) bytes; rows fp32, or double in the _rows64 form
 int64_t gram_f64_workspace_bytes(int64_t n, int d);

@@ -189,19 +189,24 @@ class StackedTrainer(object):
             if self._width(b) != a.out_dim:
                 raise ValueError(self._CHAIN % (sb.kernel, self._width(b), sa.kernel, a.out_dim))
         self.in_dim, self.channels = self._width(self.frame_layers[0]), self.frame_layers[-1].out_dim
-        if self.tail.pool_dim != 2 * self.channels:
-            raise ValueError("%s has %d rows, statistics pooling of %d channels gives %d" % (self.tail.specs[0].kernel, self.tail.pool_dim,
-                                                                                             self.channels, 2 * self.channels))
+        self.device = int(device)
+        self.pool = self._make_pool(weights, num_slots)
         self.specs = self.frame_specs + tuple(self.tail.specs)
         self.layers = self.frame_layers + list(self.tail.layers)
         self.head = self.tail.head
         self.embed_dim = self.tail.embed_dim
-        self.device = int(device)
-        self.pool = StatPool(self.channels, device)
         self.l2 = self._l2(params)
         self._torch = losses._need_device()
         self.tail._fit_workspace(self.layers)
         self.num_steps = 0                                                   # adam's t, shared by every tensor
+
+    def _make_pool(self, weights, num_slots):
+        """The pooling stage between the frame layers and the tail, checked against the tail's input width: statistics pooling
+        here; att_train's trainers put the key and value networks and the attentive pooling in its place."""
+        if self.tail.pool_dim != 2 * self.channels:
+            raise ValueError("%s has %d rows, statistics pooling of %d channels gives %d" % (self.tail.specs[0].kernel, self.tail.pool_dim,
+                                                                                             self.channels, 2 * self.channels))
+        return StatPool(self.channels, self.device)
 
     def _layer(self, spec, kernel, bias, bn, device, num_slots):
         """The frame layer of `spec` from the checkpoint's kernel, bias and batch-norm vectors (with self._stats(kernel))."""
@@ -219,8 +224,9 @@ class StackedTrainer(object):
         """The offsets as _walk takes them, checked as far as the subclass checks them."""
         return offsets
 
-    def _walk(self, x, offsets, mark, training=True):
-        """x through every frame layer, mark("frame_forward/<i>") behind layer i -> (the last layer's rows, their offsets)."""
+    def _walk(self, x, offsets, mark, training=True, keep=None):
+        """x through every frame layer, mark("frame_forward/<i>") behind layer i -> (the last layer's rows, their offsets).
+        keep, a dict if given, receives (rows, offsets) of layer i's output under i: the endpoints an attention reads."""
         raise NotImplementedError
 
     def tensors(self):
@@ -299,8 +305,10 @@ class FrameTrainer(StackedTrainer):
     def _width(self, layer):
         return layer.in_dim
 
-    def _walk(self, x, offsets, mark, training=True):
+    def _walk(self, x, offsets, mark, training=True, keep=None):
         for i, layer in enumerate(self.frame_layers):
             x = tail_train.layer_forward(layer, training, x)
+            if keep is not None:
+                keep[i] = (x, offsets)
             mark("frame_forward/%d" % i)
         return x, offsets

@@ -285,6 +285,8 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     multi-tap convolutions included, on the packed features, in exact fp32 whatever `precision` says.  The checkpoints then hold
     the new convolution kernels in the shape the input had, and biases, gamma and beta; the moving statistics and every other
     variable are unchanged.
+    On a self_attention model frame_layers and conv_layers go to att_train.AttFrameTrainer / AttConvTrainer (after
+    att_train.check_supported): the key and value networks and the query are trained and written as well.
     batch_norm="batch" (with any of the three; alone it is refused, the head has no batch norm) runs the batch norms of the
     trained layers in training mode (tail_train.batch_stats_options): the checkpoints then also hold their moving_mean and
     moving_variance, and the validation after each epoch, the unchanged Trainer.valid on the written checkpoint, normalises with
@@ -314,13 +316,19 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     rule = LearningRateRule(params, learning_rate if schedule is None else schedule[0], schedule)
 
     endpoint = trainer.embeddings
+    attention = (conv_layers or frame_layers) and p.get("pooling_type") == "self_attention"
+    if attention:                                                        # the attention trainers of att_train.py, same steps
+        from . import att_train
+        att_train.check_supported(params, conv_layers)                   # before the trainer is touched
     if conv_layers:
         from . import conv_train
-        conv_train.check_supported(params)                               # before the trainer is touched
+        if not attention:
+            conv_train.check_supported(params)                           # before the trainer is touched
         segment_layers = frame_layers = True
     elif frame_layers:
         from . import frame_train
-        frame_train.check_supported(params)                              # before the trainer is touched
+        if not attention:
+            frame_train.check_supported(params)                          # before the trainer is touched
         segment_layers = True
         trainer.embeddings = frame_train.frozen_node(params)
     else:
@@ -338,7 +346,10 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
             k = weights.get(model_io.SOFTMAX_KERNEL)
             if k is not None and tuple(k.shape) == (embed_dim, num_classes):
                 kernel, bias = np.asarray(k), weights.get(model_io.SOFTMAX_BIAS)
-        if conv_layers:
+        if attention:
+            make = att_train.AttConvTrainer if conv_layers else att_train.AttFrameTrainer
+            head = make(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
+        elif conv_layers:
             head = conv_train.ConvTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
         elif frame_layers:
             head = frame_train.FrameTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)

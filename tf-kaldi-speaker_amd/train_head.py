@@ -16,7 +16,9 @@ three runs: the head first, then `--segment-layers --keep-head` on the directory
 frame-level layer, the multi-tap convolutions included, on the packed features (conv_train.py): a fourth run, on the directory
 of the third.  `--batch-norm batch` (with any of the three) runs the batch norms of the trained layers in training mode, as
 the reference does: the statistics of the batch, the gradient through them, moving-average updates that the checkpoints then
-hold (tail_train.batch_stats_options); the default `moving` keeps the moving statistics constant.
+hold (tail_train.batch_stats_options); the default `moving` keeps the moving statistics constant.  On a `self_attention` model
+`--frame-layers` and `--conv-layers` also train the key and value networks and the query, through the gradient of the
+attentive pooling (att_train.py).
 One line per epoch: `epoch <e> step <s> loss <valid loss> eer <eer> lr <rate>`."""
 import argparse
 import os
