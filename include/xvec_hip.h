@@ -152,6 +152,10 @@ int xv_finalize(xv_handle* h);
  * switch them off to prove which path ran.  "att_fusion" (default 1): attention scores / weighted moments computed in
  * the epilogues of the last key layer / the value layer instead of from stored activations; "slab3" (default 1): one-tap
  * layers on the kernel with three activation-slab buffers (0: the two-buffer kernel, bit-identical results).
+ * "first_walk" (default 1): a first layer of at most 5 taps over a feature dimension of at most 32 whose output feeds a
+ * two-unit layer (XV_PREC_F16F6) runs on workgroups that walk the row tiles with their weights resident; 2: also when it
+ * writes split-blocked or fp32 rows (every precision but f32); 0: always on the tile kernel of the other convolutions.
+ * Bit-identical results in all three settings.
  * "grid_compact" (default 1): ResNet convolutions enumerate output bins only (0: every grid position, bit-identical);
  * "grid_f6" (default 1; set before xv_finalize, it decides the weight formats): XV_PREC_F16F6 runs the eligible ResNet
  * convolutions on the two-unit kernel (0: on the f16x3 kernels).

@@ -207,7 +207,13 @@ int launch_first_layer(const Run& r, const PlanStep& st, const Layer& L, GemmArg
     a.cin = a.K;
   }
   if (r.f16 && !guarded) XV_HIP(h, launch_feat_utt_guard(r.feats, r.feat_ld, L.cin, r.off, r.B, r.ovf(), r.s));
-  XV_HIP(h, launch_gemm_bf16x3(a, r.s));
+  // one 32-channel block and at most 5 taps: workgroups that walk the M tiles with resident weights (csrc/gemm_first.hip; the
+  // same sums, bit-identical output).  By default only where it measured faster, as the producer of the two-unit block format
+  // (76 -> 62 us; with the split-blocked / fp32 epilogue the two kernels tie within the noise: profiles/first_layer.md);
+  // xv_set_option "first_walk" 2 takes it for every shape it accepts, 0 never
+  bool walked = false;
+  if (L.cin_pad && (h->opt_first_walk > 1 || (h->opt_first_walk == 1 && a.ysb_f6))) XV_HIP(h, launch_gemm_first(a, r.s, &walked));
+  if (!walked) XV_HIP(h, launch_gemm_bf16x3(a, r.s));
   return XV_OK;
 }
 

@@ -411,6 +411,7 @@ int xv_set_option(xv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "tail_split")) h->opt_tail_split = value != 0;
   else if (!strcmp(name, "att_fusion")) h->opt_att_fusion = value != 0;
   else if (!strcmp(name, "slab3")) h->opt_slab3 = value != 0;
+  else if (!strcmp(name, "first_walk")) h->opt_first_walk = value < 0 ? 0 : (value > 2 ? 2 : value);
   else if (!strcmp(name, "grid_f6")) h->opt_grid_f6 = value != 0;      // (before xv_finalize: it decides the weight formats)
   else if (!strcmp(name, "grid_compact")) h->opt_grid_compact = value != 0;
   else if (!strcmp(name, "profile_dominant")) h->opt_profile_dominant = value != 0;

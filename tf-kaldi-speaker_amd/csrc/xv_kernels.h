@@ -148,6 +148,10 @@ hipError_t launch_feat_stage_sb(const float* x, int64_t ldx, int cin, const int3
 
 // bf16x3 / f16x3 split path (3x v_mfma_f32_16x16x32_{bf16,f16} per product tile).
 hipError_t launch_gemm_bf16x3(const GemmArgs& a, hipStream_t s);
+// the first layer as staged split-blocked rows of ONE 32-channel block, at most 5 taps, Npad % 128 == 0, plain 1-D rows and none of
+// residual / fused pooling / attention epilogues: walking workgroups with resident weights (gemm_first.hip), the sums of
+// launch_gemm_bf16x3 in the same order.  *taken = false (and nothing launched) for every other shape: the caller uses the tile kernel.
+hipError_t launch_gemm_first(const GemmArgs& a, hipStream_t s, bool* taken);
 // two-unit split of the multi-tap convolutions (XV_PREC_F16F6: f16 hi*hi + two block-scaled fp6 cross terms), gemm_f16f6.hip
 hipError_t launch_gemm_f16f6(const GemmArgs& a, hipStream_t s);
 // reduce of a K-split tail whose slices hold raw sums (a.partial / a.tail_mt / a.ksplit in {2, 4, 8}; rows from M tile nMain on):

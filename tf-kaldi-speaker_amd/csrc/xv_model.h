@@ -147,6 +147,8 @@ struct xv_handle {
   int opt_tail_split = 1;                             // K-split of the last, nearly empty round of GEMM tiles
   int opt_grid_f6 = 1;                                // XV_PREC_F16F6: the stride-1 3 x 3 ResNet convolutions of >= 128 channels on the two-unit kernel
   int opt_slab3 = 1;                                  // one-tap GEMM layers on the three-slab-buffer kernel
+  int opt_first_walk = 1;                             // staged first layer (<= 5 taps) on the walking-workgroup kernel (gemm_first.hip):
+                                                      // 1 = as the producer of the two-unit block format, 2 = every shape it takes, 0 = never
   int opt_grid_compact = 1;                           // ResNet grid convolutions enumerate output bins only (split precisions)
   int opt_att_fusion = 1;                             // attention scores / weighted moments in the GEMM epilogues
   int opt_profile_dominant = 0;                       // xv_profile_*: bracket only the step with the most FLOPs of a plan

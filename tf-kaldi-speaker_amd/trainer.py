@@ -262,8 +262,8 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ device-level predict
     def set_option(self, name, value):
-        """Execution option of the library (xv_set_option: "pool_fusion", "tail_split", "att_fusion", "slab3", "grid_f6",
-        "grid_compact", "profile_dominant"); affects plans created later ("grid_f6": set it before the weights are loaded)."""
+        """Execution option of the library (xv_set_option: "pool_fusion", "tail_split", "att_fusion", "slab3", "first_walk",
+        "grid_f6", "grid_compact", "profile_dominant"); affects plans created later ("grid_f6": set it before the weights are loaded)."""
         self._options[name] = int(value)
         if self._h is not None:
             _lib.check(self._lib.xv_set_option(self._h, name.encode(), int(value)), self._h)
