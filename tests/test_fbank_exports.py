@@ -1,9 +1,8 @@
-"""The fbank entry points are declared in include/xvec_hip.h, listed in _lib.EXPORTS and exported by the built library."""
+"""The fbank operator in the build recipe and the field order of its options.  That its entry points are declared, listed and
+exported with the header's signatures is tests/test_binding_host.py."""
 import ctypes
 import os
 import re
-
-NAMES = ["xv_fbank_create", "xv_fbank_destroy", "xv_fbank_num_frames", "xv_fbank_num_feats", "xv_fbank_compute"]
 
 
 def test_fbank_symbols_are_declared_listed_and_exported(repo_root):
@@ -11,10 +10,6 @@ def test_fbank_symbols_are_declared_listed_and_exported(repo_root):
     g.build()
     from tf_kaldi_speaker_amd import _lib
     hdr = open(os.path.join(repo_root, "include", "xvec_hip.h")).read()
-    declared = set(re.findall(r"\b(xv_[a-z0-9_]+)\s*\(", hdr))
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert name in declared and name in _lib.EXPORTS and hasattr(lib, name), name
     # the ctypes mirror has the size and the field order the header's struct has
     body = re.search(r"typedef struct \{([^}]*)\} xv_fbank_opts;", hdr).group(1)
     fields = re.findall(r"^\s*(?:int32_t|float)\s+(\w+);", body, flags=re.M)
@@ -23,7 +18,5 @@ def test_fbank_symbols_are_declared_listed_and_exported(repo_root):
     assert [f for f, _ in _lib.FbankOpts._fields_] == fields
     for (f, t), c in zip(_lib.FbankOpts._fields_, re.findall(r"^\s*(int32_t|float)\s+\w+;", body, flags=re.M)):
         assert t is (ctypes.c_int32 if c == "int32_t" else ctypes.c_float), f
-    # xv_mfcc_opts did not move
-    assert ctypes.sizeof(_lib.MfccOpts) == 19 * 4
     # the kernel lives in the MFCC's translation unit: no new source in the build recipe
     assert "fbank_kernel" in open(os.path.join(g.CSRC, "mfcc.hip")).read() and not any("fbank" in s for s in g.SOURCES)

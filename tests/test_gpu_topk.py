@@ -276,7 +276,7 @@ def test_plda_both_directions(lib, mixed):
     """A synthetic model (d = 16).  per="enroll" is llr_matrix's operand order; per="test" is xv_plda_matrix called with the
     test side first (tau as the row bias, rho as the column bias; an enrolment set of mixed num_utts has no tau: zeros)."""
     import torch
-    from tf_kaldi_speaker_amd import _lib, plda, scoring
+    from tf_kaldi_speaker_amd import _lib, plda
     rng = np.random.default_rng(8)
     d = 16
     pm, ptm, psi = ref_plda.random_model(rng, d)
@@ -298,8 +298,8 @@ def test_plda_both_directions(lib, mixed):
     k = enroll.k
     tau = test.tau(enroll.uniform_n) if not mixed else torch.zeros(m, dtype=torch.float32, device=DEV)
     swapped = torch.empty((m, n), dtype=torch.float32, device=DEV)
-    _lib.check(lib.xv_plda_matrix(0, scoring._p(test.packed), test.packed.shape[1], m, scoring._p(tau), scoring._p(enroll.packed),
-                                  enroll.packed.shape[1], n, scoring._p(enroll.bias), k, scoring._p(swapped), n, None))
+    _lib.check(lib.xv_plda_matrix(0, _lib.ptr(test.packed), test.packed.shape[1], m, _lib.ptr(tau), _lib.ptr(enroll.packed),
+                                  enroll.packed.shape[1], n, _lib.ptr(enroll.bias), k, _lib.ptr(swapped), n, None))
     st = swapped.cpu().numpy()
     for top_k in (1, 10, 200):                                     # 200 > the 140 enrolment rows: padded
         got = plda.llr_top_k(enroll, test, top_k, per="test", labels_enroll=le, labels_test=lt)

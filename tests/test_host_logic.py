@@ -111,23 +111,24 @@ def test_c_abi_library_exports_every_declared_symbol(repo_root):
     declared = set(re.findall(r"\b(xv_[a-z0-9_]+)\s*\(", hdr))
     from tf_kaldi_speaker_amd import _lib
     assert declared == set(_lib.EXPORTS)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(lib, name), name
-    lib.xv_version.restype = ctypes.c_char_p
+    lib = _lib.declare(ctypes.CDLL(_lib.LIB_PATH))                 # raises, naming it, for a symbol the library lacks
     assert b"gfx950" in lib.xv_version()
-    # the ctypes mirrors have the size the C compiler gives the structs of the header
+    # the seven ctypes mirrors have the size, the field offsets and the field types the C compiler gives the structs of the
+    # header, and the XV_* constants copied into _lib have the header's values
     import subprocess
+    import sys
     import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+    import header_protos
+    source, expect = header_protos.layout_program(_lib)
+    assert len(header_protos.MIRRORS) == 7 and sum(l.startswith("XV_") for l in expect) >= 30
     with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, "sz.c")
+        src = os.path.join(tmp, "layout.c")
         with open(src, "w") as f:
-            f.write('#include <stdio.h>\n#include "xvec_hip.h"\nint main(void) { printf("%zu %zu %zu\\n", sizeof(xv_model_desc), '
-                    'sizeof(xv_plan_info), sizeof(xv_kernel_time)); return 0; }\n')
-        exe = os.path.join(tmp, "sz")
+            f.write(source)
+        exe = os.path.join(tmp, "layout")
         subprocess.run(["gcc", "-I", os.path.join(repo_root, "include"), src, "-o", exe], check=True)
-        sizes = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    assert sizes == [ctypes.sizeof(_lib.ModelDesc), ctypes.sizeof(_lib.PlanInfo), ctypes.sizeof(_lib.KernelTime)]
+        assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")[:-1] == expect
 
 
 def test_trainer_refuses_unsupported_graphs_and_missing_gpu():

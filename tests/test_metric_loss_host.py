@@ -235,18 +235,12 @@ def test_exports_and_sources(repo_root):
     assert "metric_loss.hip" in g.SOURCES and os.path.isfile(os.path.join(g.CSRC, "metric_loss.hip"))
     g.build()
     hdr = open(os.path.join(repo_root, "include", "xvec_hip.h")).read()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in ("xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss"):
-        assert re.search(r"\b%s\s*\(" % name, hdr) and name in _lib.EXPORTS and hasattr(lib, name), name
+    lib = _lib.load()
     m = re.search(r"enum \{ XV_METRIC_SEMIHARD = 0, XV_METRIC_ANGULAR_ALL = 1, XV_METRIC_ANGULAR_HARD = 2, XV_METRIC_GE2E_SOFTMAX = 3,\s*"
                   r"XV_METRIC_GE2E_CONTRASTIVE = 4 \};", hdr)
     assert m and (_lib.XV_METRIC_SEMIHARD, _lib.XV_METRIC_ANGULAR_ALL, _lib.XV_METRIC_ANGULAR_HARD, _lib.XV_METRIC_GE2E_SOFTMAX,
                   _lib.XV_METRIC_GE2E_CONTRASTIVE) == (0, 1, 2, 3, 4)
     # the size queries are pure host code: they answer without a device
-    lib.xv_metric_loss_workspace.restype = ctypes.c_int64
-    lib.xv_metric_loss_workspace.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    lib.xv_metric_loss_slot_bytes.restype = ctypes.c_int64
-    lib.xv_metric_loss_slot_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     off = np.array([0, 640, 1280], dtype=np.int64)
     ptr = off.ctypes.data_as(ctypes.c_void_p)
     base = lib.xv_metric_loss_workspace(2, ptr, 512, 0)

@@ -32,30 +32,6 @@ XV_METRIC_SEMIHARD, XV_METRIC_ANGULAR_ALL, XV_METRIC_ANGULAR_HARD, XV_METRIC_GE2
 XV_LOGREG_MAX_SYSTEMS = 8
 XV_LOGREG_MAX_THRESHOLDS = 8
 
-EXPORTS = ["xv_version", "xv_create", "xv_set_tensor", "xv_finalize", "xv_set_option", "xv_check_overflow", "xv_flags_async", "xv_flags_decode", "xv_node_id", "xv_node_context", "xv_layer_two_unit",
-           "xv_plan_create", "xv_plan_query", "xv_plan_destroy", "xv_forward", "xv_profile_begin", "xv_profile_end",
-           "xv_destroy", "xv_last_error",
-           "xv_frontend_cmn_select", "xv_mfcc_create", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_mfcc_compute", "xv_vad_energy",
-           "xv_fbank_create", "xv_fbank_destroy", "xv_fbank_num_frames", "xv_fbank_num_feats", "xv_fbank_compute",
-           "xv_length_normalize", "xv_speaker_mean",
-           "xv_score_prepare", "xv_score_matrix", "xv_score_pairs", "xv_score_histogram",
-           "xv_plda_prepare", "xv_plda_matrix", "xv_plda_pairs", "xv_plda_histogram",
-           "xv_cohort_stats_workspace", "xv_cohort_stats", "xv_score_topk_workspace", "xv_score_topk",
-           "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_ahc", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_plda_adapt",
-           "xv_vbx_workspace", "xv_vbx",
-           "xv_loss_prepare_classes", "xv_loss_workspace", "xv_loss_classifier",
-           "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_loss_classifier_grad", "xv_opt_workspace", "xv_opt_step",
-           "xv_seg_workspace", "xv_seg_workspace_min", "xv_seg_forward", "xv_seg_backward",
-           "xv_stat_pool_forward", "xv_stat_pool_backward",
-           "xv_att_pool_workspace", "xv_att_pool_workspace_min", "xv_att_pool_forward", "xv_att_pool_backward",
-           "xv_tconv_workspace", "xv_tconv_workspace_min", "xv_tconv_forward_workspace", "xv_tconv_forward", "xv_tconv_backward",
-           "xv_bn_batch_workspace", "xv_bn_batch_workspace_min", "xv_bn_batch_forward", "xv_bn_batch_backward",
-           "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_metric_loss",
-           "xv_gram_f64_workspace", "xv_gram_f64", "xv_gram_f64_rows64", "xv_class_mean_f64",
-           "xv_logreg_workspace", "xv_logreg_stats", "xv_score_fuse",
-           "xv_reverb_tile", "xv_reverb_workspace", "xv_reverb",
-           "xv_ark_open", "xv_ark_open_scp", "xv_ark_scp_count", "xv_ark_scp_shapes", "xv_ark_next_batch", "xv_ark_pending_shape", "xv_ark_skipped", "xv_ark_set_copy_threads", "xv_ark_error", "xv_ark_close", "xv_ark_format_vectors", "xv_crc32c", "xv_pack_rows"]
-
 
 class ModelDesc(C.Structure):
     _fields_ = [
@@ -123,183 +99,189 @@ class KernelTime(C.Structure):
                 ("flops", C.c_int64), ("bytes", C.c_int64)]
 
 
+vp, i32, i64, f32, f64, u32, cstr, P = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_uint32, C.c_char_p, C.POINTER
+
+# Every entry point of include/xvec_hip.h, in the header's order and under its section headings: (name, return type, argument
+# types).  tests/test_binding_host.py holds each entry to the header's prototype.
+SIGNATURES = (
+    # model, plans, forward, profiling
+    ("xv_version", cstr, ()),
+    ("xv_create", i32, (P(ModelDesc), i32, P(vp))),
+    ("xv_set_tensor", i32, (vp, cstr, vp, P(i64), i32)),
+    ("xv_finalize", i32, (vp,)),
+    ("xv_set_option", i32, (vp, cstr, i32)),
+    ("xv_check_overflow", i32, (vp, i32)),
+    ("xv_flags_async", i32, (vp, vp, vp)),
+    ("xv_flags_decode", i32, (vp,)),
+    ("xv_node_id", i32, (vp, cstr)),
+    ("xv_layer_two_unit", i32, (vp, cstr)),
+    ("xv_node_context", i32, (vp, i32)),
+    ("xv_plan_create", i32, (vp, vp, i32, i32, vp, P(vp))),
+    ("xv_plan_query", i32, (vp, P(PlanInfo))),
+    ("xv_plan_destroy", None, (vp,)),
+    ("xv_forward", i32, (vp, vp, vp, i32, vp, i64, vp, i64, vp)),
+    ("xv_profile_begin", i32, (vp, i32)),
+    ("xv_profile_end", i32, (vp, P(KernelTime), i32, P(i32))),
+    # feature front-end on the GPU
+    ("xv_frontend_cmn_select", i32, (i32, vp, i32, i32, vp, i32, vp, i64, i32, i32, i32, vp, vp, vp)),
+    # MFCC features and energy VAD on the GPU
+    ("xv_mfcc_create", i32, (P(MfccOpts), i32, P(vp))),
+    ("xv_mfcc_destroy", None, (vp,)),
+    ("xv_mfcc_num_frames", i64, (vp, i64)),
+    ("xv_mfcc_compute", i32, (vp, vp, vp, vp, i32, vp, i64, vp)),
+    ("xv_vad_energy", i32, (i32, vp, i64, vp, i32, f32, f32, i32, f32, vp, vp)),
+    # Fbank features on the GPU
+    ("xv_fbank_create", i32, (P(FbankOpts), i32, P(vp))),
+    ("xv_fbank_destroy", None, (vp,)),
+    ("xv_fbank_num_frames", i64, (vp, i64)),
+    ("xv_fbank_num_feats", i32, (vp,)),
+    ("xv_fbank_compute", i32, (vp, vp, vp, vp, i32, vp, i64, vp, vp)),
+    # post-step on the GPU
+    ("xv_length_normalize", i32, (i32, vp, i64, i64, i32, i32, vp, i64, vp)),
+    ("xv_speaker_mean", i32, (i32, vp, i64, i32, vp, vp, i64, vp, i64, vp)),
+    # cosine scoring on the GPU
+    ("xv_score_prepare", i32, (i32, vp, i64, i64, i32, vp, vp, i64, i32, i32, i32, f32, vp, i64, vp)),
+    ("xv_score_matrix", i32, (i32, vp, i64, i64, vp, i64, i64, i32, vp, i64, vp)),
+    ("xv_score_pairs", i32, (i32, vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp)),
+    ("xv_score_histogram", i32, (i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, vp)),
+    # PLDA scoring on the GPU
+    ("xv_plda_prepare", i32, (i32, vp, i64, i64, i32, vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp)),
+    ("xv_plda_matrix", i32, (i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, i64, vp)),
+    ("xv_plda_pairs", i32, (i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, vp, i64, vp, vp)),
+    ("xv_plda_histogram", i32, (i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, f64, f64, i32, vp, vp, vp)),
+    # score normalisation on the GPU
+    ("xv_cohort_stats_workspace", i64, (i64, i64, i32)),
+    ("xv_cohort_stats", i32, (i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp)),
+    # identification on the GPU
+    ("xv_score_topk_workspace", i64, (i64, i64, i32)),
+    ("xv_score_topk", i32, (i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, vp)),
+    # speaker clustering on the GPU
+    ("xv_ahc_matrix_floats", i64, (i64,)),
+    ("xv_ahc_workspace", i64, (i64, vp)),
+    ("xv_ahc", i32, (i32, vp, vp, vp, i64, f64, vp, vp, vp, vp, vp, vp, i64, vp)),
+    # per-recording PCA adaptation of a PLDA model on the GPU
+    ("xv_plda_adapt_workspace", i64, (i64, i32)),
+    ("xv_plda_adapt_slot_bytes", i64, (i32,)),
+    ("xv_plda_adapt", i32, (i32, vp, i64, vp, i64, i32, vp, vp, vp, f64, vp, vp, vp, vp, vp, vp, i64, vp)),
+    # VB-HMM resegmentation of clustered x-vectors on the GPU
+    ("xv_vbx_workspace", i64, (i64, vp, vp, i32)),
+    ("xv_vbx", i32, (i32, vp, i64, vp, vp, i64, i32, vp, vp, i32, vp, vp, f64, f64, f64, i32, f64, vp, vp, vp, vp, i64, vp)),
+    # classifier-head validation loss on the GPU
+    ("xv_loss_prepare_classes", i32, (i32, vp, i64, i32, i64, i32, vp, i64, vp)),
+    ("xv_loss_workspace", i64, (i64, i64)),
+    ("xv_loss_classifier", i32, (i32, vp, i64, i64, i32, vp, vp, i64, i64, vp, i32, f64, f64, vp, vp, vp, vp, vp, i64, vp)),
+    # loss and gradients of the classifier heads
+    ("xv_loss_grad_workspace", i64, (i64, i64, i32)),
+    ("xv_loss_grad_workspace_min", i64, (i64, i64, i32)),
+    ("xv_loss_classifier_grad", i32, (i32, vp, i64, i64, i32, vp, vp, i64, i64, vp, i32, f64, f64, f64, vp, vp, vp, vp, vp, i64, vp,
+                                      vp, vp, i64, vp)),
+    # one optimizer step on one float32 parameter tensor
+    ("xv_opt_workspace", i64, (i64,)),
+    ("xv_opt_step", i32, (i32, i32, i32, vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, vp, i64, vp)),
+    # one segment-level layer with its current weights, forward and backward
+    ("xv_seg_workspace", i64, (i64, i32, i32)),
+    ("xv_seg_workspace_min", i64, (i64, i32, i32)),
+    ("xv_seg_forward", i32, (i32, vp, i64, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64, vp)),
+    ("xv_seg_backward", i32, (i32, vp, i64, vp, i64, vp, i64, i64, i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp,
+                              vp, i64, vp)),
+    # statistics pooling of the caller's own packed rows, forward and backward
+    ("xv_stat_pool_forward", i32, (i32, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp)),
+    ("xv_stat_pool_backward", i32, (i32, vp, i64, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp)),
+    # self-attentive pooling of the caller's own packed rows, forward and backward
+    ("xv_att_pool_workspace", i64, (i64, i64, i32, i32, i32, i32, i32)),
+    ("xv_att_pool_workspace_min", i64, (i64, i64, i32, i32, i32, i32, i32)),
+    ("xv_att_pool_forward", i32, (i32, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, f32, vp, i64, i64, vp, i64, vp, i64,
+                                  vp, i64, vp)),
+    ("xv_att_pool_backward", i32, (i32, vp, i64, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, f32, vp, i64, i64, vp, i64,
+                                   vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp)),
+    # one frame-level layer on packed utterances with its current weights, forward and backward
+    ("xv_tconv_workspace", i64, (i64, i64, i64, i32, i32, i32)),
+    ("xv_tconv_workspace_min", i64, (i64, i64, i64, i32, i32, i32)),
+    ("xv_tconv_forward_workspace", i64, (i64, i64)),
+    ("xv_tconv_forward", i32, (i32, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64,
+                               vp, i64, vp)),
+    ("xv_tconv_backward", i32, (i32, vp, i64, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i32,
+                                vp, i64, vp, vp, vp, vp, vp, i64, vp)),
+    # batch norm in training mode behind the stored product z of a trained layer
+    ("xv_bn_batch_workspace", i64, (i64, i32)),
+    ("xv_bn_batch_workspace_min", i64, (i64, i32)),
+    ("xv_bn_batch_forward", i32, (i32, vp, i64, i64, i32, vp, vp, i32, f64, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp)),
+    ("xv_bn_batch_backward", i32, (i32, vp, i64, vp, i64, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, i64, vp)),
+    # metric-learning loss heads on the GPU
+    ("xv_metric_loss_workspace", i64, (i64, vp, i32, i32)),
+    ("xv_metric_loss_slot_bytes", i64, (i32, i32, i32)),
+    ("xv_metric_loss", i32, (i32, vp, i64, vp, i64, i32, vp, i32, i32, f64, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, i64, vp)),
+    # back-end training statistics on the GPU
+    ("xv_gram_f64_workspace", i64, (i64, i32)),
+    ("xv_gram_f64", i32, (i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp)),
+    ("xv_gram_f64_rows64", i32, (i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp)),
+    ("xv_class_mean_f64", i32, (i32, vp, i64, i64, i32, vp, vp, i64, vp, vp, i64, vp)),
+    # score calibration and fusion on the GPU
+    ("xv_logreg_workspace", i64, (i64, i32)),
+    ("xv_logreg_stats", i32, (i32, vp, i64, i64, i32, vp, vp, f64, f64, f64, vp, i32, vp, vp, vp, i64, vp)),
+    ("xv_score_fuse", i32, (i32, vp, i64, i64, i32, vp, vp, vp)),
+    # reverberation and additive noise
+    ("xv_reverb_tile", i32, (P(i32), P(i32))),
+    ("xv_reverb_workspace", i64, (vp, i64, vp, i64, i64, i64, i64, i64)),
+    ("xv_reverb", i32, (i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp)),
+    # host-side ark I/O
+    ("xv_ark_open", i32, (cstr, i32, P(vp))),
+    ("xv_ark_open_scp", i32, (cstr, P(vp))),
+    ("xv_ark_scp_count", i64, (vp,)),
+    ("xv_ark_scp_shapes", i32, (vp, vp, vp, i64)),
+    ("xv_ark_next_batch", i32, (vp, i64, i32, i32, vp, i64, vp, vp, i64, P(i32), P(i32))),
+    ("xv_ark_pending_shape", i32, (vp, P(i32), P(i32))),
+    ("xv_ark_skipped", i64, (vp,)),
+    ("xv_ark_set_copy_threads", i32, (vp, i32)),
+    ("xv_ark_error", cstr, (vp,)),
+    ("xv_ark_close", None, (vp,)),
+    ("xv_ark_format_vectors", i64, (vp, i32, vp, i32, i64, vp, i64)),
+    ("xv_pack_rows", i64, (vp, vp, i32, vp, i32)),
+    ("xv_crc32c", u32, (u32, vp, i64)),
+    # teardown and the error string
+    ("xv_destroy", None, (vp,)),
+    ("xv_last_error", cstr, (vp,)),
+)
+EXPORTS = [name for name, _, _ in SIGNATURES]
+
 _lib = None
+
+
+def declare(cdll):
+    """Give every entry point of SIGNATURES on the loaded handle `cdll` its return and argument types.  Raises, naming them,
+    if symbols are missing."""
+    missing = [n for n in EXPORTS if not hasattr(cdll, n)]
+    if missing:
+        raise RuntimeError("libxvec_hip.so lacks symbols: %s" % ", ".join(missing))
+    for name, restype, argtypes in SIGNATURES:
+        fn = getattr(cdll, name)
+        fn.restype = restype
+        fn.argtypes = list(argtypes)
+    return cdll
 
 
 def load():
     """Load libxvec_hip.so once and declare the signatures.  Raises on any problem."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise RuntimeError(
-            "HIP extension %s is missing: the x-vector path has no CPU fallback. "
-            "Build it with __graft_entry__.build() (hipcc --offload-arch=gfx950)." % LIB_PATH)
-    import torch  # noqa: F401  (loads torch's libamdhip64 first; see module docstring)
-    lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [n for n in EXPORTS if not hasattr(lib, n)]
-    if missing:
-        raise RuntimeError("libxvec_hip.so lacks symbols: %s" % ", ".join(missing))
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.xv_version.restype = C.c_char_p
-    lib.xv_version.argtypes = []
-    lib.xv_last_error.restype = C.c_char_p
-    lib.xv_last_error.argtypes = [vp]
-    lib.xv_create.argtypes = [C.POINTER(ModelDesc), i32, C.POINTER(vp)]
-    lib.xv_set_tensor.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
-    lib.xv_finalize.argtypes = [vp]
-    lib.xv_set_option.argtypes = [vp, C.c_char_p, i32]
-    lib.xv_check_overflow.argtypes = [vp, i32]
-    lib.xv_flags_async.argtypes = [vp, vp, vp]
-    lib.xv_flags_decode.argtypes = [vp]
-    lib.xv_node_id.argtypes = [vp, C.c_char_p]
-    lib.xv_node_context.argtypes = [vp, i32]
-    lib.xv_layer_two_unit.argtypes = [vp, C.c_char_p]
-    lib.xv_plan_create.argtypes = [vp, vp, i32, i32, vp, C.POINTER(vp)]
-    lib.xv_plan_query.argtypes = [vp, C.POINTER(PlanInfo)]
-    lib.xv_plan_destroy.argtypes = [vp]
-    lib.xv_plan_destroy.restype = None
-    lib.xv_forward.argtypes = [vp, vp, vp, i32, vp, i64, vp, i64, vp]
-    lib.xv_profile_begin.argtypes = [vp, i32]
-    lib.xv_profile_end.argtypes = [vp, C.POINTER(KernelTime), i32, C.POINTER(i32)]
-    lib.xv_destroy.argtypes = [vp]
-    lib.xv_destroy.restype = None
-    lib.xv_frontend_cmn_select.argtypes = [i32, vp, i32, i32, vp, i32, vp, i64, i32, i32, i32, vp, vp, vp]
-    lib.xv_mfcc_create.argtypes = [C.POINTER(MfccOpts), i32, C.POINTER(vp)]
-    lib.xv_mfcc_destroy.argtypes = [vp]
-    lib.xv_mfcc_destroy.restype = None
-    lib.xv_mfcc_num_frames.argtypes = [vp, i64]
-    lib.xv_mfcc_num_frames.restype = i64
-    lib.xv_mfcc_compute.argtypes = [vp, vp, vp, vp, i32, vp, i64, vp]
-    lib.xv_vad_energy.argtypes = [i32, vp, i64, vp, i32, C.c_float, C.c_float, i32, C.c_float, vp, vp]
-    lib.xv_fbank_create.argtypes = [C.POINTER(FbankOpts), i32, C.POINTER(vp)]
-    lib.xv_fbank_destroy.argtypes = [vp]
-    lib.xv_fbank_destroy.restype = None
-    lib.xv_fbank_num_frames.argtypes = [vp, i64]
-    lib.xv_fbank_num_frames.restype = i64
-    lib.xv_fbank_num_feats.argtypes = [vp]
-    lib.xv_fbank_compute.argtypes = [vp, vp, vp, vp, i32, vp, i64, vp, vp]
-    lib.xv_length_normalize.argtypes = [i32, vp, i64, i64, i32, i32, vp, i64, vp]
-    lib.xv_speaker_mean.argtypes = [i32, vp, i64, i32, vp, vp, i64, vp, i64, vp]
-    lib.xv_score_prepare.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, i32, i32, i32, C.c_float, vp, i64, vp]
-    lib.xv_score_matrix.argtypes = [i32, vp, i64, i64, vp, i64, i64, i32, vp, i64, vp]
-    lib.xv_score_pairs.argtypes = [i32, vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp]
-    lib.xv_score_histogram.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, vp]
-    lib.xv_plda_prepare.argtypes = [i32, vp, i64, i64, i32, vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp]
-    lib.xv_plda_matrix.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, i64, vp]
-    lib.xv_plda_pairs.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, i32, vp, vp, i64, vp, vp]
-    lib.xv_plda_histogram.argtypes = [i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, vp]
-    lib.xv_cohort_stats_workspace.argtypes = [i64, i64, i32]
-    lib.xv_cohort_stats_workspace.restype = i64
-    lib.xv_cohort_stats.argtypes = [i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp]
-    lib.xv_score_topk_workspace.argtypes = [i64, i64, i32]
-    lib.xv_score_topk_workspace.restype = i64
-    lib.xv_score_topk.argtypes = [i32, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, vp]
-    lib.xv_ahc_matrix_floats.argtypes = [i64]
-    lib.xv_ahc_matrix_floats.restype = i64
-    lib.xv_ahc_workspace.argtypes = [i64, vp]
-    lib.xv_ahc_workspace.restype = i64
-    lib.xv_ahc.argtypes = [i32, vp, vp, vp, i64, C.c_double, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.xv_plda_adapt_workspace.argtypes = [i64, i32]
-    lib.xv_plda_adapt_workspace.restype = i64
-    lib.xv_plda_adapt_slot_bytes.argtypes = [i32]
-    lib.xv_plda_adapt_slot_bytes.restype = i64
-    lib.xv_plda_adapt.argtypes = [i32, vp, i64, vp, i64, i32, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.xv_vbx_workspace.argtypes = [i64, vp, vp, i32]
-    lib.xv_vbx_workspace.restype = i64
-    lib.xv_vbx.argtypes = [i32, vp, i64, vp, vp, i64, i32, vp, vp, i32, vp, vp, C.c_double, C.c_double, C.c_double, i32, C.c_double,
-                           vp, vp, vp, vp, i64, vp]
-    lib.xv_loss_prepare_classes.argtypes =[i32, vp, i64, i32, i64, i32, vp, i64, vp]
-    lib.xv_loss_workspace.argtypes = [i64, i64]
-    lib.xv_loss_workspace.restype = i64
-    lib.xv_loss_classifier.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, i64, vp, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, i64, vp]
-    lib.xv_loss_grad_workspace.argtypes = [i64, i64, i32]
-    lib.xv_loss_grad_workspace.restype = i64
-    lib.xv_loss_grad_workspace_min.argtypes = [i64, i64, i32]
-    lib.xv_loss_grad_workspace_min.restype = i64
-    lib.xv_loss_classifier_grad.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, i64, vp, i32, C.c_double, C.c_double, C.c_double,
-                                            vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]
-    lib.xv_opt_workspace.argtypes = [i64]
-    lib.xv_opt_workspace.restype = i64
-    lib.xv_opt_step.argtypes = [i32, i32, i32, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i64, vp, i64, vp]
-    lib.xv_seg_workspace.argtypes = [i64, i32, i32]
-    lib.xv_seg_workspace.restype = i64
-    lib.xv_seg_workspace_min.argtypes = [i64, i32, i32]
-    lib.xv_seg_workspace_min.restype = i64
-    lib.xv_seg_forward.argtypes = [i32, vp, i64, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64, vp]
-    lib.xv_seg_backward.argtypes = [i32, vp, i64, vp, i64, vp, i64, i64, i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp,
-                                    vp, i64, vp]
-    lib.xv_stat_pool_forward.argtypes = [i32, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp]
-    lib.xv_stat_pool_backward.argtypes = [i32, vp, i64, vp, i64, i32, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp]
-    lib.xv_att_pool_workspace.argtypes = [i64, i64, i32, i32, i32, i32, i32]
-    lib.xv_att_pool_workspace.restype = i64
-    lib.xv_att_pool_workspace_min.argtypes = [i64, i64, i32, i32, i32, i32, i32]
-    lib.xv_att_pool_workspace_min.restype = i64
-    lib.xv_att_pool_forward.argtypes = [i32, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, C.c_float, vp, i64, i64, vp, i64, vp, i64,
-                                        vp, i64, vp]
-    lib.xv_att_pool_backward.argtypes = [i32, vp, i64, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, C.c_float, vp, i64, i64, vp, i64,
-                                         vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-    lib.xv_tconv_workspace.argtypes = [i64, i64, i64, i32, i32, i32]
-    lib.xv_tconv_workspace.restype = i64
-    lib.xv_tconv_workspace_min.argtypes = [i64, i64, i64, i32, i32, i32]
-    lib.xv_tconv_workspace_min.restype = i64
-    lib.xv_tconv_forward_workspace.argtypes = [i64, i64]
-    lib.xv_tconv_forward_workspace.restype = i64
-    lib.xv_tconv_forward.argtypes = [i32, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64,
-                                     vp, i64, vp]
-    lib.xv_tconv_backward.argtypes = [i32, vp, i64, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i32,
-                                      vp, i64, vp, vp, vp, vp, vp, i64, vp]
-    lib.xv_bn_batch_workspace.argtypes = [i64, i32]
-    lib.xv_bn_batch_workspace.restype = i64
-    lib.xv_bn_batch_workspace_min.argtypes = [i64, i32]
-    lib.xv_bn_batch_workspace_min.restype = i64
-    lib.xv_bn_batch_forward.argtypes = [i32, vp, i64, i64, i32, vp, vp, i32, C.c_double, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp]
-    lib.xv_bn_batch_backward.argtypes = [i32, vp, i64, vp, i64, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, i64, vp]
-    lib.xv_metric_loss_workspace.argtypes = [i64, vp, i32, i32]
-    lib.xv_metric_loss_workspace.restype = i64
-    lib.xv_metric_loss_slot_bytes.argtypes = [i32, i32, i32]
-    lib.xv_metric_loss_slot_bytes.restype = i64
-    lib.xv_metric_loss.argtypes = [i32, vp, i64, vp, i64, i32, vp, i32, i32, C.c_double, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.xv_gram_f64_workspace.argtypes = [i64, i32]
-    lib.xv_gram_f64_workspace.restype = i64
-    lib.xv_gram_f64.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
-    lib.xv_gram_f64_rows64.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
-    lib.xv_class_mean_f64.argtypes = [i32, vp, i64, i64, i32, vp, vp, i64, vp, vp, i64, vp]
-    lib.xv_logreg_workspace.argtypes = [i64, i32]
-    lib.xv_logreg_workspace.restype = i64
-    lib.xv_logreg_stats.argtypes = [i32, vp, i64, i64, i32, vp, vp, C.c_double, C.c_double, C.c_double, vp, i32, vp, vp, vp, i64, vp]
-    lib.xv_score_fuse.argtypes = [i32, vp, i64, i64, i32, vp, vp, vp]
-    lib.xv_reverb_tile.argtypes = [C.POINTER(i32), C.POINTER(i32)]
-    lib.xv_reverb_workspace.argtypes = [vp, i64, vp, i64, i64, i64, i64, i64]
-    lib.xv_reverb_workspace.restype = i64
-    lib.xv_reverb.argtypes = [i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    lib.xv_ark_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
-    lib.xv_ark_open_scp.argtypes = [C.c_char_p, C.POINTER(vp)]
-    lib.xv_ark_scp_count.argtypes = [vp]
-    lib.xv_ark_scp_count.restype = i64
-    lib.xv_ark_scp_shapes.argtypes = [vp, vp, vp, i64]
-    lib.xv_ark_next_batch.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, i64, C.POINTER(i32), C.POINTER(i32)]
-    lib.xv_ark_pending_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    lib.xv_ark_skipped.argtypes = [vp]
-    lib.xv_ark_set_copy_threads.argtypes = [vp, i32]
-    lib.xv_ark_skipped.restype = i64
-    lib.xv_ark_error.argtypes = [vp]
-    lib.xv_ark_error.restype = C.c_char_p
-    lib.xv_ark_close.argtypes = [vp]
-    lib.xv_ark_close.restype = None
-    lib.xv_ark_format_vectors.argtypes = [vp, i32, vp, i32, i64, vp, i64]
-    lib.xv_ark_format_vectors.restype = i64
-    lib.xv_crc32c.argtypes = [C.c_uint32, vp, i64]
-    lib.xv_pack_rows.argtypes = [vp, vp, i32, vp, i32]
-    lib.xv_pack_rows.restype = i64
-    lib.xv_crc32c.restype = C.c_uint32
-    for n in EXPORTS:
-        if n not in ("xv_version", "xv_last_error", "xv_plan_destroy", "xv_destroy", "xv_ark_skipped", "xv_ark_error",
-                     "xv_ark_close", "xv_ark_format_vectors", "xv_ark_scp_count", "xv_crc32c", "xv_pack_rows", "xv_gram_f64_workspace",
-                     "xv_loss_workspace", "xv_loss_grad_workspace", "xv_loss_grad_workspace_min", "xv_opt_workspace", "xv_seg_workspace", "xv_seg_workspace_min", "xv_bn_batch_workspace", "xv_bn_batch_workspace_min", "xv_metric_loss_workspace", "xv_metric_loss_slot_bytes", "xv_logreg_workspace", "xv_reverb_workspace", "xv_cohort_stats_workspace", "xv_score_topk_workspace", "xv_ahc_matrix_floats", "xv_ahc_workspace", "xv_plda_adapt_workspace", "xv_plda_adapt_slot_bytes", "xv_vbx_workspace", "xv_mfcc_destroy", "xv_mfcc_num_frames", "xv_fbank_destroy", "xv_fbank_num_frames"):
-            getattr(lib, n).restype = i32
-    _lib = lib
-    return lib
+    if _lib is None:
+        if not os.path.isfile(LIB_PATH):
+            raise RuntimeError(
+                "HIP extension %s is missing: the x-vector path has no CPU fallback. "
+                "Build it with __graft_entry__.build() (hipcc --offload-arch=gfx950)." % LIB_PATH)
+        import torch  # noqa: F401  (loads torch's libamdhip64 first; see module docstring)
+        _lib = declare(C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL))
+    return _lib
+
+
+def ptr(t):
+    """Device or host address of a tensor for a pointer argument; None stays None (NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """torch's current stream on `device`, as the hipStream_t the entry points take."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class XvError(RuntimeError):

@@ -29,6 +29,7 @@ import re
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import conv_train
 from . import frame_train
 from . import head_train
@@ -37,7 +38,6 @@ from . import tail_train
 
 StepResult = head_train.StepResult
 SegSpec = tail_train.SegSpec
-_p = tail_train._p
 
 
 def _dict(params):
@@ -185,9 +185,9 @@ class AttPool(object):
         self._covers = False
 
     def _call_args(self):
-        return (_p(self._key), self.key_dim, self.key_dim, _p(self._value), self.value_dim, self.value_dim, _p(self.q), self.dq,
-                self.heads, int(self.split_key), int(self.split_value), C.c_float(self.scale), _p(self._offsets), self._batch,
-                self._rows, _p(self._weights), self.heads, _p(self._pooled), self.out_dim, _p(self._var), self.out_dim // 2)
+        return (ptr(self._key), self.key_dim, self.key_dim, ptr(self._value), self.value_dim, self.value_dim, ptr(self.q), self.dq,
+                self.heads, int(self.split_key), int(self.split_value), C.c_float(self.scale), ptr(self._offsets), self._batch,
+                self._rows, ptr(self._weights), self.heads, ptr(self._pooled), self.out_dim, ptr(self._var), self.out_dim // 2)
 
     def forward(self, key_rows, value_rows, offsets):
         """key_rows [rows, Dk], value_rows [rows, Dv] on the device, float32 contiguous; offsets [B + 1] (host integers or an
@@ -212,8 +212,8 @@ class AttPool(object):
             self._weights = torch.empty((max(rows, 1), self.heads), dtype=torch.float32, device=key_rows.device)
             self._pooled = torch.empty((max(batch, 1), self.out_dim), dtype=torch.float32, device=key_rows.device)
             self._var = torch.empty((max(batch, 1), self.out_dim // 2), dtype=torch.float32, device=key_rows.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.xv_att_pool_forward(self.device, *self._call_args(), C.c_void_p(stream)))
+            stream = _lib.stream(self.device)
+            _lib.check(self._lib.xv_att_pool_forward(self.device, *self._call_args(), stream))
         return self._pooled[:batch]
 
     def weights(self):
@@ -242,11 +242,11 @@ class AttPool(object):
                 _lib.check(need)
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = _lib.stream(self.device)
             args = self._call_args()
-            _lib.check(self._lib.xv_att_pool_backward(self.device, _p(g_pooled), self.out_dim, *args, _p(gkey), self.key_dim,
-                                                      _p(gvalue), self.value_dim, _p(self.gq), self.dq, _p(self._ws),
-                                                      self._ws.numel(), C.c_void_p(stream)))
+            _lib.check(self._lib.xv_att_pool_backward(self.device, ptr(g_pooled), self.out_dim, *args, ptr(gkey), self.key_dim,
+                                                      ptr(gvalue), self.value_dim, ptr(self.gq), self.dq, ptr(self._ws),
+                                                      self._ws.numel(), stream))
         return gkey, gvalue
 
     def query(self):

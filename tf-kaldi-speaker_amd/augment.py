@@ -19,6 +19,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from .mfcc import _to_bool, read_wav
 
 log = logging.getLogger("xvec.augment")
@@ -317,13 +318,11 @@ def reverberate_packed(wave_dev, utts, rir_dev=None, noise_dev=None, want_i16=Tr
             raise ValueError("an output must be a contiguous 1-D tensor of %d samples" % total)
     B = len(utts)
     meta = torch.empty((3, B), dtype=torch.int32, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)      # noqa: E731
-    stream = torch.cuda.current_stream(dev.index).cuda_stream
-    _lib.check(lib.xv_reverb(dev.index, ptr(wave_dev), sizes[0], ptr(rir_dev), sizes[1], ptr(noise_dev), sizes[2], ut, B, nt, nn,
-                             C.c_void_p(out_i16.data_ptr()) if out_i16 is not None else C.c_void_p(0),
-                             C.c_void_p(out_f32.data_ptr()) if out_f32 is not None else C.c_void_p(0), total,
-                             C.c_void_p(meta[0].data_ptr()), C.c_void_p(meta[1].data_ptr()), C.c_void_p(meta[2].data_ptr()),
-                             C.c_void_p(workspace.data_ptr()), int(workspace.numel()), C.c_void_p(stream)))
+    src = lambda t: ptr(t) if t is not None and t.numel() > 0 else None      # noqa: E731
+    stream = _lib.stream(dev.index)
+    _lib.check(lib.xv_reverb(dev.index, src(wave_dev), sizes[0], src(rir_dev), sizes[1], src(noise_dev), sizes[2], ut, B, nt, nn,
+                             ptr(out_i16), ptr(out_f32), total, ptr(meta[0]), ptr(meta[1]), ptr(meta[2]),
+                             ptr(workspace), int(workspace.numel()), stream))
     host = meta.cpu().numpy()
     r = Result()
     r.out_i16, r.out_f32, r.offsets = out_i16, out_f32, offsets

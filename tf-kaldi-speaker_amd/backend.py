@@ -13,11 +13,11 @@ that takes a `Stats` is numpy float64 on the host and runs without one.
 Kaldi is absent from the reference tree: ivector-compute-lda.cc and the PldaStats / PldaEstimator of plda.cc are restated from
 the published sources (**parity unpinned**), checked against tests/helpers/ref_backend.py, a transcription of the Kaldi loops
 that accumulates speaker by speaker and runs the EM class by class.  `ivector-adapt-plda` (sre only) stays with Kaldi."""
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import plda as plda_mod
 from . import scoring
 
@@ -104,10 +104,10 @@ def _gram(lib, torch, device, rows, n, d, center, weights, rows64=False):
     need = _lib.check(lib.xv_gram_f64_workspace(n, d))
     ws = torch.empty((max(need, 8) // 8,), dtype=torch.float64, device=rows.device)
     g = torch.empty((d, d), dtype=torch.float64, device=rows.device)
-    stream = torch.cuda.current_stream(device).cuda_stream
+    stream = _lib.stream(device)
     fn = lib.xv_gram_f64_rows64 if rows64 else lib.xv_gram_f64
-    _lib.check(fn(device, scoring._p(rows), rows.shape[1], n, d, None if center is None else scoring._p(center),
-                  None if weights is None else scoring._p(weights), scoring._p(g), scoring._p(ws), need, C.c_void_p(stream)))
+    _lib.check(fn(device, ptr(rows), rows.shape[1], n, d, ptr(center),
+                  ptr(weights), ptr(g), ptr(ws), need, stream))
     return g
 
 
@@ -136,9 +136,9 @@ def scatter_stats(x, class_index, center=None, device=0):
         idxd = torch.from_numpy(idx.astype(np.int32)).to(dev)
         s = counts.shape[0]
         md = torch.empty((s, d), dtype=torch.float64, device=dev)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_class_mean_f64(device, scoring._p(xd), d, n, d, scoring._p(offd), scoring._p(idxd), s, None,
-                                         scoring._p(md), d, C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_class_mean_f64(device, ptr(xd), d, n, d, ptr(offd), ptr(idxd), s, None,
+                                         ptr(md), d, stream))
         means = md.cpu().numpy()
         mean = counts @ means / counts.sum()
         c = mean if center is None else center

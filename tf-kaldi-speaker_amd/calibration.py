@@ -21,7 +21,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .scoring import _need_device, _p
+from ._lib import ptr
+from .scoring import _need_device
 
 MAX_SYSTEMS = _lib.XV_LOGREG_MAX_SYSTEMS
 MAX_THRESHOLDS = _lib.XV_LOGREG_MAX_THRESHOLDS
@@ -146,10 +147,10 @@ def _stats_dev(sd, n, k, lds, td, theta, tau, c_tar, c_non, thresholds, device):
             _ws[device] = ws = torch.empty((max(need, 1 << 16),), dtype=torch.uint8, device=sd.device)
         out = torch.empty((nd,), dtype=torch.float64, device=sd.device)
         cnt = torch.empty((3 + 2 * MAX_THRESHOLDS,), dtype=torch.int64, device=sd.device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_logreg_stats(device, _p(sd), lds, n, k, _p(td), C.c_void_p(theta.ctypes.data), float(tau), float(c_tar),
-                                       float(c_non), C.c_void_p(thr.ctypes.data) if thr.size else None, thr.size, _p(out),
-                                       _p(cnt), _p(ws), ws.numel(), C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_logreg_stats(device, ptr(sd), lds, n, k, ptr(td), C.c_void_p(theta.ctypes.data), float(tau), float(c_tar),
+                                       float(c_non), C.c_void_p(thr.ctypes.data) if thr.size else None, thr.size, ptr(out),
+                                       ptr(cnt), ptr(ws), ws.numel(), stream))
         o, c = out.cpu().numpy(), cnt.cpu().numpy()
     H = np.zeros((k + 1, k + 1))
     H[np.triu_indices(k + 1)] = o[k + 2:]
@@ -256,8 +257,8 @@ def apply(model, scores, device=0, as_tensor=False):
     theta = np.ascontiguousarray(model.theta)
     with torch.cuda.device(device):
         out = torch.empty((n,), dtype=torch.float32, device=sd.device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_score_fuse(device, _p(sd), lds, n, k, C.c_void_p(theta.ctypes.data), _p(out), C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_score_fuse(device, ptr(sd), lds, n, k, C.c_void_p(theta.ctypes.data), ptr(out), stream))
         return out if as_tensor else out.cpu().numpy()
 
 

@@ -28,8 +28,8 @@ import sys
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import scoring
-from .scoring import _p
 
 Clustering = collections.namedtuple("Clustering", ["labels", "num_clusters", "merge_a", "merge_b", "merge_height"])
 
@@ -97,7 +97,7 @@ def _run(sizes, fill, threshold, targets, device, budget=None):
     out = [None] * len(sizes)
     with torch.cuda.device(device):
         dev = torch.device("cuda:%d" % device)
-        stream = torch.cuda.current_stream(device).cuda_stream
+        stream = _lib.stream(device)
         for run in _chunks(sizes, MATRIX_BUDGET_BYTES if budget is None else budget):
             rows = np.ascontiguousarray([sizes[g] for g in run], dtype=np.int32)
             tg = None if targets is None else np.ascontiguousarray(targets[run], dtype=np.int32)
@@ -117,9 +117,9 @@ def _run(sizes, fill, threshold, targets, device, budget=None):
             if need < 0:
                 raise _lib.XvError(need, "xv_ahc_workspace: bad group sizes")
             ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.xv_ahc(device, _p(s), rows.ctypes.data_as(C.c_void_p), None if tg is None else tg.ctypes.data_as(C.c_void_p),
-                                  len(run), threshold, _p(labels), _p(count), _p(merge_a), _p(merge_b), _p(height), _p(ws), ws.numel(),
-                                  C.c_void_p(stream)))
+            _lib.check(lib.xv_ahc(device, ptr(s), rows.ctypes.data_as(C.c_void_p), None if tg is None else tg.ctypes.data_as(C.c_void_p),
+                                  len(run), threshold, ptr(labels), ptr(count), ptr(merge_a), ptr(merge_b), ptr(height), ptr(ws), ws.numel(),
+                                  stream))
             labels, merge_a, merge_b, height, count = (t.cpu().numpy() for t in (labels, merge_a, merge_b, height, count))
             off = 0
             for i, (g, n) in enumerate(zip(run, rows.tolist())):
@@ -188,9 +188,9 @@ def cosine(x, groups, threshold=None, num_clusters=None, mean=None, transform=No
 
     def fill(members, view):
         a = rows[torch.from_numpy(members).to(rows.device)].contiguous()
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_score_matrix(device, _p(a), d, len(members), _p(a), d, len(members), d, _p(view), view.shape[1],
-                                       C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_score_matrix(device, ptr(a), d, len(members), ptr(a), d, len(members), d, ptr(view), view.shape[1],
+                                       stream))
 
     return _by_group(n, groups, fill, threshold, num_clusters, device)
 
@@ -213,9 +213,9 @@ def _plda_fill(model, x, names, members, mean, transform, normalize, normalize_l
         return whole[0]
 
     def matrix(a, rho, b, tau, k, count, view):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_plda_matrix(device, _p(a), a.shape[1], count, _p(rho), _p(b), b.shape[1], count, _p(tau), k,
-                                      _p(view), view.shape[1], C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_plda_matrix(device, ptr(a), a.shape[1], count, ptr(rho), ptr(b), b.shape[1], count, ptr(tau), k,
+                                      ptr(view), view.shape[1], stream))
 
     def fill_global(g, view):
         enroll, test, k, tau = global_operands()

@@ -23,11 +23,11 @@ the head keeps the rule of head_train.optimizer_config, the clip is per tensor, 
 frame_variables, trained_names, l2_assignment, check_supported, out_offsets, kernel_to_rows and rows_to_kernel are pure host
 code; the rest needs a HIP device."""
 import collections
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import frame_train
 from . import head_train
 from . import tail_train
@@ -37,7 +37,6 @@ ConvSpec = collections.namedtuple("ConvSpec", "kernel bias bn act taps")      # 
 
 # network_type -> (variable scope, the kernel widths of the frame-level layers in forward order)
 _NETS = {"tdnn": ("tdnn", (5, 5, 7, 1, 1)), "extended_tdnn": ("etdnn", (5, 1, 5, 1, 7, 1, 9, 1, 1, 1))}
-_p = tail_train._p
 
 
 def _dict(params):
@@ -140,12 +139,12 @@ class TConvLayer(tail_train.Layer):
             if total_out:
                 ws = self._workspace(int(self._lib.xv_tconv_forward_workspace(batch, total_out)), x.device)
                 bn = [None] * 4 if stats else self.bn or [None] * 4
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                _lib.check(self._lib.xv_tconv_forward(self.device, _p(x), self.channels, self.channels, self.taps, _p(off), batch,
-                                                      total_in, total_out, _p(self.w), self.ldw, self.out_dim, _p(self.b), _p(bn[0]),
-                                                      _p(bn[1]), _p(bn[2]), _p(bn[3]), _lib.XV_SEG_ACT_NONE if stats else self.act,
-                                                      _p(z), self.out_dim, _p(y), self.out_dim, _p(ws), ws.numel(),
-                                                      C.c_void_p(stream)))
+                stream = _lib.stream(self.device)
+                _lib.check(self._lib.xv_tconv_forward(self.device, ptr(x), self.channels, self.channels, self.taps, ptr(off), batch,
+                                                      total_in, total_out, ptr(self.w), self.ldw, self.out_dim, ptr(self.b), ptr(bn[0]),
+                                                      ptr(bn[1]), ptr(bn[2]), ptr(bn[3]), _lib.XV_SEG_ACT_NONE if stats else self.act,
+                                                      ptr(z), self.out_dim, ptr(y), self.out_dim, ptr(ws), ws.numel(),
+                                                      stream))
                 if stats:
                     y = self._bn_forward(z, total_out, stream)
         self._x, self._z, self._off, self._sizes = x, z, off, (batch, total_in, total_out)
@@ -172,20 +171,20 @@ class TConvLayer(tail_train.Layer):
             ws = self._workspace(int(self._lib.xv_tconv_workspace(batch, total_in, total_out, self.taps, self.channels, self.out_dim)),
                                  x.device)
             bn = self.bn or [None] * 4
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = _lib.stream(self.device)
             if self._batch:                  # through the statistics first; the operator then passes gz through its mask
                 gz = self._bn_backward(gy, z, total_out, stream)
-                _lib.check(self._lib.xv_tconv_backward(self.device, _p(gz), self.out_dim, _p(x), self.channels, self.channels,
-                                                       self.taps, _p(self._off), batch, total_in, total_out, _p(z), self.out_dim,
-                                                       _p(self.w), self.ldw, self.out_dim, None, None, None, None,
-                                                       _lib.XV_SEG_ACT_NONE, _p(gx), self.channels, _p(self.gw), _p(self.gb), None,
-                                                       None, _p(ws), ws.numel(), C.c_void_p(stream)))
+                _lib.check(self._lib.xv_tconv_backward(self.device, ptr(gz), self.out_dim, ptr(x), self.channels, self.channels,
+                                                       self.taps, ptr(self._off), batch, total_in, total_out, ptr(z), self.out_dim,
+                                                       ptr(self.w), self.ldw, self.out_dim, None, None, None, None,
+                                                       _lib.XV_SEG_ACT_NONE, ptr(gx), self.channels, ptr(self.gw), ptr(self.gb), None,
+                                                       None, ptr(ws), ws.numel(), stream))
                 return gx
-            _lib.check(self._lib.xv_tconv_backward(self.device, _p(gy), self.out_dim, _p(x), self.channels, self.channels, self.taps,
-                                                   _p(self._off), batch, total_in, total_out, _p(z), self.out_dim, _p(self.w), self.ldw,
-                                                   self.out_dim, _p(bn[0]), _p(bn[1]), _p(bn[2]), _p(bn[3]), self.act, _p(gx),
-                                                   self.channels, _p(self.gw), _p(self.gb), _p(self.ggamma), _p(self.gbeta), _p(ws),
-                                                   ws.numel(), C.c_void_p(stream)))
+            _lib.check(self._lib.xv_tconv_backward(self.device, ptr(gy), self.out_dim, ptr(x), self.channels, self.channels, self.taps,
+                                                   ptr(self._off), batch, total_in, total_out, ptr(z), self.out_dim, ptr(self.w), self.ldw,
+                                                   self.out_dim, ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]), self.act, ptr(gx),
+                                                   self.channels, ptr(self.gw), ptr(self.gb), ptr(self.ggamma), ptr(self.gbeta), ptr(ws),
+                                                   ws.numel(), stream))
         return gx
 
     def kernel(self):

@@ -6,6 +6,7 @@ hands out the per-frame log energy, which a file made with --use-energy=false do
 import ctypes as C
 
 from . import _lib
+from ._lib import ptr
 from .mfcc import FRAME_FIELDS, FrameOptions, packed_offsets
 
 
@@ -77,10 +78,10 @@ class Fbank(object):
         if total > 0:
             soff_dev = torch.from_numpy(sample_offsets).to(dev)
             foff_dev = torch.from_numpy(frame_offsets).to(dev)
-            stream = torch.cuda.current_stream(dev.index).cuda_stream
-            _lib.check(self._lib.xv_fbank_compute(self._h, C.c_void_p(wave_dev.data_ptr()), C.c_void_p(soff_dev.data_ptr()),
-                                                  C.c_void_p(foff_dev.data_ptr()), B, C.c_void_p(out.data_ptr()), ld,
-                                                  C.c_void_p(log_e.data_ptr()) if energy else None, C.c_void_p(stream)))
+            stream = _lib.stream(dev.index)
+            _lib.check(self._lib.xv_fbank_compute(self._h, ptr(wave_dev), ptr(soff_dev),
+                                                  ptr(foff_dev), B, ptr(out), ld,
+                                                  ptr(log_e) if energy else None, stream))
         return (out, frame_offsets, log_e) if energy else (out, frame_offsets)
 
 

@@ -26,11 +26,11 @@ frame_variables, frozen_node, trained_names, l2_assignment and check_supported a
 StackedTrainer is "frame layers -> StatPool -> TailTrainer" for any kind of frame layer: it builds and checks the chain, and its
 step is tail_train.TailTrainer._step.  FrameTrainer here and conv_train.ConvTrainer say only what their frame layers are;
 stacked_names and stacked_l2 give both modules their trained_names and l2_assignment."""
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import head_train
 from . import losses
 from . import tail_train
@@ -104,7 +104,6 @@ def l2_assignment(params):
     return stacked_l2(frame_variables(params), params)
 
 
-_p = tail_train._p
 
 
 class StatPool(object):
@@ -139,9 +138,9 @@ class StatPool(object):
             batch = int(off.numel()) - 1
             pooled = torch.empty((max(batch, 1), 2 * c), dtype=torch.float32, device=x_dev.device)
             var = torch.empty((max(batch, 1), c), dtype=torch.float32, device=x_dev.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.xv_stat_pool_forward(self.device, _p(x_dev), c, c, _p(off), batch, rows, _p(pooled), 2 * c, _p(var), c,
-                                                      C.c_void_p(stream)))
+            stream = _lib.stream(self.device)
+            _lib.check(self._lib.xv_stat_pool_forward(self.device, ptr(x_dev), c, c, ptr(off), batch, rows, ptr(pooled), 2 * c, ptr(var), c,
+                                                      stream))
         self._x, self._offsets, self._pooled, self._var, self._batch, self._rows = x_dev, off, pooled, var, batch, rows
         self._covers = covers
         return pooled[:batch]
@@ -157,10 +156,10 @@ class StatPool(object):
         with torch.cuda.device(self.device):
             make = torch.empty if self._covers else torch.zeros           # every row has an owner: every element is written
             gx = make((self._rows, c), dtype=torch.float32, device=self._x.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.xv_stat_pool_backward(self.device, _p(g_pooled), 2 * c, _p(self._x), c, c, _p(self._offsets), self._batch,
-                                                       self._rows, _p(self._pooled), 2 * c, _p(self._var), c, _p(gx), c,
-                                                       C.c_void_p(stream)))
+            stream = _lib.stream(self.device)
+            _lib.check(self._lib.xv_stat_pool_backward(self.device, ptr(g_pooled), 2 * c, ptr(self._x), c, c, ptr(self._offsets), self._batch,
+                                                       self._rows, ptr(self._pooled), 2 * c, ptr(self._var), c, ptr(gx), c,
+                                                       stream))
         return gx
 
 

@@ -1,11 +1,11 @@
 """GPU feature front-end: sliding-window CMN + voiced-frame selection on a packed batch (csrc/frontend.hip),
 the counterpart of the Kaldi pipe `apply-cmvn-sliding --norm-vars=false --center=true --cmn-window=300 |
 select-voiced-frames` of egs/voxceleb/v1/nnet/run_extract_embeddings.sh:47."""
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 
 
 def cmn_select_packed(feats_dev, offsets, vads, cmn_window=300, center=True, min_window=100, dim=None, device_index=None,
@@ -49,10 +49,10 @@ def cmn_select_packed(feats_dev, offsets, vads, cmn_window=300, center=True, min
     out = torch.empty((int(src.shape[0]), dim), dtype=torch.float32, device=dev)
     if src.shape[0] == 0:
         return out, new_off, kept
-    stream = torch.cuda.current_stream(idx).cuda_stream
-    rc = lib.xv_frontend_cmn_select(idx, C.c_void_p(feats_dev.data_ptr()), int(feats_dev.shape[1]), dim,
-                                    C.c_void_p(off_dev.data_ptr()), B, C.c_void_p(src_dev.data_ptr()), int(src.shape[0]),
+    stream = _lib.stream(idx)
+    rc = lib.xv_frontend_cmn_select(idx, ptr(feats_dev), int(feats_dev.shape[1]), dim,
+                                    ptr(off_dev), B, ptr(src_dev), int(src.shape[0]),
                                     int(cmn_window), int(bool(center)), int(min_window),
-                                    C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+                                    ptr(scratch), ptr(out), stream)
     _lib.check(rc)
     return out, new_off, kept

@@ -13,12 +13,12 @@ plan_train_batches stands in for KaldiDataRandomQueue (dataset/data_loader.py:28
 unpinned**, like valid.plan_end2end_batches.  No CPU path: HeadTrainer needs a HIP device; plan_train_batches, xavier_uniform
 and LearningRateRule are pure host code."""
 import collections
-import ctypes as C
 import os
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import losses
 from . import model_io
 
@@ -88,11 +88,10 @@ class HeadTrainer(object):
         self.num_steps = 0                                                   # adam's t
 
     def _apply(self, w, g, slots, lr, l2):
-        p = lambda t: C.c_void_p(t.data_ptr())                              # noqa: E731
-        stream = self._torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.xv_opt_step(self.device, self.kind, int(self.nesterov), p(w), p(g), p(slots[0]) if slots else None,
-                                         p(slots[1]) if len(slots) > 1 else None, w.numel(), float(lr), l2, self.clip_norm,
-                                         self.momentum, self.num_steps, p(self._ws), self._ws.numel(), C.c_void_p(stream)))
+        stream = _lib.stream(self.device)
+        _lib.check(self._lib.xv_opt_step(self.device, self.kind, int(self.nesterov), ptr(w), ptr(g), ptr(slots[0]) if slots else None,
+                                         ptr(slots[1]) if len(slots) > 1 else None, w.numel(), float(lr), l2, self.clip_norm,
+                                         self.momentum, self.num_steps, ptr(self._ws), self._ws.numel(), stream))
 
     def step(self, x, labels, learning_rate, global_step=0):
         """One training step on a batch of embeddings x [n, E]: the mean loss of the head at `global_step` (its margin annealing),

@@ -12,11 +12,11 @@ like scoring.py.  No CPU path: without a HIP device classifier_loss and Classifi
 valid_params are pure host code."""
 import collections
 import copy
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 
 SOFTMAX_KERNEL = "softmax/output/kernel"      # [E, num_speakers] (loss.py:30-34, 129)
 SOFTMAX_BIAS = "softmax/output/bias"          # [num_speakers], the plain softmax only (tf.layers.dense)
@@ -85,10 +85,6 @@ def head_config(params, global_step=0, validation=False):
     return func, _HEADS[func], float(margin), fa
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def _need_device():
     import torch
     if not torch.cuda.is_available():
@@ -137,9 +133,9 @@ class ClassifierHead(object):
         with torch.cuda.device(self.device):
             kd = _f32(kernel, self.device, torch)
             self.classes = torch.zeros((self.num_classes, self._ldc), dtype=torch.float32, device=kd.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(lib.xv_loss_prepare_classes(self.device, _p(kd), self.num_classes, self.embed_dim, self.num_classes,
-                                                   int(func != "softmax"), _p(self.classes), self._ldc, C.c_void_p(stream)))
+            stream = _lib.stream(self.device)
+            _lib.check(lib.xv_loss_prepare_classes(self.device, ptr(kd), self.num_classes, self.embed_dim, self.num_classes,
+                                                   int(func != "softmax"), ptr(self.classes), self._ldc, stream))
             self.bias = None if bias is None else _f32(bias, self.device, torch)
         self._ws = None
         self._gws = None
@@ -161,9 +157,9 @@ class ClassifierHead(object):
                 with torch.cuda.device(self.device):
                     kd = _f32(self._kernel_src, self.device, torch)
                     rows = torch.zeros((self.num_classes, self._ldc), dtype=torch.float32, device=kd.device)
-                    stream = torch.cuda.current_stream(self.device).cuda_stream
-                    _lib.check(lib.xv_loss_prepare_classes(self.device, _p(kd), self.num_classes, self.embed_dim, self.num_classes, 0,
-                                                           _p(rows), self._ldc, C.c_void_p(stream)))
+                    stream = _lib.stream(self.device)
+                    _lib.check(lib.xv_loss_prepare_classes(self.device, ptr(kd), self.num_classes, self.embed_dim, self.num_classes, 0,
+                                                           ptr(rows), self._ldc, stream))
                     torch.cuda.current_stream(self.device).synchronize()      # kd may be a temporary
                 self._raw_rows, self._kernel_src = rows, None
         return self._raw_rows
@@ -190,11 +186,11 @@ class ClassifierHead(object):
             need = int(lib.xv_loss_workspace(n, self.num_classes))
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=xd.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(lib.xv_loss_classifier(self.device, _p(xd), self.embed_dim, n, self.embed_dim, _p(ld), _p(self.classes),
-                                              self._ldc, self.num_classes, None if self.bias is None else _p(self.bias), head,
-                                              margin, fa, _p(out[0]), _p(out[1]), _p(out[2]), _p(top1), _p(self._ws),
-                                              self._ws.numel(), C.c_void_p(stream)))
+            stream = _lib.stream(self.device)
+            _lib.check(lib.xv_loss_classifier(self.device, ptr(xd), self.embed_dim, n, self.embed_dim, ptr(ld), ptr(self.classes),
+                                              self._ldc, self.num_classes, ptr(self.bias), head,
+                                              margin, fa, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(top1), ptr(self._ws),
+                                              self._ws.numel(), stream))
             loss, target, lse, top1 = out[0, :n], out[1, :n], out[2, :n], top1[:n]
             if as_tensor:
                 return LossResult(loss, target, lse, top1, float(loss.double().mean()) if n else float("nan"))
@@ -229,14 +225,14 @@ class ClassifierHead(object):
             need = int(lib.xv_loss_grad_workspace(n, self.num_classes, self.embed_dim))
             if self._gws is None or self._gws.numel() < need:
                 self._gws = torch.empty(need, dtype=torch.uint8, device=xd.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = _lib.stream(self.device)
             scale = 1.0 / n if grad_scale is None else float(grad_scale)
-            _lib.check(lib.xv_loss_classifier_grad(self.device, _p(xd), self.embed_dim, n, self.embed_dim, _p(ld), _p(self.raw_rows),
-                                                   self._ldc, self.num_classes, None if self.bias is None else _p(self.bias), head,
-                                                   margin, fa, scale, _p(out[0]), _p(out[1]), _p(out[2]), _p(top1),
-                                                   None if gx is None else _p(gx), self.embed_dim, _p(grad_rows),
-                                                   None if grad_bias is None else _p(grad_bias), _p(self._gws), self._gws.numel(),
-                                                   C.c_void_p(stream)))
+            _lib.check(lib.xv_loss_classifier_grad(self.device, ptr(xd), self.embed_dim, n, self.embed_dim, ptr(ld), ptr(self.raw_rows),
+                                                   self._ldc, self.num_classes, ptr(self.bias), head,
+                                                   margin, fa, scale, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(top1),
+                                                   ptr(gx), self.embed_dim, ptr(grad_rows),
+                                                   ptr(grad_bias), ptr(self._gws), self._gws.numel(),
+                                                   stream))
         return out[:, :n], top1[:n], None if gx is None else gx[:n], grad_rows, grad_bias
 
     def loss_and_grad(self, x, labels, global_step=0, grad_scale=None, need_grad_x=True, as_tensor=False):

@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .losses import _HEADS, _dict, _f32, _p
+from ._lib import ptr
+from .losses import _HEADS, _dict, _f32
 
 MAX_GROUP_ROWS = 4096
 MAX_SLOTS = 512           # groups (or panels of groups over 1024 rows) in flight; the result does not depend on it
@@ -77,11 +78,11 @@ def _run(x, labels, offsets, kind, pos_head=0, margin=0.0, squared=False, normal
         top1 = torch.empty(n, dtype=torch.int32, device=xd.device) if ge2e else None
         gloss = torch.empty(groups, dtype=torch.float64, device=xd.device)
         gcount = torch.empty((groups, 2), dtype=torch.int64, device=xd.device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_metric_loss(device, _p(xd), int(xd.shape[1]), off.ctypes.data_as(C.c_void_p), groups, d, _p(ld), kind,
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_metric_loss(device, ptr(xd), int(xd.shape[1]), off.ctypes.data_as(C.c_void_p), groups, d, ptr(ld), kind,
                                       int(pos_head), float(margin), int(bool(squared)), int(bool(normalize)), float(w), float(b),
-                                      _p(rows), _p(counts), None if top1 is None else _p(top1), _p(gloss), _p(gcount), _p(ws),
-                                      ws.numel(), C.c_void_p(stream)))
+                                      ptr(rows), ptr(counts), ptr(top1), ptr(gloss), ptr(gcount), ptr(ws),
+                                      ws.numel(), stream))
         gl = gloss.cpu().numpy()
         loss = float(np.mean(gl))
         if as_tensor:

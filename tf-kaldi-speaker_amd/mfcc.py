@@ -10,6 +10,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 
 WINDOW_TYPES = ("povey", "hamming", "hanning", "rectangular")
 
@@ -301,10 +302,10 @@ class Mfcc(object):
             return out, frame_offsets
         soff_dev = torch.from_numpy(sample_offsets).to(dev)
         foff_dev = torch.from_numpy(frame_offsets).to(dev)
-        stream = torch.cuda.current_stream(dev.index).cuda_stream
-        _lib.check(self._lib.xv_mfcc_compute(self._h, C.c_void_p(wave_dev.data_ptr()), C.c_void_p(soff_dev.data_ptr()),
-                                             C.c_void_p(foff_dev.data_ptr()), B, C.c_void_p(out.data_ptr()), ld,
-                                             C.c_void_p(stream)))
+        stream = _lib.stream(dev.index)
+        _lib.check(self._lib.xv_mfcc_compute(self._h, ptr(wave_dev), ptr(soff_dev),
+                                             ptr(foff_dev), B, ptr(out), ld,
+                                             stream))
         return out, frame_offsets
 
 
@@ -340,10 +341,10 @@ def vad_packed(feats_dev, frame_offsets, vopts=None):
     if feats_dev.shape[0] == 0:
         return vad
     foff_dev = torch.from_numpy(frame_offsets).to(dev)
-    stream = torch.cuda.current_stream(dev.index).cuda_stream
-    _lib.check(lib.xv_vad_energy(dev.index, C.c_void_p(feats_dev.data_ptr()), int(feats_dev.shape[1]), C.c_void_p(foff_dev.data_ptr()),
+    stream = _lib.stream(dev.index)
+    _lib.check(lib.xv_vad_energy(dev.index, ptr(feats_dev), int(feats_dev.shape[1]), ptr(foff_dev),
                                  B, vopts.vad_energy_threshold, vopts.vad_energy_mean_scale, vopts.vad_frames_context,
-                                 vopts.vad_proportion_threshold, C.c_void_p(vad.data_ptr()), C.c_void_p(stream)))
+                                 vopts.vad_proportion_threshold, ptr(vad), stream))
     return vad
 
 

@@ -27,6 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import kaldi_io
 from . import scoring
 
@@ -265,10 +266,10 @@ class PldaRows(object):
                 tabd = torch.from_numpy(tab).to(self.rows.device)
                 out = torch.empty((len(self),), dtype=torch.float32, device=self.rows.device)
                 if len(self):
-                    stream = torch.cuda.current_stream(self.device).cuda_stream
-                    _lib.check(_lib.load().xv_plda_prepare(self.device, scoring._p(self.rows), d, len(self), d, None, 0, d, _NORM_NONE, 1, 0,
-                                                           scoring._p(tabd), None, 1, None, None, 0, None, 0, scoring._p(out),
-                                                           C.c_void_p(stream)))
+                    stream = _lib.stream(self.device)
+                    _lib.check(_lib.load().xv_plda_prepare(self.device, ptr(self.rows), d, len(self), d, None, 0, d, _NORM_NONE, 1, 0,
+                                                           ptr(tabd), None, 1, None, None, 0, None, 0, ptr(out),
+                                                           stream))
             self._tau[n] = out
         return self._tau[n]
 
@@ -315,12 +316,12 @@ def _prepare(model, x, side, num_utts, normalize_length, simple_length_norm, dev
         packed = torch.zeros((n, ldp), dtype=torch.float32, device=xd.device)
         bias = torch.empty((n,), dtype=torch.float32, device=xd.device) if side == "enroll" else None
         if n:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.xv_plda_prepare(device, scoring._p(xd), d_in, n, d_in, scoring._p(aff), d_in + 1, d,
+            stream = _lib.stream(device)
+            _lib.check(lib.xv_plda_prepare(device, ptr(xd), d_in, n, d_in, ptr(aff), d_in + 1, d,
                                            _norm_mode(normalize_length, simple_length_norm), 0 if side == "enroll" else 1,
-                                           int(mixed), scoring._p(tabd), None if logd is None else scoring._p(logd), tab.shape[0],
-                                           None if idx is None else scoring._p(idx), scoring._p(rows), d, scoring._p(packed), ldp,
-                                           None if bias is None else scoring._p(bias), C.c_void_p(stream)))
+                                           int(mixed), ptr(tabd), ptr(logd), tab.shape[0],
+                                           ptr(idx), ptr(rows), d, ptr(packed), ldp,
+                                           ptr(bias), stream))
     return PldaRows(model, side, device, rows, packed, bias, counts)
 
 
@@ -365,10 +366,10 @@ def llr_matrix(enroll, test, as_tensor=False):
     n, m, dev = len(enroll), len(test), enroll.device
     with torch.cuda.device(dev):
         out = torch.empty((n, m), dtype=torch.float32, device=enroll.rows.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.xv_plda_matrix(dev, scoring._p(enroll.packed), enroll.packed.shape[1], n, scoring._p(enroll.bias),
-                                      scoring._p(test.packed), test.packed.shape[1], m, None if tau is None else scoring._p(tau), k,
-                                      scoring._p(out), max(m, 1), C.c_void_p(stream)))
+        stream = _lib.stream(dev)
+        _lib.check(lib.xv_plda_matrix(dev, ptr(enroll.packed), enroll.packed.shape[1], n, ptr(enroll.bias),
+                                      ptr(test.packed), test.packed.shape[1], m, ptr(tau), k,
+                                      ptr(out), max(m, 1), stream))
         return out if as_tensor else out.cpu().numpy()
 
 
@@ -411,10 +412,10 @@ def llr_pairs(enroll, test, ia, ib, as_tensor=False):
         iad = torch.from_numpy(ia.astype(np.int32)).to(enroll.rows.device)
         ibd = torch.from_numpy(ib.astype(np.int32)).to(enroll.rows.device)
         out = torch.empty((ia.size,), dtype=torch.float32, device=enroll.rows.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.xv_plda_pairs(dev, scoring._p(enroll.packed), enroll.packed.shape[1], n, scoring._p(enroll.bias),
-                                     scoring._p(test.packed), test.packed.shape[1], m, None if tau is None else scoring._p(tau), k,
-                                     scoring._p(iad), scoring._p(ibd), ia.size, scoring._p(out), C.c_void_p(stream)))
+        stream = _lib.stream(dev)
+        _lib.check(lib.xv_plda_pairs(dev, ptr(enroll.packed), enroll.packed.shape[1], n, ptr(enroll.bias),
+                                     ptr(test.packed), test.packed.shape[1], m, ptr(tau), k,
+                                     ptr(iad), ptr(ibd), ia.size, ptr(out), stream))
         return out if as_tensor else out.cpu().numpy()
 
 
@@ -438,11 +439,11 @@ def llr_histograms(enroll, labels_e, test, labels_t, lo, hi, nbins=8192):
         lad = torch.from_numpy(np.ascontiguousarray(ids[:n])).to(enroll.rows.device)
         lbd = torch.from_numpy(np.ascontiguousarray(ids[n:])).to(enroll.rows.device)
         hist = torch.zeros((2, nbins), dtype=torch.int64, device=enroll.rows.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.xv_plda_histogram(dev, scoring._p(enroll.packed), enroll.packed.shape[1], n, scoring._p(enroll.bias),
-                                         scoring._p(lad), scoring._p(test.packed), test.packed.shape[1], m,
-                                         None if tau is None else scoring._p(tau), scoring._p(lbd), k, lo, hi, nbins,
-                                         C.c_void_p(hist.data_ptr()), C.c_void_p(hist.data_ptr() + 8 * nbins), C.c_void_p(stream)))
+        stream = _lib.stream(dev)
+        _lib.check(lib.xv_plda_histogram(dev, ptr(enroll.packed), enroll.packed.shape[1], n, ptr(enroll.bias),
+                                         ptr(lad), ptr(test.packed), test.packed.shape[1], m,
+                                         ptr(tau), ptr(lbd), k, lo, hi, nbins,
+                                         ptr(hist), C.c_void_p(hist.data_ptr() + 8 * nbins), stream))
         h = hist.cpu().numpy().view(np.uint64)
     return h[0].copy(), h[1].copy()
 
@@ -492,7 +493,7 @@ def _adapt_raw(model, xs, offsets, target_energy, device=0, want_pca=True, budge
     dims, eig, pcas, affs, psis, sweeps = [], [], [], [], [], []
     with torch.cuda.device(device):
         dev = torch.device("cuda:%d" % device)
-        stream = torch.cuda.current_stream(device).cuda_stream
+        stream = _lib.stream(device)
         mean, ainv, psi = _adapt_device(model, device, torch)
         for g0 in range(0, groups, run):
             g1 = min(groups, g0 + run)
@@ -512,9 +513,9 @@ def _adapt_raw(model, xs, offsets, target_energy, device=0, want_pca=True, budge
             else:
                 size = int(ws_bytes)
             ws = torch.empty((max(size, 8),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.xv_plda_adapt(device, scoring._p(xs), d, off.ctypes.data_as(C.c_void_p), cnt, d, scoring._p(mean),
-                                         scoring._p(ainv), scoring._p(psi), te, scoring._p(dim), scoring._p(eigval), scoring._p(pca),
-                                         scoring._p(affine), scoring._p(psi_out), scoring._p(ws), size, C.c_void_p(stream)))
+            _lib.check(lib.xv_plda_adapt(device, ptr(xs), d, off.ctypes.data_as(C.c_void_p), cnt, d, ptr(mean),
+                                         ptr(ainv), ptr(psi), te, ptr(dim), ptr(eigval), ptr(pca),
+                                         ptr(affine), ptr(psi_out), ptr(ws), size, stream))
             dims.append(dim.cpu().numpy())
             eig.append(eigval.cpu().numpy())
             if want_pca:

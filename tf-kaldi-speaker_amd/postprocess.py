@@ -2,13 +2,13 @@
 binaries: speaker-level means of the utterance x-vectors (`ivector-mean ark:$data/spk2utt ...`) and length
 normalisation (`ivector-normalize-length --scaleup=false`), computed on the GPU by csrc/post.hip through the C ABI
 (xv_length_normalize / xv_speaker_mean).  Tables are read and written natively (native_ark).  No CPU path."""
-import ctypes as C
 import os
 import shutil
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import native_ark
 
 
@@ -59,9 +59,9 @@ def length_normalize(x, scaleup=False, device=0):
         return x.copy()
     with torch.cuda.device(device):
         d = _device_tensor(x, device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_length_normalize(device, C.c_void_p(d.data_ptr()), x.shape[1], x.shape[0], x.shape[1],
-                                           int(bool(scaleup)), C.c_void_p(d.data_ptr()), x.shape[1], C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_length_normalize(device, ptr(d), x.shape[1], x.shape[0], x.shape[1],
+                                           int(bool(scaleup)), ptr(d), x.shape[1], stream))
         return d.cpu().numpy()
 
 
@@ -88,10 +88,10 @@ def speaker_mean(keys, x, spk2utt, device=0):
         d_off = torch.from_numpy(np.asarray(off, dtype=np.int32)).to(d.device)
         d_idx = torch.from_numpy(np.asarray(idx, dtype=np.int32)).to(d.device)
         out = torch.empty((len(spks), x.shape[1]), dtype=torch.float32, device=d.device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_speaker_mean(device, C.c_void_p(d.data_ptr()), x.shape[1], x.shape[1], C.c_void_p(d_off.data_ptr()),
-                                       C.c_void_p(d_idx.data_ptr()), len(spks), C.c_void_p(out.data_ptr()), x.shape[1],
-                                       C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_speaker_mean(device, ptr(d), x.shape[1], x.shape[1], ptr(d_off),
+                                       ptr(d_idx), len(spks), ptr(out), x.shape[1],
+                                       stream))
         return spks, out.cpu().numpy(), counts
 
 

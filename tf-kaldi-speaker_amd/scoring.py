@@ -19,10 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
+from ._lib import ptr
 
 
 def _need_device():
@@ -86,10 +83,10 @@ def prepare(x, mean=None, transform=None, normalize=True, eps=0.0, device=0, as_
         td = None if transform is None else _rows(transform, device, "transform")
         out = torch.empty((n, d_out), dtype=torch.float32, device=xd.device)
         if n:
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.xv_score_prepare(device, _p(xd), d_in, n, d_in, None if md is None else _p(md),
-                                            None if td is None else _p(td), t_cols, d_out, t_cols, int(bool(normalize)),
-                                            float(eps), _p(out), d_out, C.c_void_p(stream)))
+            stream = _lib.stream(device)
+            _lib.check(lib.xv_score_prepare(device, ptr(xd), d_in, n, d_in, ptr(md),
+                                            ptr(td), t_cols, d_out, t_cols, int(bool(normalize)),
+                                            float(eps), ptr(out), d_out, stream))
         return out if as_tensor else out.cpu().numpy()
 
 
@@ -103,8 +100,8 @@ def cosine_matrix(a, b, device=0, as_tensor=False):
     with torch.cuda.device(device):
         ad, bd = _rows(a, device, "a"), _rows(b, device, "b")
         out = torch.empty((n, m), dtype=torch.float32, device=ad.device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_score_matrix(device, _p(ad), d, n, _p(bd), d, m, d, _p(out), max(m, 1), C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_score_matrix(device, ptr(ad), d, n, ptr(bd), d, m, d, ptr(out), max(m, 1), stream))
         return out if as_tensor else out.cpu().numpy()
 
 
@@ -127,9 +124,9 @@ def cosine_pairs(a, b, ia, ib, device=0, as_tensor=False):
         iad = torch.from_numpy(ia.astype(np.int32)).to(ad.device)
         ibd = torch.from_numpy(ib.astype(np.int32)).to(ad.device)
         out = torch.empty((ia.size,), dtype=torch.float32, device=ad.device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_score_pairs(device, _p(ad), d, n, _p(bd), d, m, d, _p(iad), _p(ibd), ia.size, _p(out),
-                                      C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_score_pairs(device, ptr(ad), d, n, ptr(bd), d, m, d, ptr(iad), ptr(ibd), ia.size, ptr(out),
+                                      stream))
         return out if as_tensor else out.cpu().numpy()
 
 
@@ -170,8 +167,8 @@ def _panel_args(torch, device, dev, row_bias, ids_a, col_bias, ids_b):
     """What xv_cohort_stats and xv_score_topk take beside their operands: the id arrays uploaded to `dev` -> (row_bias,
     labels_a, col_bias, labels_b), each a pointer or None, the current stream, and the uploads (to keep until the call)."""
     held = [None if ids is None else torch.from_numpy(ids).to(dev) for ids in (ids_a, ids_b)]
-    rb, la, cb, lb = (None if t is None else _p(t) for t in (row_bias, held[0], col_bias, held[1]))
-    return rb, la, cb, lb, C.c_void_p(torch.cuda.current_stream(device).cuda_stream), held
+    rb, la, cb, lb = (ptr(t) for t in (row_bias, held[0], col_bias, held[1]))
+    return rb, la, cb, lb, _lib.stream(device), held
 
 
 def _top_k(ad, lda, n, row_bias, bd, ldb, m, col_bias, d, k, ids_a, ids_b, device, as_tensor):
@@ -193,8 +190,8 @@ def _top_k(ad, lda, n, row_bias, bd, ldb, m, col_bias, d, k, ids_a, ids_b, devic
             if ws is None or ws.numel() < want:
                 _topk_ws[device] = ws = torch.empty((want,), dtype=torch.uint8, device=dev)
             rb, la, cb, lb, stream, held = _panel_args(torch, device, dev, row_bias, ids_a, col_bias, ids_b)
-            _lib.check(lib.xv_score_topk(device, _p(ad), lda, n, rb, la, _p(bd), ldb, m, cb, lb, d, k,
-                                         _p(scores), _p(indices), k, _p(count), _p(ws), ws.numel(), stream))
+            _lib.check(lib.xv_score_topk(device, ptr(ad), lda, n, rb, la, ptr(bd), ldb, m, cb, lb, d, k,
+                                         ptr(scores), ptr(indices), k, ptr(count), ptr(ws), ws.numel(), stream))
         if as_tensor:
             return TopK(scores, indices, count)
         return TopK(scores.cpu().numpy(), indices.cpu().numpy(), count.cpu().numpy())
@@ -286,10 +283,10 @@ def score_histograms(a, labels_a, b=None, labels_b=None, nbins=65536, device=0):
         lad = torch.from_numpy(np.ascontiguousarray(ida)).to(ad.device)
         bd, lbd = (ad, lad) if self_mode else (_rows(b, device, "b"), torch.from_numpy(np.ascontiguousarray(idb)).to(ad.device))
         hist = torch.zeros((2, nbins), dtype=torch.int64, device=ad.device)      # uint64 counts (torch has no uint64 arithmetic)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_score_histogram(device, _p(ad), d, n, _p(lad), _p(bd), d, m, _p(lbd), d, int(self_mode), nbins,
-                                          C.c_void_p(hist.data_ptr()), C.c_void_p(hist.data_ptr() + 8 * nbins),
-                                          C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_score_histogram(device, ptr(ad), d, n, ptr(lad), ptr(bd), d, m, ptr(lbd), d, int(self_mode), nbins,
+                                          ptr(hist), C.c_void_p(hist.data_ptr() + 8 * nbins),
+                                          stream))
         h = hist.cpu().numpy().view(np.uint64)
     return h[0].copy(), h[1].copy()
 

@@ -22,6 +22,7 @@ import collections
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import scoring
 
 CohortStats = collections.namedtuple("CohortStats", ["mean", "std", "count"])
@@ -58,10 +59,9 @@ def _stats(ad, lda, n, row_bias, bd, ldb, m, col_bias, k, top_k, ids_a, ids_b, w
                 workspace_bytes = max(need, min((n + 127) // 128 * 128 * per_row, DEFAULT_WORKSPACE_BYTES // need * need))
             workspace_bytes = int(workspace_bytes)
             ws = torch.empty((max(workspace_bytes, 1),), dtype=torch.uint8, device=dev)
-            p = scoring._p
             rb, la, cb, lb, stream, held = scoring._panel_args(torch, device, dev, row_bias, ids_a, col_bias, ids_b)
-            _lib.check(lib.xv_cohort_stats(device, p(ad), lda, n, rb, la, p(bd), ldb, m, cb, lb, k, top_k,
-                                           p(mean), p(std), p(count), p(ws), workspace_bytes, stream))
+            _lib.check(lib.xv_cohort_stats(device, ptr(ad), lda, n, rb, la, ptr(bd), ldb, m, cb, lb, k, top_k,
+                                           ptr(mean), ptr(std), ptr(count), ptr(ws), workspace_bytes, stream))
         if as_tensor:
             return CohortStats(mean, std, count)
         return CohortStats(mean.cpu().numpy(), std.cpu().numpy(), count.cpu().numpy())

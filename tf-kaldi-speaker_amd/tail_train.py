@@ -23,11 +23,11 @@ of one trained layer (SegLayer and conv_train.TConvLayer add their operator); la
 between the checkpoint's names and the layers; and TailTrainer._step, the step behind the forward (the head's loss and
 gradient, the backward, Adam's shared count, one update per tensor, the StepResult), with its optional `mark` callback."""
 import collections
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import head_train
 from . import losses
 from . import model_io
@@ -122,10 +122,6 @@ def batch_stats_options(params, batch_norm, kernel=None):
                 bessel=kernel is not None and np.ndim(kernel) == 4)
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class Layer(object):
     """What every trained layer keeps on the device: the rows [N, ldw] of the weights (ldw = the width K rounded up to 4, the
     padding stays zero), the bias, the four batch-norm vectors or None, their gradients, the optimizer slots and a workspace
@@ -211,9 +207,9 @@ class Layer(object):
         self._mean = torch.empty((self.out_dim,), dtype=torch.float32, device=z.device)
         self._var = torch.empty((self.out_dim,), dtype=torch.float32, device=z.device)
         ws = self._bn_workspace(rows, z.device)
-        _lib.check(self._lib.xv_bn_batch_forward(self.device, _p(z), self.out_dim, rows, self.out_dim, _p(self.bn[0]), _p(self.bn[1]),
-                                                 self.act, self.momentum, int(self.bessel), _p(self.bn[2]), _p(self.bn[3]), _p(y),
-                                                 self.out_dim, _p(self._mean), _p(self._var), _p(ws), ws.numel(), C.c_void_p(stream)))
+        _lib.check(self._lib.xv_bn_batch_forward(self.device, ptr(z), self.out_dim, rows, self.out_dim, ptr(self.bn[0]), ptr(self.bn[1]),
+                                                 self.act, self.momentum, int(self.bessel), ptr(self.bn[2]), ptr(self.bn[3]), ptr(y),
+                                                 self.out_dim, ptr(self._mean), ptr(self._var), ptr(ws), ws.numel(), stream))
         return y
 
     def _bn_backward(self, gy, z, rows, stream):
@@ -221,10 +217,10 @@ class Layer(object):
         torch = self._torch
         gz = torch.empty((rows, self.out_dim), dtype=torch.float32, device=z.device)
         ws = self._bn_workspace(rows, z.device)
-        _lib.check(self._lib.xv_bn_batch_backward(self.device, _p(gy), self.out_dim, _p(z), self.out_dim, rows, self.out_dim,
-                                                  _p(self._mean), _p(self._var), _p(self.bn[0]), _p(self.bn[1]), self.act, _p(gz),
-                                                  self.out_dim, _p(self.ggamma), _p(self.gbeta), _p(ws), ws.numel(),
-                                                  C.c_void_p(stream)))
+        _lib.check(self._lib.xv_bn_batch_backward(self.device, ptr(gy), self.out_dim, ptr(z), self.out_dim, rows, self.out_dim,
+                                                  ptr(self._mean), ptr(self._var), ptr(self.bn[0]), ptr(self.bn[1]), self.act, ptr(gz),
+                                                  self.out_dim, ptr(self.ggamma), ptr(self.gbeta), ptr(ws), ws.numel(),
+                                                  stream))
         return gz
 
 
@@ -249,11 +245,11 @@ class SegLayer(Layer):
             z = torch.empty((max(n, 1), self.out_dim), dtype=torch.float32, device=x.device)
             y = self._scratch_y(n, x.device) if batch else torch.empty((max(n, 1), self.out_dim), dtype=torch.float32, device=x.device)
             bn = [None] * 4 if batch else self.bn or [None] * 4
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.xv_seg_forward(self.device, _p(x), self.in_dim, n, self.in_dim, _p(self.w), self.ldw, self.out_dim,
-                                                _p(self.b), _p(bn[0]), _p(bn[1]), _p(bn[2]), _p(bn[3]),
-                                                _lib.XV_SEG_ACT_NONE if batch else self.act, _p(z), self.out_dim,
-                                                _p(y), self.out_dim, C.c_void_p(stream)))
+            stream = _lib.stream(self.device)
+            _lib.check(self._lib.xv_seg_forward(self.device, ptr(x), self.in_dim, n, self.in_dim, ptr(self.w), self.ldw, self.out_dim,
+                                                ptr(self.b), ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]),
+                                                _lib.XV_SEG_ACT_NONE if batch else self.act, ptr(z), self.out_dim,
+                                                ptr(y), self.out_dim, stream))
             if batch:
                 y = self._bn_forward(z, n, stream)
         self._x, self._z = x, z
@@ -272,18 +268,18 @@ class SegLayer(Layer):
             gx = torch.empty((n, self.in_dim), dtype=torch.float32, device=x.device) if want_gx else None
             ws = self._workspace(int(self._lib.xv_seg_workspace(n, self.in_dim, self.out_dim)), x.device)
             bn = self.bn or [None] * 4
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = _lib.stream(self.device)
             if self._batch:                  # through the statistics first; the operator then passes gz through its mask
                 gz = self._bn_backward(gy, z, n, stream)
-                _lib.check(self._lib.xv_seg_backward(self.device, _p(gz), self.out_dim, _p(x), self.in_dim, _p(z), self.out_dim, n,
-                                                     self.in_dim, _p(self.w), self.ldw, self.out_dim, None, None, None, None,
-                                                     _lib.XV_SEG_ACT_NONE, _p(gx), self.in_dim, _p(self.gw), _p(self.gb), None, None,
-                                                     _p(ws), ws.numel(), C.c_void_p(stream)))
+                _lib.check(self._lib.xv_seg_backward(self.device, ptr(gz), self.out_dim, ptr(x), self.in_dim, ptr(z), self.out_dim, n,
+                                                     self.in_dim, ptr(self.w), self.ldw, self.out_dim, None, None, None, None,
+                                                     _lib.XV_SEG_ACT_NONE, ptr(gx), self.in_dim, ptr(self.gw), ptr(self.gb), None, None,
+                                                     ptr(ws), ws.numel(), stream))
                 return gx
-            _lib.check(self._lib.xv_seg_backward(self.device, _p(gy), self.out_dim, _p(x), self.in_dim, _p(z), self.out_dim, n,
-                                                 self.in_dim, _p(self.w), self.ldw, self.out_dim, _p(bn[0]), _p(bn[1]), _p(bn[2]),
-                                                 _p(bn[3]), self.act, _p(gx), self.in_dim, _p(self.gw), _p(self.gb), _p(self.ggamma),
-                                                 _p(self.gbeta), _p(ws), ws.numel(), C.c_void_p(stream)))
+            _lib.check(self._lib.xv_seg_backward(self.device, ptr(gy), self.out_dim, ptr(x), self.in_dim, ptr(z), self.out_dim, n,
+                                                 self.in_dim, ptr(self.w), self.ldw, self.out_dim, ptr(bn[0]), ptr(bn[1]), ptr(bn[2]),
+                                                 ptr(bn[3]), self.act, ptr(gx), self.in_dim, ptr(self.gw), ptr(self.gb), ptr(self.ggamma),
+                                                 ptr(self.gbeta), ptr(ws), ws.numel(), stream))
         return gx
 
     def kernel(self):
@@ -393,10 +389,10 @@ class TailTrainer(object):
 
     def _apply(self, w, g, slots, lr, l2):
         h = self.head
-        stream = self._torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.xv_opt_step(self.device, h.kind, int(h.nesterov), _p(w), _p(g), _p(slots[0]) if slots else None,
-                                         _p(slots[1]) if len(slots) > 1 else None, w.numel(), float(lr), l2, h.clip_norm, h.momentum,
-                                         self.num_steps, _p(self._ws), self._ws.numel(), C.c_void_p(stream)))
+        stream = _lib.stream(self.device)
+        _lib.check(self._lib.xv_opt_step(self.device, h.kind, int(h.nesterov), ptr(w), ptr(g), ptr(slots[0]) if slots else None,
+                                         ptr(slots[1]) if len(slots) > 1 else None, w.numel(), float(lr), l2, h.clip_norm, h.momentum,
+                                         self.num_steps, ptr(self._ws), self._ws.numel(), stream))
 
     def _step(self, owner, forward, backward, labels, learning_rate, global_step, mark):
         """THE training step, of this trainer (owner is self) and of every trainer stacked in front of it (frame_train.Stacked):

@@ -16,6 +16,7 @@ import sys
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import model_io
 
 _PRECISIONS = {"f32": _lib.XV_PREC_F32, "bf16x3": _lib.XV_PREC_BF16X3, "f16x3": _lib.XV_PREC_F16X3, "f16f6": _lib.XV_PREC_F16F6}
@@ -286,9 +287,9 @@ class Trainer(object):
         torch = self._torch
         off = np.ascontiguousarray(offsets, dtype=np.int32)
         plan = C.c_void_p()
-        stream = torch.cuda.current_stream(self._device_index).cuda_stream
+        stream = _lib.stream(self._device_index)
         rc = self._lib.xv_plan_create(self._h, off.ctypes.data_as(C.c_void_p), len(off) - 1, nid,
-                                      C.c_void_p(stream), C.byref(plan))
+                                      stream, C.byref(plan))
         if rc == _lib.XV_ERR_TOO_SHORT:
             raise ValueError(self._lib.xv_last_error(self._h).decode())
         _lib.check(rc, self._h)
@@ -348,9 +349,9 @@ class Trainer(object):
         # `out` may also be PINNED host memory (device-accessible): the last kernel then writes the embeddings straight into it and
         # no copy sits between two forwards (a D2H copy on the compute stream is an engine switch: tools/pipeline_probe.py)
         assert (out.is_cuda or out.is_pinned()) and out.dtype == torch.float32 and out.is_contiguous()
-        stream = torch.cuda.current_stream(self._device_index).cuda_stream
-        args = (self._h, plan, C.c_void_p(feats_dev.data_ptr()), int(feats_dev.shape[1]),
-                C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream))
+        stream = _lib.stream(self._device_index)
+        args = (self._h, plan, ptr(feats_dev), int(feats_dev.shape[1]),
+                ptr(out), out.numel(), ptr(ws), ws.numel(), stream)
         _lib.check(self._lib.xv_forward(*args), self._h)
         return out
 
@@ -423,8 +424,8 @@ class Trainer(object):
         if self._precision not in _F16_RANGE or self._h is None:
             host_flags.zero_()
             return
-        stream = self._torch.cuda.current_stream(self._device_index).cuda_stream
-        _lib.check(self._lib.xv_flags_async(self._h, C.c_void_p(host_flags.data_ptr()), C.c_void_p(stream)), self._h)
+        stream = _lib.stream(self._device_index)
+        _lib.check(self._lib.xv_flags_async(self._h, ptr(host_flags), stream), self._h)
 
     def raise_on_flags(self, code, emb=None):
         if code == 1 or (emb is not None and self._precision in _F16_RANGE and not np.isfinite(emb).all()):
@@ -435,7 +436,7 @@ class Trainer(object):
                                      "silently (subnormal low halves); rescale the features or run with precision 'bf16x3'" % self._precision)
 
     def decode_flags(self, host_flags):
-        return int(self._lib.xv_flags_decode(C.c_void_p(host_flags.data_ptr()))) if self._lib is not None else 0
+        return int(self._lib.xv_flags_decode(ptr(host_flags))) if self._lib is not None else 0
 
     def _checked(self, emb):
         """Host copies of fp16-split results are range-checked, so that an overflow fails loudly instead of writing wrong
@@ -586,7 +587,7 @@ class Trainer(object):
             ptrs = np.fromiter((u.__array_interface__["data"][0] for u in utterances), dtype=np.uint64, count=n)
             nbytes = np.asarray(lens, dtype=np.int64) * (4 * d)
             got = self._lib.xv_pack_rows(C.c_void_p(ptrs.ctypes.data), C.c_void_p(nbytes.ctypes.data), n,
-                                         C.c_void_p(pin.data_ptr()), 4)
+                                         ptr(pin), 4)
             if got != int(nbytes.sum()):
                 raise RuntimeError("xv_pack_rows copied %d of %d bytes" % (got, int(nbytes.sum())))
             return

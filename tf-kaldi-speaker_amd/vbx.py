@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from . import scoring
-from .scoring import _p
 
 MAX_ROWS = 8192
 MAX_SPEAKERS = 64
@@ -129,10 +129,10 @@ def vb_hmm(model, rows, offsets, gamma, pi, num_spk=None, fa=0.3, fb=17.0, loop_
             raise _lib.XvError(need, (lib.xv_last_error(None) or b"").decode("utf-8", "replace"))
         size = need if ws_bytes is None else int(ws_bytes)
         ws = torch.empty((max(size, 8),), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.xv_vbx(device, _p(xd), d, offsets.ctypes.data_as(C.c_void_p), spk.ctypes.data_as(C.c_void_p), groups, d, _p(a),
-                              _p(psi), r, _p(gd), _p(pd), fa, fb, loop_prob, max_iters, epsilon, _p(labels), _p(elbo), _p(iters), _p(ws),
-                              size, C.c_void_p(stream)))
+        stream = _lib.stream(device)
+        _lib.check(lib.xv_vbx(device, ptr(xd), d, offsets.ctypes.data_as(C.c_void_p), spk.ctypes.data_as(C.c_void_p), groups, d, ptr(a),
+                              ptr(psi), r, ptr(gd), ptr(pd), fa, fb, loop_prob, max_iters, epsilon, ptr(labels), ptr(elbo), ptr(iters), ptr(ws),
+                              size, stream))
         lo, hi = (int(offsets[0]), int(offsets[-1])) if groups else (0, 0)
         out = RawResult(gd, pd, elbo[:groups], iters[:groups], labels[lo:hi])
         if not as_tensor:
