@@ -1017,6 +1017,47 @@ int xv_metric_loss(int device, const float* x_dev, int64_t ldx, const int64_t* o
                    int32_t* row_top1_dev /* [total] or NULL */, double* group_loss_dev /* [G] */,
                    int64_t* group_count_dev /* [G, 2] */, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- gradients of the triplet heads (csrc/metric_loss_grad.hip): what fine-tuning with `semihard_triplet_loss` or
+ * `angular_triplet_loss` needs (egs/voxceleb/v1/nnet/lib/finetune.py, model/trainer.py:113-129).  Notation, layout and forward
+ * outputs are those of xv_metric_loss above: row_loss, row_count, group_loss and group_count are bit for bit what it writes for
+ * the same arguments (one product chain, one mining order).  grad_x_dev [total, ldg] = float32(grad_scale dL_g / dx_i), L_g the
+ * loss of the row's group; everything before that rounding is double.  The gradient is that of model/loss.py:387-663 as
+ * TensorFlow differentiates it wherever TensorFlow's choice is unique: **parity unpinned** against TensorFlow, pinned to
+ * torch.autograd in float64 (tests/test_metric_grad_host.py).  Comparisons, masks, counts and the normalisers (pairs, A + 1e-16,
+ * B) are constants.  The choices:
+ *   Hinge: max(t, 0) passes 1 iff t > 0; so does the clamp of D2 (it passes iff D2 > 0).
+ *   Selections (the semi-hard negative z, hp_i and hn_i of HARD) send their gradient to one element, the lowest column among
+ *     equals.  TensorFlow splits a tie evenly: different on exact ties only.
+ *   XV_METRIC_SEMIHARD: an active term of the pair (i, j) adds +1 at d(i, j) and -1 at d(i, k*).  dd/dD2 = 1 with `squared`,
+ *     else 1 / (2 d) where D2 > 0 and 0 where D2 == 0 (the reference's mask * 1e-16, model/common.py:86-92: duplicate rows give
+ *     0, never inf).  n_i = G(v_i, v_i) is differentiated: dD2/dv_i = 2 (v_i - v_j).
+ *   XV_METRIC_ANGULAR_ALL: every triplet with t > 0 adds +1 at c(i, k) and -pos'(c(i, j)) at c(i, j).
+ *   XV_METRIC_ANGULAR_HARD: a row with a negative and hn_i - hp_i > 0 adds +1/B at c(i, k*) and -pos'(c(i, j*)) / B at c(i, j*).
+ *     The pair (i, i) carries no gradient: c(i, i) is the constant 1 (TensorFlow would form inf * 0 there for arcsoftmax).
+ *   pos': asoftmax 1 (m = 1), 4 |c| (m = 2), s3 (32 c^3 - 16 c) (m = 4), signs being constants; amsoftmax 1; arcsoftmax
+ *     cos m + c sin m / sqrt(1 - c^2), negated on the branch c <= cos(pi - m).
+ *   Clip: dc/dG = 1 for -1 < G < 1, else 0; pos' is never evaluated at |c| = 1.
+ *   Normalisation (`normalize`, always for the angular kinds): gx_i = s_i (gu_i - (gu_i . u_i) u_i) where sum x^2 > 1e-12
+ *     (tested as s_i < 1e6), else s_i gu_i: the max branch is a constant.
+ *   No NaN or inf comes out of finite rows whose products stay finite.
+ * A group's outputs are a pure function of its own rows, labels and the options: the same bits on every repeat, alone or in any
+ *   batch, in any group order, for every legal ws_bytes, leading dimension and 4-byte aligned base, whatever the buffers held
+ *   before.  No floating-point atomics.  The columns d .. ldg - 1 of grad_x_dev are never written.  The per-element error bound
+ *   is derived in the header of csrc/metric_loss_grad.hip (tests/helpers/ref_metric_grad.bounds()).
+ * Kinds 0 .. 2 only: the GE2E kinds return XV_ERR_UNSUPPORTED (the reference never trains with them), as does a group over
+ *   1024 rows (panel and counts of a group live in LDS).  ldg >= d and a finite grad_scale, else XV_ERR_INVALID; everything
+ *   xv_metric_loss refuses is refused alike.  Every argument check comes before the first HIP call and the outputs are untouched
+ *   on any error.  num_groups = 0 returns XV_OK and touches nothing.
+ * Workspace (8-byte aligned): xv_metric_loss_grad_workspace is the least ws_bytes: tables, three doubles per row and one slot of
+ *   8 B (B + d) bytes rounded up to 256, B = the largest group (dL/dM [B, B] and its product with the rows [B, d]); every
+ *   further slot lets one more group run at a time (up to 64).  It returns the negative code for arguments the call refuses. */
+int64_t xv_metric_loss_grad_workspace(int64_t num_groups, const int64_t* offsets_host /* [num_groups + 1] */, int d, int kind);
+int xv_metric_loss_grad(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host /* [num_groups + 1] */,
+                        int64_t num_groups, int d, const int32_t* labels_dev, int kind, int pos_head, double margin, int squared,
+                        int normalize, double grad_scale, double* row_loss_dev /* [total] */, int64_t* row_count_dev /* [total] */,
+                        double* group_loss_dev /* [G] */, int64_t* group_count_dev /* [G, 2] */,
+                        float* grad_x_dev /* [total, ldg] */, int64_t ldg, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- back-end training statistics on the GPU (csrc/backend.hip): the sums behind `ivector-mean`, `ivector-compute-lda` and
  * `ivector-compute-plda` (egs/voxceleb/v1/run.sh:384-400, egs/sre/v1/run.sh:399-411); the d x d linear algebra behind them is
  * host float64 (tf_kaldi_speaker_amd.backend).  Kaldi is absent from the reference tree: **parity unpinned**.

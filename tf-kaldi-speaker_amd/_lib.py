@@ -211,6 +211,8 @@ SIGNATURES = (
     ("xv_metric_loss_workspace", i64, (i64, vp, i32, i32)),
     ("xv_metric_loss_slot_bytes", i64, (i32, i32, i32)),
     ("xv_metric_loss", i32, (i32, vp, i64, vp, i64, i32, vp, i32, i32, f64, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, i64, vp)),
+    ("xv_metric_loss_grad_workspace", i64, (i64, vp, i32, i32)),
+    ("xv_metric_loss_grad", i32, (i32, vp, i64, vp, i64, i32, vp, i32, i32, f64, i32, i32, f64, vp, vp, vp, vp, vp, i64, vp, i64, vp)),
     # back-end training statistics on the GPU
     ("xv_gram_f64_workspace", i64, (i64, i32)),
     ("xv_gram_f64", i32, (i32, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp)),

@@ -59,7 +59,7 @@ def _node(d, which):
     return int(m.group(1))
 
 
-def check_supported(params, conv_layers=False):
+def check_supported(params, conv_layers=False, metric=False):
     """NotImplementedError, with the reason, for what the attention trainers do not cover (the module's docstring lists it).
     conv_layers: every frame layer is trained (AttConvTrainer); otherwise the layers behind frame_train.frozen_node
     (AttFrameTrainer), and an attention input in front of that node is refused as well."""
@@ -84,7 +84,7 @@ def check_supported(params, conv_layers=False):
     if not 1 <= nk <= _lib.XV_MAX_ATT_LAYERS or nv > _lib.XV_MAX_ATT_LAYERS:
         raise NotImplementedError("att_key_num_nodes needs 1 .. %d layers and att_value_num_nodes at most %d, got %d and %d"
                                   % (_lib.XV_MAX_ATT_LAYERS, _lib.XV_MAX_ATT_LAYERS, nk, nv))
-    tail_train.check_supported(params)
+    tail_train.check_supported(params, metric)
     if net not in conv_train._NETS:
         raise NotImplementedError("Not implement %s network" % net)
     widths = conv_train._NETS[net][1]
@@ -135,19 +135,19 @@ def _layer_names(specs):
     return out
 
 
-def trained_names(params, conv_layers=False):
+def trained_names(params, conv_layers=False, metric=False):
     """The TensorFlow names of every variable the attention trainer updates: the frame layers, the key network, the value
     network, the query, then tail_train.trained_names."""
     key, value, query = attention_variables(params)
-    return _layer_names(_frame_specs(params, conv_layers)) + _layer_names(key + value) + [query] + tail_train.trained_names(params)
+    return _layer_names(_frame_specs(params, conv_layers)) + _layer_names(key + value) + [query] + tail_train._trained_names(params, metric)
 
 
-def l2_assignment(params, conv_layers=False):
+def l2_assignment(params, conv_layers=False, metric=False):
     """name -> the l2 factor of its update: weight_l2_regularizer on every kernel, the attention's included, optimizer_config's
     rule on the head's kernel, 0 on the query and on every bias, gamma and beta."""
     reg = float(_dict(params).get("weight_l2_regularizer", 0.0))
-    out = dict.fromkeys(trained_names(params, conv_layers), 0.0)
-    out.update(tail_train.l2_assignment(params))
+    out = dict.fromkeys(trained_names(params, conv_layers, metric), 0.0)
+    out.update(tail_train._l2_assignment(params, metric))
     key, value, _ = attention_variables(params)
     for spec in tuple(_frame_specs(params, conv_layers)) + key + value:
         out[spec.kernel] = reg
@@ -363,11 +363,12 @@ class AttFrameTrainer(_AttStage, frame_train.FrameTrainer):
     learning_rate, global_step=0, mark=None); mark sees "attention_forward" behind "frame_forward" and "attention_backward" behind
     "pool_backward" in addition to StackedTrainer's stages."""
 
-    _check = staticmethod(lambda params: check_supported(params, False))
+    _check = staticmethod(lambda params, metric=False: check_supported(params, False, metric))
     _l2 = staticmethod(lambda params: l2_assignment(params, False))
+    _metric_l2 = staticmethod(lambda params: l2_assignment(params, False, True))
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
-        frame_train.FrameTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias, batch_norm)
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving", metric=False):
+        frame_train.FrameTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias, batch_norm, metric)
         self._open()
 
 
@@ -376,9 +377,10 @@ class AttConvTrainer(_AttStage, conv_train.ConvTrainer):
     networks, the query, the segment-level layers and the head.  forward(feats_dev, offsets), step(feats_dev, offsets, labels,
     learning_rate, global_step=0, mark=None); the marks are AttFrameTrainer's."""
 
-    _check = staticmethod(lambda params: check_supported(params, True))
+    _check = staticmethod(lambda params, metric=False: check_supported(params, True, metric))
     _l2 = staticmethod(lambda params: l2_assignment(params, True))
+    _metric_l2 = staticmethod(lambda params: l2_assignment(params, True, True))
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
-        conv_train.ConvTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias, batch_norm)
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving", metric=False):
+        conv_train.ConvTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias, batch_norm, metric)
         self._open()

@@ -43,10 +43,10 @@ def _dict(params):
     return params if isinstance(params, dict) else params.dict
 
 
-def check_supported(params):
+def check_supported(params, metric=False):
     """NotImplementedError for everything frame_train.check_supported refuses: ResNet-18, any pooling other than statistics
-    pooling, PReLU, feature_norm, the heads and optimizers HeadTrainer refuses."""
-    frame_train.check_supported(params)
+    pooling, PReLU, feature_norm, the heads and optimizers HeadTrainer refuses (metric: tail_train's second door)."""
+    frame_train.check_supported(params, metric)
 
 
 def frame_variables(params):
@@ -73,6 +73,15 @@ def trained_names(params):
 def l2_assignment(params):
     """name -> the l2 factor of its update, the convolutions' kernels included (frame_train.stacked_l2 of frame_variables)."""
     return frame_train.stacked_l2(frame_variables(params), params)
+
+
+def metric_trained_names(params):
+    """trained_names behind the metric door (tail_train.metric_trained_names): no head layer."""
+    return frame_train.stacked_names(frame_variables(params), params, True)
+
+
+def metric_l2_assignment(params):
+    return frame_train.stacked_l2(frame_variables(params), params, True)
 
 
 def out_offsets(offsets, taps):
@@ -198,11 +207,12 @@ class ConvTrainer(frame_train.StackedTrainer):
     integers."""
 
     _check, _specs, _l2 = staticmethod(check_supported), staticmethod(frame_variables), staticmethod(l2_assignment)
+    _metric_l2 = staticmethod(metric_l2_assignment)
     _CHAIN = "%s takes %d channels, %s gives %d"
     _INPUT = ("feats_dev", "")
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
-        frame_train.StackedTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias, batch_norm)
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving", metric=False):
+        frame_train.StackedTrainer.__init__(self, params, weights, num_classes, device, seed, kernel, bias, batch_norm, metric)
         self.context = sum(layer.taps - 1 for layer in self.frame_layers)
 
     def _layer(self, spec, kernel, bias, bn, device, num_slots):

@@ -1122,4 +1122,53 @@ int xv_metric_loss(int device, const float* x_dev, int64_t ldx, const int64_t* o
   });
 }
 
+// kinds and group sizes of the gradient: the forward's checks, then what only the gradient refuses
+static int metric_grad_groups(const char* who, int64_t num_groups, const int64_t* offsets_host, int d, int kind) {
+  if (const int rc = metric_groups(who, num_groups, offsets_host, d, kind)) return rc;
+  if (kind > XV_METRIC_ANGULAR_HARD)
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: kind %d has no gradient (the triplet kinds 0 .. 2 have)", who, kind);
+  for (int64_t g = 0; g < num_groups; ++g)
+    if (offsets_host[g + 1] - offsets_host[g] > 1024)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: group %lld has %lld rows (the gradient takes 1 .. 1024)", who, (long long)g,
+                  (long long)(offsets_host[g + 1] - offsets_host[g]));
+  return XV_OK;
+}
+
+int64_t xv_metric_loss_grad_workspace(int64_t num_groups, const int64_t* offsets_host, int d, int kind) {
+  if (const int rc = metric_grad_groups("xv_metric_loss_grad_workspace", num_groups, offsets_host, d, kind)) return rc;
+  if (num_groups == 0) return 0;
+  return metric_loss_grad_workspace_bytes(num_groups, offsets_host, d);
+}
+
+int xv_metric_loss_grad(int device, const float* x_dev, int64_t ldx, const int64_t* offsets_host, int64_t num_groups, int d,
+                        const int32_t* labels_dev, int kind, int pos_head, double margin, int squared, int normalize,
+                        double grad_scale, double* row_loss_dev, int64_t* row_count_dev, double* group_loss_dev,
+                        int64_t* group_count_dev, float* grad_x_dev, int64_t ldg, void* ws_dev, int64_t ws_bytes, void* stream) {
+  if (const int rc = metric_grad_groups("xv_metric_loss_grad", num_groups, offsets_host, d, kind)) return rc;
+  if (num_groups == 0) return XV_OK;
+  if (!x_dev || !labels_dev || !row_loss_dev || !row_count_dev || !group_loss_dev || !group_count_dev || !grad_x_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss_grad: null pointer");
+  if (ldx < d) return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss_grad: ldx = %lld < d = %d", (long long)ldx, d);
+  if (ldg < d) return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss_grad: ldg = %lld < d = %d", (long long)ldg, d);
+  if (!std::isfinite(margin) || !std::isfinite(grad_scale))
+    return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss_grad: margin and grad_scale must be finite");
+  if (kind == XV_METRIC_ANGULAR_ALL || kind == XV_METRIC_ANGULAR_HARD) {
+    if (pos_head < XV_LOSS_ASOFTMAX || pos_head > XV_LOSS_ARCSOFTMAX)
+      return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss_grad: unknown pos_head %d", pos_head);
+    if (pos_head == XV_LOSS_ASOFTMAX && margin != 1.0 && margin != 2.0 && margin != 4.0)
+      return fail(nullptr, XV_ERR_UNSUPPORTED, "xv_metric_loss_grad: m=%g is not supported (asoftmax: 1, 2 or 4)", margin);
+  }
+  const int64_t need = metric_loss_grad_workspace_bytes(num_groups, offsets_host, d);
+  if (ws_bytes < need || !ws_dev)
+    return fail(nullptr, XV_ERR_WORKSPACE, "xv_metric_loss_grad: workspace of %lld bytes, %lld needed", (long long)(ws_dev ? ws_bytes : 0),
+                (long long)need);
+  if (reinterpret_cast<uintptr_t>(ws_dev) & 7)
+    return fail(nullptr, XV_ERR_INVALID, "xv_metric_loss_grad: the workspace must be 8-byte aligned (it holds offsets and doubles)");
+  return with_device(device, "xv_metric_loss_grad", [&] {
+    return launch_metric_loss_grad(x_dev, ldx, offsets_host, num_groups, d, labels_dev, kind, pos_head, margin, squared ? 1 : 0,
+                                   normalize ? 1 : 0, grad_scale, row_loss_dev, row_count_dev, group_loss_dev, group_count_dev,
+                                   grad_x_dev, ldg, ws_dev, ws_bytes, to_stream(stream));
+  });
+}
+
 }  // extern "C"

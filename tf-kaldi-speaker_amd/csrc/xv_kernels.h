@@ -334,6 +334,15 @@ hipError_t launch_metric_loss(const float* x, int64_t ldx, const int64_t* offset
                               double* row_loss, int64_t* row_count, int32_t* row_top1, double* group_loss, int64_t* group_count,
                               void* ws, int64_t ws_bytes, hipStream_t stream);
 
+// The triplet kinds with their gradient (csrc/metric_loss_grad.hip): the forward outputs of launch_metric_loss, bit for bit,
+// and grad_x [total, ldg] = float32(grad_scale dL_g / dx).  The caller has checked every argument (kinds 0 .. 2, 1 .. 1024 rows
+// per group); num_groups >= 1.
+int64_t metric_loss_grad_workspace_bytes(int64_t num_groups, const int64_t* offsets, int d);
+hipError_t launch_metric_loss_grad(const float* x, int64_t ldx, const int64_t* offsets, int64_t num_groups, int d,
+                                   const int32_t* labels, int kind, int pos_head, double margin, int squared, int normalize,
+                                   double grad_scale, double* row_loss, int64_t* row_count, double* group_loss, int64_t* group_count,
+                                   float* grad_x, int64_t ldg, void* ws, int64_t ws_bytes, hipStream_t stream);
+
 // classifier-head validation loss (csrc/loss.hip): model/loss.py:9-48,80-384 without the logit matrix
 // kernel [E, ldk] -> class rows [C, ldr], columns normalised (tf.nn.l2_normalize) when `normalize`
 hipError_t launch_loss_classes(const float* kernel, int64_t ldk, int E, int64_t C, int normalize, float* rows, int64_t ldr,

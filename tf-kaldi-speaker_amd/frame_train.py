@@ -46,15 +46,16 @@ def _dict(params):
     return params if isinstance(params, dict) else params.dict
 
 
-def check_supported(params):
+def check_supported(params, metric=False):
     """NotImplementedError for what the frame-level stage does not cover: ResNet-18 (its dense1 / dense2 follow 2-D
-    convolutions), any pooling other than statistics pooling, then everything tail_train.check_supported refuses."""
+    convolutions), any pooling other than statistics pooling, then everything tail_train.check_supported refuses (metric: its
+    second door)."""
     d = _dict(params)
     if d.get("network_type", "tdnn") == "resnet_18":
         raise NotImplementedError("resnet_18: no 1-tap frame layers lie between its convolutions and the pooling node")
     if d.get("pooling_type", "statistics_pooling") != "statistics_pooling":
         raise NotImplementedError("pooling_type %s: only the gradient of statistics_pooling is implemented" % d.get("pooling_type"))
-    tail_train.check_supported(params)
+    tail_train.check_supported(params, metric)
     if d.get("network_type", "tdnn") not in _FRAME:
         raise NotImplementedError("Not implement %s network" % d.get("network_type"))
 
@@ -74,21 +75,21 @@ def frozen_node(params):
     return "tdnn%d_relu" % _FRAME[_dict(params).get("network_type", "tdnn")][2]
 
 
-def stacked_names(frame_specs, params):
+def stacked_names(frame_specs, params, metric=False):
     """The TensorFlow names of every variable a StackedTrainer with these frame layers updates: the frame layers first, then
     tail_train.trained_names."""
     out = []
     for spec in frame_specs:
         out += [spec.kernel, spec.bias, spec.bn + "/gamma", spec.bn + "/beta"]
-    return out + tail_train.trained_names(params)
+    return out + tail_train._trained_names(params, metric)
 
 
-def stacked_l2(frame_specs, params):
+def stacked_l2(frame_specs, params, metric=False):
     """name -> the l2 factor of its update: weight_l2_regularizer on every kernel, the frame layers' included, optimizer_config's
     rule on the head's kernel, 0 on every bias, gamma and beta."""
     reg = float(_dict(params).get("weight_l2_regularizer", 0.0))
-    out = dict.fromkeys(stacked_names(frame_specs, params), 0.0)
-    out.update(tail_train.l2_assignment(params))
+    out = dict.fromkeys(stacked_names(frame_specs, params, metric), 0.0)
+    out.update(tail_train._l2_assignment(params, metric))
     for spec in frame_specs:
         out[spec.kernel] = reg
     return out
@@ -102,6 +103,15 @@ def trained_names(params):
 def l2_assignment(params):
     """name -> the l2 factor of its update (stacked_l2 of frame_variables)."""
     return stacked_l2(frame_variables(params), params)
+
+
+def metric_trained_names(params):
+    """trained_names behind the metric door (tail_train.metric_trained_names): no head layer."""
+    return stacked_names(frame_variables(params), params, True)
+
+
+def metric_l2_assignment(params):
+    return stacked_l2(frame_variables(params), params, True)
 
 
 
@@ -173,15 +183,17 @@ class StackedTrainer(object):
     layer its momentum and, by the rank of its own kernel, bessel.  forward() is the inference path in both modes."""
 
     _check = _specs = _l2 = None        # the module's check_supported, frame_variables and l2_assignment, as staticmethods
+    _metric_l2 = None                   # its metric_l2_assignment
     _CHAIN = None       # "%s ... %d ..., %s ... %d": a layer's kernel and input width, the layer before and its output width
     _INPUT = None       # (the argument's name in the messages, what follows "must be a device tensor")
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
-        self._check(params)
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving", metric=False):
+        self._check(params, metric)
         self.params = params
         self.batch_norm = batch_norm
+        self.metric = bool(metric)                       # tail_train.check_supported: the door of the two triplet losses
         self.frame_specs = self._specs(params)
-        self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias, batch_norm)
+        self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias, batch_norm, metric)
         num_slots = len(self.tail.layers[0].slots["kernel"])
         self.frame_layers = [self._layer(spec, *tail_train.layer_weights(spec, weights), device, num_slots) for spec in self.frame_specs]
         for a, b, sa, sb in zip(self.frame_layers[:-1], self.frame_layers[1:], self.frame_specs[:-1], self.frame_specs[1:]):
@@ -194,7 +206,7 @@ class StackedTrainer(object):
         self.layers = self.frame_layers + list(self.tail.layers)
         self.head = self.tail.head
         self.embed_dim = self.tail.embed_dim
-        self.l2 = self._l2(params)
+        self.l2 = self._metric_l2(params) if metric else self._l2(params)
         self._torch = losses._need_device()
         self.tail._fit_workspace(self.layers)
         self.num_steps = 0                                                   # adam's t, shared by every tensor
@@ -292,6 +304,7 @@ class FrameTrainer(StackedTrainer):
     through.  forward(frames_dev, offsets), step(frames_dev, offsets, labels, learning_rate, global_step=0, mark=None)."""
 
     _check, _specs, _l2 = staticmethod(check_supported), staticmethod(frame_variables), staticmethod(l2_assignment)
+    _metric_l2 = staticmethod(metric_l2_assignment)
     _CHAIN = "%s has %d rows, %s %d columns"
     _INPUT = ("frames_dev", ": the frames never leave the device")
 

@@ -265,6 +265,10 @@ def _conv_step(trainer, head, feats, labels, lr, step):
         return head.step(dev, np.arange(b + 1, dtype=np.int64) * t, labels, lr, global_step=step)
 
 
+METRIC_HEAD_ONLY = ("loss_func %s has no classifier layer: there is no head to train; give --segment-layers, --frame-layers or "
+                    "--conv-layers")
+
+
 def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_model_dir, weights=None, seed=0, keep_head=False,
                precision=None, log=None, segment_layers=False, frame_layers=False, conv_layers=False, batch_norm="moving"):
     """Train the head of `trainer` (a Trainer built for "predict" with the pre-trained weights loaded; its params name the head,
@@ -290,6 +294,11 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     trained layers in training mode (tail_train.batch_stats_options): the checkpoints then also hold their moving_mean and
     moving_variance, and the validation after each epoch, the unchanged Trainer.valid on the written checkpoint, normalises with
     them.  The default "moving" changes nothing.
+    With `semihard_triplet_loss` or `angular_triplet_loss` (valid.METRIC_LOSSES) the trainers are built through their metric
+    door (tail_train.check_supported): there is no classifier layer, so at least one of the three layer switches is needed and
+    keep_head means nothing; a batch needs two speakers and two segments of each (a negative and a positive); every variable
+    of `weights`, any softmax/output/* included, is written back unchanged unless a layer trains it; and each epoch's checkpoint
+    is judged by valid.metric_valid (e2e_valid_loss for the angular triplet loss, as save_and_set_valid_loss decides).
     -> [(epoch, step, valid loss, eer, learning rate)]."""
     if batch_norm not in ("moving", "batch"):
         raise ValueError("batch_norm must be moving or batch, got %r" % (batch_norm,))
@@ -300,6 +309,14 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     from .trainer import Trainer
     params = trainer.params
     p = params.dict
+    metric = p.get("loss_func") in valid_mod.METRIC_LOSSES
+    if metric:
+        if not (segment_layers or frame_layers or conv_layers):
+            raise ValueError(METRIC_HEAD_ONLY % p.get("loss_func"))
+        if int(p.get("num_segments_per_speaker", 0)) < 2 or int(p.get("num_speakers_per_batch", 0)) < 2:
+            raise ValueError("%s needs num_speakers_per_batch >= 2 and num_segments_per_speaker >= 2 (a negative and a positive "
+                             "pair in every batch), got %s and %s" % (p.get("loss_func"), p.get("num_speakers_per_batch"),
+                                                                      p.get("num_segments_per_speaker")))
     if weights is None:
         weights, _ = model_io.load_weights(trainer.model)
         if weights is None:
@@ -318,16 +335,16 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     attention = (conv_layers or frame_layers) and p.get("pooling_type") == "self_attention"
     if attention:                                                        # the attention trainers of att_train.py, same steps
         from . import att_train
-        att_train.check_supported(params, conv_layers)                   # before the trainer is touched
+        att_train.check_supported(params, conv_layers, metric)           # before the trainer is touched
     if conv_layers:
         from . import conv_train
         if not attention:
-            conv_train.check_supported(params)                           # before the trainer is touched
+            conv_train.check_supported(params, metric)                   # before the trainer is touched
         segment_layers = frame_layers = True
     elif frame_layers:
         from . import frame_train
         if not attention:
-            frame_train.check_supported(params)                          # before the trainer is touched
+            frame_train.check_supported(params, metric)                  # before the trainer is touched
         segment_layers = True
         trainer.embeddings = frame_train.frozen_node(params)
     else:
@@ -335,28 +352,30 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     try:
         if segment_layers:
             from . import tail_train
-            tail_train.check_supported(params)
+            tail_train.check_supported(params, metric)
             embed_dim = int(weights[tail_train.segment_variables(params)[1].kernel].shape[1])
         else:
             probe = trainer.predict(np.zeros((1, int(p["min_segment_len"]), trainer.dim), dtype=np.float32))
             embed_dim = int(probe.shape[-1])
         kernel = bias = None
-        if keep_head:
+        if keep_head and not metric:
             k = weights.get(model_io.SOFTMAX_KERNEL)
             if k is not None and tuple(k.shape) == (embed_dim, num_classes):
                 kernel, bias = np.asarray(k), weights.get(model_io.SOFTMAX_BIAS)
         if attention:
             make = att_train.AttConvTrainer if conv_layers else att_train.AttFrameTrainer
-            head = make(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
+            head = make(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm, metric)
         elif conv_layers:
-            head = conv_train.ConvTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
+            head = conv_train.ConvTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm, metric)
         elif frame_layers:
-            head = frame_train.FrameTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
+            head = frame_train.FrameTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm, metric)
         elif segment_layers:
-            head = tail_train.TailTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm)
+            head = tail_train.TailTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm, metric)
         else:
             head = HeadTrainer(params, embed_dim, num_classes, trainer._device_index, seed, kernel, bias)
-        frozen = {k: v for k, v in weights.items() if k not in (model_io.SOFTMAX_KERNEL, model_io.SOFTMAX_BIAS)}
+        # the metric door trains no head: whatever softmax/output/* the checkpoint holds is kept as it is
+        frozen = dict(weights) if metric else {k: v for k, v in weights.items()
+                                               if k not in (model_io.SOFTMAX_KERNEL, model_io.SOFTMAX_BIAS)}
         nnet = os.path.join(out_model_dir, "nnet")
         history, step = [], 0
         for epoch in range(num_epochs):
@@ -382,9 +401,13 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
             model_io.save_model(out_model_dir, p, trainer.dim, out, step=step)
             judge = Trainer(params, out_model_dir, trainer.dim, single_cpu=True, device=trainer._device_index,
                             precision=precision or trainer._precision)
-            judge.build("valid")
-            valid_loss, emb, labels = judge.valid(valid_dir, valid_spklist, batch_type=p.get("batch_type", "softmax"),
-                                                  output_embeddings=True)
+            if metric:
+                valid_loss, emb, labels = valid_mod.metric_valid(judge, valid_dir, valid_spklist,
+                                                                 batch_type=p.get("batch_type", "softmax"), output_embeddings=True)
+            else:
+                judge.build("valid")
+                valid_loss, emb, labels = judge.valid(valid_dir, valid_spklist, batch_type=p.get("batch_type", "softmax"),
+                                                      output_embeddings=True)
             judge.close()
             eer = scoring.pairwise_eer(emb, labels, device=trainer._device_index)[0]
             new_lr, stop = rule.after(epoch, valid_loss)

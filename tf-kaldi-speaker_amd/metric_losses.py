@@ -6,8 +6,10 @@ double from float32 rows; the rules are stated in include/xvec_hip.h and pinned 
 
 A call takes one batch, or many with `offsets` ([G + 1] row offsets): every batch (group) is evaluated on its own, all of them
 in one launch sequence, and `loss` is the mean of the group losses.  Arrays go in as numpy or as float32 device tensors, like
-losses.py.  Gradients, `generalized_angular_triplet_loss` and the `ge2e` loss with learnable w, b are not implemented.  No CPU
-path: without a HIP device the loss functions raise RuntimeError; from_params itself is pure host code."""
+losses.py.  MetricHead.loss_and_grad adds the gradient of the two triplet losses (csrc/metric_loss_grad.hip, xv_metric_loss_grad:
+what fine-tuning needs; the rule and its choices are in include/xvec_hip.h).  `generalized_angular_triplet_loss` and the `ge2e`
+loss with learnable w, b are not implemented.  No CPU path: without a HIP device the loss functions raise RuntimeError;
+from_params and MetricHead's constructor are pure host code."""
 import collections
 import ctypes as C
 
@@ -19,8 +21,11 @@ from .losses import _HEADS, _dict, _f32
 
 MAX_GROUP_ROWS = 4096
 MAX_SLOTS = 512           # groups (or panels of groups over 1024 rows) in flight; the result does not depend on it
+MAX_GRAD_ROWS = 1024      # the gradient keeps a group's panel and counts in LDS
+MAX_GRAD_SLOT_BYTES = 1 << 28
 
 MetricResult = collections.namedtuple("MetricResult", "loss rows counts top1 group_loss group_counts")
+MetricGrad = collections.namedtuple("MetricGrad", MetricResult._fields + ("grad_x",))
 
 _KINDS = {"semihard": _lib.XV_METRIC_SEMIHARD, "all": _lib.XV_METRIC_ANGULAR_ALL, "hard": _lib.XV_METRIC_ANGULAR_HARD,
           "softmax": _lib.XV_METRIC_GE2E_SOFTMAX, "contrastive": _lib.XV_METRIC_GE2E_CONTRASTIVE}
@@ -155,3 +160,77 @@ def from_params(params, validation=True, device=0):
     if func in _HEADS:
         raise NotImplementedError("loss_func %r is a classifier head: losses.ClassifierHead evaluates it" % func)
     raise NotImplementedError("Not implement %s loss" % func)                     # trainer.py:129
+
+
+def _run_grad(x, labels, offsets, kind, pos_head, margin, squared, normalize, grad_scale, device, as_tensor, sync=True):
+    if not hasattr(labels, "shape"):
+        labels = np.asarray(labels)
+    n, d, off = _check_groups(x, labels, offsets)
+    if np.diff(off).max() > MAX_GRAD_ROWS:
+        raise ValueError("a group of %d rows: the gradient takes at most %d" % (int(np.diff(off).max()), MAX_GRAD_ROWS))
+    if not np.isfinite(grad_scale):
+        raise ValueError("grad_scale must be finite, got %r" % (grad_scale,))
+    torch = _need_device()
+    lib = _lib.load()
+    device = int(device)
+    with torch.cuda.device(device):
+        xd = _f32(x, device, torch)
+        if isinstance(labels, torch.Tensor):
+            ld = labels.to(device=xd.device, dtype=torch.int32).contiguous().reshape(-1)
+        else:
+            ld = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).to(xd.device)
+        groups = len(off) - 1
+        need = int(lib.xv_metric_loss_grad_workspace(groups, off.ctypes.data_as(C.c_void_p), d, kind))
+        if need < 0:
+            _lib.check(need)
+        # one slot (dL/dM [B, B] and its product with the rows [B, d]) is in `need`; every further one lets one more group run
+        b = int(np.diff(off).max())
+        slot = (8 * b * (b + d) + 255) // 256 * 256
+        extra = max(min(groups, 64, MAX_GRAD_SLOT_BYTES // slot) - 1, 0)
+        ws = torch.empty(need + slot * extra, dtype=torch.uint8, device=xd.device)
+        rows = torch.empty(n, dtype=torch.float64, device=xd.device)
+        counts = torch.empty(n, dtype=torch.int64, device=xd.device)
+        gloss = torch.empty(groups, dtype=torch.float64, device=xd.device)
+        gcount = torch.empty((groups, 2), dtype=torch.int64, device=xd.device)
+        gx = torch.empty((n, d), dtype=torch.float32, device=xd.device)
+        _lib.check(lib.xv_metric_loss_grad(device, ptr(xd), int(xd.shape[1]), off.ctypes.data_as(C.c_void_p), groups, d, ptr(ld),
+                                           kind, int(pos_head), float(margin), int(bool(squared)), int(bool(normalize)),
+                                           float(grad_scale), ptr(rows), ptr(counts), ptr(gloss), ptr(gcount), ptr(gx), d, ptr(ws),
+                                           ws.numel(), _lib.stream(device)))
+        if as_tensor and not sync:                                   # a trainer's step: nothing is read back here
+            return MetricGrad(None, rows, counts, None, gloss, gcount, gx)
+        gl = gloss.cpu().numpy()
+        loss = float(np.mean(gl))
+        if as_tensor:
+            return MetricGrad(loss, rows, counts, None, gloss, gcount, gx)
+        return MetricGrad(loss, rows.cpu().numpy(), counts.cpu().numpy(), None, gl, gcount.cpu().numpy(), gx.cpu().numpy())
+
+
+class MetricHead:
+    """The training side of the switch of model/trainer.py:113-129 for the two triplet losses: the options from_params(params,
+    validation=False) takes (`normalize` for the semi-hard loss, params.margin, triplet_loss_squared, loss_type, triplet_type).
+    loss_and_grad(x, labels, offsets=None, grad_scale=1.0) -> MetricGrad: MetricResult's fields, bit for bit those of the
+    forward functions, and grad_x [n, d] = float32(grad_scale dL_g / dx) for the loss L_g of each row's group."""
+
+    def __init__(self, params, device=0):
+        d = _dict(params)
+        self.loss_func = d.get("loss_func")
+        self.forward = from_params(params, validation=False, device=device)      # refuses what has no triplet head
+        self.device = device
+        self.margin = float(d["margin"])
+        self.squared, self.normalize, self.pos_head = False, True, 0
+        if self.loss_func == "semihard_triplet_loss":
+            self.kind, self.squared = _lib.XV_METRIC_SEMIHARD, bool(d["triplet_loss_squared"])
+        else:
+            if d["triplet_type"] not in ("all", "hard"):
+                raise ValueError("triplet_type %r: all or hard" % (d["triplet_type"],))
+            self.kind, self.pos_head = _KINDS[d["triplet_type"]], _ANGULAR_HEADS[d["loss_type"]]
+
+    def loss(self, x, labels, offsets=None):
+        return self.forward(x, labels, offsets)
+
+    def loss_and_grad(self, x, labels, offsets=None, grad_scale=1.0, as_tensor=False, sync=True):
+        """as_tensor: the arrays stay device tensors; with sync=False as well the call only enqueues and `loss` is None (read
+        group_loss when it is needed)."""
+        return _run_grad(x, labels, offsets, self.kind, self.pos_head, self.margin, self.squared, self.normalize, grad_scale,
+                         self.device, as_tensor, sync)

@@ -30,6 +30,7 @@ from . import _lib
 from ._lib import ptr
 from . import head_train
 from . import losses
+from . import metric_losses
 from . import model_io
 
 StepResult = head_train.StepResult
@@ -43,8 +44,13 @@ def _dict(params):
     return params if isinstance(params, dict) else params.dict
 
 
-def check_supported(params):
-    """NotImplementedError for what the segment-level backward pass does not cover, then for everything HeadTrainer refuses."""
+METRIC_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss")       # valid.METRIC_LOSSES: what the second door takes
+
+
+def check_supported(params, metric=False):
+    """NotImplementedError for what the segment-level backward pass does not cover, then for everything HeadTrainer refuses.
+    metric=True is the second door, as valid.metric_valid is for validation: it takes `semihard_triplet_loss` and
+    `angular_triplet_loss` (metric_losses.MetricHead, no classifier layer) and refuses every other loss."""
     d = _dict(params)
     if d.get("network_relu_type") == "prelu":
         raise NotImplementedError("network_relu_type prelu: the trainable alpha of the segment layers is not implemented")
@@ -52,7 +58,14 @@ def check_supported(params):
         raise NotImplementedError("feature_norm: the gradient of the l2 scaling behind the last layer is not implemented")
     if d.get("network_type", "tdnn") not in _SCOPES:
         raise NotImplementedError("Not implement %s network" % d.get("network_type"))
-    losses.head_config(params, 0, False)
+    if metric:
+        if d.get("loss_func") not in METRIC_LOSSES:
+            raise NotImplementedError("loss_func %r: the metric door trains %s" % (d.get("loss_func"), " and ".join(METRIC_LOSSES)))
+        if d.get("aux_loss_func"):
+            raise NotImplementedError("aux_loss_func %r: auxiliary losses are not implemented" % (d["aux_loss_func"],))
+        metric_losses.from_params(params, validation=False)       # loss_type, triplet_type, asoftmax m
+    else:
+        losses.head_config(params, 0, False)
     if d.get("sample_with_prob"):
         raise NotImplementedError("sample_with_prob is not implemented")
     head_train.optimizer_config(params)
@@ -72,11 +85,22 @@ def segment_variables(params):
 
 def trained_names(params):
     """The TensorFlow names of every variable TailTrainer updates, the head's last."""
+    return _trained_names(params, False)
+
+
+def metric_trained_names(params):
+    """trained_names behind the metric door: there is no head layer."""
+    return _trained_names(params, True)
+
+
+def _trained_names(params, metric):
     out = []
     for spec in segment_variables(params):
         out += [spec.kernel, spec.bias]
         if spec.bn:
             out += [spec.bn + "/gamma", spec.bn + "/beta"]
+    if metric:
+        return out
     out.append(model_io.SOFTMAX_KERNEL)
     if _dict(params).get("loss_func") == "softmax":
         out.append(model_io.SOFTMAX_BIAS)
@@ -86,12 +110,22 @@ def trained_names(params):
 def l2_assignment(params):
     """name -> the l2 factor of its update: weight_l2_regularizer on the two dense kernels, optimizer_config's rule on the
     head's kernel, 0 on every bias, gamma and beta."""
+    return _l2_assignment(params, False)
+
+
+def metric_l2_assignment(params):
+    """l2_assignment behind the metric door: the names of metric_trained_names."""
+    return _l2_assignment(params, True)
+
+
+def _l2_assignment(params, metric):
     d = _dict(params)
     reg = float(d.get("weight_l2_regularizer", 0.0))
-    out = dict.fromkeys(trained_names(params), 0.0)
+    out = dict.fromkeys(_trained_names(params, metric), 0.0)
     for spec in segment_variables(params):
         out[spec.kernel] = reg
-    out[model_io.SOFTMAX_KERNEL] = head_train.optimizer_config(params)[3]
+    if not metric:
+        out[model_io.SOFTMAX_KERNEL] = head_train.optimizer_config(params)[3]
     return out
 
 
@@ -327,6 +361,17 @@ def _no_mark(stage):
     pass
 
 
+class MetricTail(object):
+    """What stands in HeadTrainer's place behind the metric door: the optimizer's settings and Adam's count, and
+    metric_losses.MetricHead for the loss and its gradient.  It owns no parameter."""
+
+    def __init__(self, params, device=0):
+        self.kind, self.momentum, self.nesterov, self.l2, self.clip_norm = head_train.optimizer_config(params)
+        self.params, self.loss_func = params, _dict(params).get("loss_func")
+        self.head = metric_losses.MetricHead(params, device)
+        self.num_steps = 0
+
+
 class TailTrainer(object):
     """The two segment-level layers, built from the checkpoint's variables, and a head_train.HeadTrainer behind them.
 
@@ -336,9 +381,10 @@ class TailTrainer(object):
     path, with the CURRENT moving statistics.  trained_names(), l2_assignment() and tensors() do not change: the moving
     statistics are no optimizer tensors.  **Parity unpinned** against TensorFlow, pinned to torch (include/xvec_hip.h)."""
 
-    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving"):
-        check_supported(params)
+    def __init__(self, params, weights, num_classes, device=0, seed=0, kernel=None, bias=None, batch_norm="moving", metric=False):
+        check_supported(params, metric)
         self.params = params
+        self.metric = bool(metric)
         self.batch_norm = batch_norm
         stats = batch_stats_options(params, batch_norm)
         self.specs = segment_variables(params)
@@ -349,8 +395,10 @@ class TailTrainer(object):
             raise ValueError("%s has %d rows, %s %d columns" % (self.specs[1].kernel, self.layers[1].in_dim, self.specs[0].kernel,
                                                                   self.layers[0].out_dim))
         self.pool_dim, self.embed_dim = self.layers[0].in_dim, self.layers[1].out_dim
-        self.head = head_train.HeadTrainer(params, self.embed_dim, num_classes, device, seed, kernel, bias)
-        self.l2 = l2_assignment(params)
+        # metric=True: no classifier layer is built; num_classes, seed, kernel and bias are not used
+        self.head = MetricTail(params, device) if metric else head_train.HeadTrainer(params, self.embed_dim, num_classes, device, seed,
+                                                                                     kernel, bias)
+        self.l2 = _l2_assignment(params, metric)
         torch = losses._need_device()
         self._torch, self._lib, self.device = torch, _lib.load(), int(device)
         self._ws = None
@@ -359,7 +407,7 @@ class TailTrainer(object):
 
     def _fit_workspace(self, layers):
         """Grow the optimizer's workspace to the largest tensor among `layers` and the head."""
-        largest = max([layer.w.numel() for layer in layers] + [self.head.head.raw_rows.numel()])
+        largest = max([layer.w.numel() for layer in layers] + ([] if self.metric else [self.head.head.raw_rows.numel()]))
         need = max(int(self._lib.xv_opt_workspace(largest)), 8)
         if self._ws is None or self._ws.numel() < need:
             with self._torch.cuda.device(self.device):
@@ -368,6 +416,8 @@ class TailTrainer(object):
     def tensors(self):
         """[(TensorFlow name, parameter, gradient, slots)] of everything trained, in the order of trained_names()."""
         out = layer_tensors(self.specs, self.layers)
+        if self.metric:
+            return out
         h = self.head
         out.append((model_io.SOFTMAX_KERNEL, h.head.raw_rows, h._grad_rows, h._row_slots))
         if h.head.bias is not None:
@@ -405,15 +455,21 @@ class TailTrainer(object):
         mark = mark or _no_mark
         with torch.cuda.device(self.device):
             y = forward(mark)
-            out, top1, gx, _, _ = h.head._grad_device(y, labels, global_step, None, True, h._grad_rows, h._grad_bias)
+            if self.metric:        # one group = the batch, grad_scale 1; the group loss, no accuracy
+                res = h.head.loss_and_grad(y, labels, as_tensor=True, sync=False)
+                gx = res.grad_x
+            else:
+                out, top1, gx, _, _ = h.head._grad_device(y, labels, global_step, None, True, h._grad_rows, h._grad_bias)
+                n = int(out.shape[1])
             mark("head")
-            n = int(out.shape[1])
             backward(gx, mark)
             owner.num_steps += 1
             self.num_steps = h.num_steps = owner.num_steps
             for name, w, g, slots in owner.tensors():
                 self._apply(w, g, slots, learning_rate, owner.l2[name])
             mark("optimizer")
+            if self.metric:
+                return StepResult(float(res.group_loss[0]), float("nan"))
             lab = losses._labels_dev(labels, n, out.device, torch)
             return StepResult(float(out[0].double().mean()) if n else float("nan"),
                               float((top1 == lab).double().mean()) if n else float("nan"))
@@ -437,6 +493,8 @@ class TailTrainer(object):
     def variables(self):
         """name -> float32 numpy of every trained variable under its TensorFlow name (kernels as [in, out])."""
         out = layer_variables(self.specs, self.layers)
+        if self.metric:
+            return out
         out[model_io.SOFTMAX_KERNEL] = self.head.kernel()
         if self.head.bias() is not None:
             out[model_io.SOFTMAX_BIAS] = self.head.bias()

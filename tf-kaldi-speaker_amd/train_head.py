@@ -18,7 +18,10 @@ of the third.  `--batch-norm batch` (with any of the three) runs the batch norms
 the reference does: the statistics of the batch, the gradient through them, moving-average updates that the checkpoints then
 hold (tail_train.batch_stats_options); the default `moving` keeps the moving statistics constant.  On a `self_attention` model
 `--frame-layers` and `--conv-layers` also train the key and value networks and the query, through the gradient of the
-attentive pooling (att_train.py).
+attentive pooling (att_train.py).  When the configuration's loss_func is `semihard_triplet_loss` or `angular_triplet_loss` the
+same switches fine-tune with that loss (metric_losses.MetricHead, csrc/metric_loss_grad.hip): there is no classifier layer, so
+one of the three is required, `--keep-head` is accepted and ignored, the checkpoint's own softmax/output/* is copied unchanged,
+and the `loss` of an epoch's line is valid.metric_valid's.
 One line per epoch: `epoch <e> step <s> loss <valid loss> eer <eer> lr <rate>`."""
 import argparse
 import os
@@ -70,6 +73,9 @@ def main(argv=None):
     if not os.path.isfile(config_json):
         sys.exit("Cannot find params.json in %s" % config_json)
     params = Params(config_json)
+    if params.dict.get("loss_func") in ("semihard_triplet_loss", "angular_triplet_loss") and not (
+            args.segment_layers or args.frame_layers or args.conv_layers):
+        parser.error(head_train.METRIC_HEAD_ONLY % params.dict.get("loss_func"))
     with open(os.path.join(nnet_dir, "feature_dim"), "r") as f:
         dim = int(f.readline().strip())
     if "selected_dim" in params.dict:
