@@ -39,6 +39,7 @@ if [ $# != 6 ]; then
   echo "  --frame-layers <false>   # also train the 1-tap frame layers in front of the pooling node; implies --segment-layers"
   echo "                           # (run the head alone first, then --segment-layers, then this)"
   echo "  --conv-layers <false>    # train every frame-level layer, the multi-tap convolutions included; implies the other two"
+  echo "                           # (on a resnet_18 model: every 2-D convolution and block, conv5, dense1, dense2)"
   echo "                           # (the fourth run, after --frame-layers)"
   echo "  --batch-norm <moving>    # moving: inference-mode batch norm, the moving statistics stay constant; batch: the"
   echo "                           # statistics of the batch and moving-average updates in the trained layers (needs one of"

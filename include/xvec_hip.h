@@ -916,6 +916,79 @@ int xv_tconv_backward(int device, const float* gy_dev, int64_t ldgy, const float
                       const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx, float* gw_dev,
                       float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- one grid convolution of the ResNet on packed utterances with its CURRENT weights, forward and backward, and the residual
+ * join of a block (csrc/gconv_grad.hip): tf.layers.conv2d(.., (kh, kw), strides=(st, sf), padding='same') of model/resnet.py +
+ * batch norm in INFERENCE mode + activation.  The grid twin of xv_tconv_*; it is what training conv0_1 and the blocks of the
+ * ResNet-18 needs.  **Parity unpinned** against TensorFlow; pinned to torch.autograd in float64 of F.pad + F.conv2d + eval-mode
+ * batch_norm + relu / leaky_relu (tests/test_gconv_host.py).
+ * Layout: rows are (utterance, frame, bin).  x_dev [*, ldx] has C = channels columns; offsets_dev [batch + 1] is int32 on the
+ *   device, counts FRAMES, ascends, offsets[0] >= 0; utterance b has L = offsets[b + 1] - offsets[b] frames of F_in = bins bins,
+ *   its element (l, f) is row (offsets[b] + l) F_in + f.  It produces L_out = ceil(L / st) frames of F_out = ceil(F_in / sf) bins
+ *   (TensorFlow's 'same'); along each axis pad = max((out - 1) s + k - in, 0) / 2 zeros stand in front (integer division), taken
+ *   per utterance along time and independently along frequency.  The outputs are packed densely from frame 0: out_off[b] = sum_{a
+ *   < b} L_out_a, computed on the device; element (lo, fo) is row (out_off[b] + lo) F_out + fo of z, y and gy.  total_in >=
+ *   offsets[batch] - offsets[0] and total_out >= out_off[batch] are host values in FRAMES that size grids and the workspace and
+ *   nothing else.  w_dev [N = out_dim, ldw] holds the ROWS of the weights with K = kh kw C columns, k = (dl kw + df) C + c: the
+ *   HWIO kernel [kh, kw, C, N] reshaped to [kh kw C, N] and transposed.  bias_dev may be NULL (the ResNet's grid convolutions
+ *   have use_bias=False), and then gbias_dev may be NULL too; gamma, beta, moving_mean, moving_variance [N] and act as for
+ *   xv_seg_forward.
+ * The rule, with X the gathered view: X[o, (dl kw + df) C + c] = x at (lo st - pad_t + dl, fo sf - pad_f + df, c) of the
+ *   utterance of output row o, a ZERO where that frame lies outside the utterance's own L frames or the bin outside [0, F_in):
+ *   z_oj = sum_k X[o, k] w[j, k] (+ b_j);
+ *   h, y, a = gy act'(h), gz, gbeta, ggamma and gbias are exactly the lines of xv_tconv_forward / xv_tconv_backward;
+ *   gw[j, k] = sum over all output rows of all utterances of gz_oj X[o, k], the columns beyond K left alone;
+ *   gx[i, c] = sum over the taps (dl, df) ascending, then j ascending, of gz[o(i, tap), j] w[j, tap C + c] in the row numbering
+ *   of x [*, ldgx]: for input element (l, f) a tap contributes only where l + pad_t - dl is divisible by st and f + pad_f - df by
+ *   sf and the quotients are an output position of the same utterance.  Every owned input row is written; an input that no
+ *   output reads (odd positions under a strided 1 x 1) gets exact zeros.  gx_dev = NULL skips that product.
+ * Orders (all exact fp32 products on v_mfma_f32_32x32x2_f32, no floating-point atomics anywhere): the chain of z runs over k
+ *   ascending from 0, then + b_j; the chain of gx over the taps ascending, then j ascending (through round4(N) - N exact zeros per
+ *   tap, and through the taps that contribute nothing as zero operands); the chain of gw over the output rows ascending, cut into
+ *   S contiguous ranges of ceil32(ceil(rows_out / S')) rows whose sums are added in ascending order in float32, S' = max(1,
+ *   min(ceil(1024 / (ceil(N / 64) ceil(K / 64))), 256, ceil(rows_out / 1024))), rows_out = total_out F_out; the column sums
+ *   gbeta, ggamma and gbias run in double in the slice order of xv_tconv_backward over the rows_out rows.  Every order is a
+ *   function of the shapes and total_out alone.
+ * Properties (tests/test_gpu_gconv.py): every output is bit-identical on every repeat, for every legal ws_bytes and whatever the
+ *   workspace and the outputs held before; z, y and gx of an utterance are a pure function of its own rows and the parameters,
+ *   alone or in any batch, at any position.  Nothing outside the owned rows is read; nothing outside the first total_out F_out
+ *   rows of z and y and the owned rows of gx is written.  ldx >= C is supported; 16-byte accesses are used only where the bases,
+ *   the leading dimensions and C allow.  The per-element error bound is derived in the header of csrc/gconv_grad.hip.  Both
+ *   calls only enqueue work and never wait.  batch = 0 or total_out = 0 is legal: XV_OK, nothing touched.
+ * kh, kw in {1, 3}, st, sf in {1, 2}, kh kw channels <= 16384, 1 <= out_dim <= 4096, 1 <= bins <= 4096, batch <= 2^24, total_in
+ *   bins and total_out F_out <= 2^24 rows: XV_ERR_UNSUPPORTED beyond.  A leading dimension below its width, an unknown activation,
+ *   a missing pointer, some but not all of the four batch-norm pointers: XV_ERR_INVALID.  Every check comes before the first
+ *   launch: a refused call writes nothing.
+ * Workspace (16-byte aligned; XV_ERR_WORKSPACE below the least size): xv_gconv_forward keeps out_off and the map of the output
+ *   rows in the first xv_gconv_forward_workspace(batch, total_out, bins, sf) bytes.  xv_gconv_backward takes any ws_bytes >=
+ *   xv_gconv_workspace_min(..): the two row maps, gz [rows_out, round4(N)], the slice sums and the S planes of gw.  Nothing is
+ *   panelled, so xv_gconv_workspace equals xv_gconv_workspace_min and a larger workspace is not used.  The backward call builds
+ *   its own maps.  All three are 0 for batch = 0 or total_out = 0, and XV_ERR_UNSUPPORTED for a window or stride the calls refuse.
+ * The residual join, on [rows, N = out_dim] operands each with a pitch of its own, every access a scalar float32 one:
+ *   xv_add_act_forward:  s = p + q (one float32 addition), y = act(s) by the activation's line of xv_seg_forward;
+ *   xv_add_act_backward: g = gy act'(s), s recomputed by the forward's instruction, act'(0) that of the lower branch; g is the
+ *   gradient of both p and q.  The outputs are the bits of numpy float32 written the same way.  rows <= 2^28, out_dim <= 65536:
+ *   XV_ERR_UNSUPPORTED beyond; rows = 0: XV_OK, nothing touched. */
+int64_t xv_gconv_workspace(int64_t batch, int64_t total_in, int64_t total_out, int bins, int kh, int kw, int st, int sf, int channels,
+                           int out_dim);
+int64_t xv_gconv_workspace_min(int64_t batch, int64_t total_in, int64_t total_out, int bins, int kh, int kw, int st, int sf,
+                               int channels, int out_dim);
+int64_t xv_gconv_forward_workspace(int64_t batch, int64_t total_out, int bins, int sf);
+int xv_gconv_forward(int device, const float* x_dev, int64_t ldx, int channels, int bins, int kh, int kw, int st, int sf,
+                     const int32_t* offsets_dev, int64_t batch, int64_t total_in, int64_t total_out, const float* w_dev, int64_t ldw,
+                     int out_dim, const float* bias_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev,
+                     const float* var_dev, int act, float* z_dev, int64_t ldz, float* y_dev, int64_t ldy, void* ws_dev,
+                     int64_t ws_bytes, void* stream);
+int xv_gconv_backward(int device, const float* gy_dev, int64_t ldgy, const float* x_dev, int64_t ldx, int channels, int bins, int kh,
+                      int kw, int st, int sf, const int32_t* offsets_dev, int64_t batch, int64_t total_in, int64_t total_out,
+                      const float* z_dev, int64_t ldz, const float* w_dev, int64_t ldw, int out_dim, const float* gamma_dev,
+                      const float* beta_dev, const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx,
+                      float* gw_dev, float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes,
+                      void* stream);
+int xv_add_act_forward(int device, const float* p_dev, int64_t ldp, const float* q_dev, int64_t ldq, int64_t rows, int out_dim, int act,
+                       float* y_dev, int64_t ldy, void* stream);
+int xv_add_act_backward(int device, const float* gy_dev, int64_t ldgy, const float* p_dev, int64_t ldp, const float* q_dev, int64_t ldq,
+                        int64_t rows, int out_dim, int act, float* g_dev, int64_t ldg, void* stream);
+
 /* ---- batch norm in TRAINING mode behind the stored product z of a trained layer (csrc/bn_batch.hip): the batch statistics, h
  * and y, the moving-average update (tf.layers.batch_normalization(training=True) with the UPDATE_OPS of model/trainer.py:501-527)
  * and the gradient through the statistics.  z_dev [n, ldz] (N = out_dim columns) is what xv_seg_forward / xv_tconv_forward store

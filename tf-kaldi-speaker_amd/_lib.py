@@ -202,6 +202,16 @@ SIGNATURES = (
                                vp, i64, vp)),
     ("xv_tconv_backward", i32, (i32, vp, i64, vp, i64, i32, i32, vp, i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i32,
                                 vp, i64, vp, vp, vp, vp, vp, i64, vp)),
+    # one grid convolution of the ResNet on packed utterances, forward and backward, and the residual join of a block
+    ("xv_gconv_workspace", i64, (i64, i64, i64, i32, i32, i32, i32, i32, i32, i32)),
+    ("xv_gconv_workspace_min", i64, (i64, i64, i64, i32, i32, i32, i32, i32, i32, i32)),
+    ("xv_gconv_forward_workspace", i64, (i64, i64, i32, i32)),
+    ("xv_gconv_forward", i32, (i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp, i32,
+                               vp, i64, vp, i64, vp, i64, vp)),
+    ("xv_gconv_backward", i32, (i32, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, vp, i64, vp, i64, i32, vp, vp,
+                                vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp)),
+    ("xv_add_act_forward", i32, (i32, vp, i64, vp, i64, i64, i32, i32, vp, i64, vp)),
+    ("xv_add_act_backward", i32, (i32, vp, i64, vp, i64, vp, i64, i64, i32, i32, vp, i64, vp)),
     # batch norm in training mode behind the stored product z of a trained layer
     ("xv_bn_batch_workspace", i64, (i64, i32)),
     ("xv_bn_batch_workspace_min", i64, (i64, i32)),

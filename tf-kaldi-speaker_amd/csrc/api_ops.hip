@@ -745,6 +745,131 @@ int xv_tconv_backward(int device, const float* gy_dev, int64_t ldgy, const float
   });
 }
 
+namespace {
+
+bool gconv_window_ok(int kh, int kw, int st, int sf) {
+  return (kh == 1 || kh == 3) && (kw == 1 || kw == 3) && (st == 1 || st == 2) && (sf == 1 || sf == 2);
+}
+
+// the checks the two calls of a grid convolution share; `op` names the caller in the message
+int gconv_check(const char* op, int channels, int bins, int kh, int kw, int st, int sf, int out_dim, int64_t batch, int64_t total_in,
+                int64_t total_out, int64_t ldx, int64_t ldw, const void* gamma, const void* beta, const void* mm, const void* mv,
+                int act) {
+  if (!gconv_window_ok(kh, kw, st, sf))
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: kh, kw in {1, 3} and st, sf in {1, 2}, got %d, %d, %d, %d", op, kh, kw, st, sf);
+  if (channels < 1 || (int64_t)kh * kw * channels > 16384 || out_dim < 1 || out_dim > 4096 || bins < 1 || bins > 4096 ||
+      batch > (1 << 24) || total_in > (1 << 24) || total_out > (1 << 24) || total_in * bins > (1 << 24) ||
+      total_out * ((bins + sf - 1) / sf) > (1 << 24))
+    return fail(nullptr, XV_ERR_UNSUPPORTED,
+                "%s: kh * kw * channels <= 16384, 1 <= out_dim, bins <= 4096, batch and rows <= 2^24, got %d, %d, %d, %lld, %lld, %lld",
+                op, channels, out_dim, bins, (long long)batch, (long long)total_in, (long long)total_out);
+  if (batch < 0 || total_in < 0 || total_out < 0 || ldx < channels || ldw < (int64_t)kh * kw * channels)
+    return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
+  return layer_lines_check(op, gamma, beta, mm, mv, act);
+}
+
+}  // namespace
+
+// a grid convolution of the ResNet on packed utterances + batch norm + activation, and the residual join (include/xvec_hip.h,
+// csrc/gconv_grad.hip)
+int64_t xv_gconv_workspace(int64_t batch, int64_t total_in, int64_t total_out, int bins, int kh, int kw, int st, int sf, int channels,
+                           int out_dim) {
+  if (!gconv_window_ok(kh, kw, st, sf)) return XV_ERR_UNSUPPORTED;
+  return gconv_workspace_bytes(batch, total_in, total_out, bins, kh, kw, st, sf, channels, out_dim);
+}
+
+int64_t xv_gconv_workspace_min(int64_t batch, int64_t total_in, int64_t total_out, int bins, int kh, int kw, int st, int sf,
+                               int channels, int out_dim) {
+  return xv_gconv_workspace(batch, total_in, total_out, bins, kh, kw, st, sf, channels, out_dim);
+}
+
+int64_t xv_gconv_forward_workspace(int64_t batch, int64_t total_out, int bins, int sf) {
+  if (sf != 1 && sf != 2) return XV_ERR_UNSUPPORTED;
+  return gconv_forward_workspace_bytes(batch, total_out, bins, sf);
+}
+
+int xv_gconv_forward(int device, const float* x_dev, int64_t ldx, int channels, int bins, int kh, int kw, int st, int sf,
+                     const int32_t* offsets_dev, int64_t batch, int64_t total_in, int64_t total_out, const float* w_dev, int64_t ldw,
+                     int out_dim, const float* bias_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev,
+                     const float* var_dev, int act, float* z_dev, int64_t ldz, float* y_dev, int64_t ldy, void* ws_dev,
+                     int64_t ws_bytes, void* stream) {
+  if (!x_dev || !offsets_dev || !w_dev || !z_dev || !y_dev) return fail(nullptr, XV_ERR_INVALID, "xv_gconv_forward: null pointer");
+  int rc = gconv_check("xv_gconv_forward", channels, bins, kh, kw, st, sf, out_dim, batch, total_in, total_out, ldx, ldw, gamma_dev,
+                       beta_dev, mean_dev, var_dev, act);
+  if (rc != XV_OK) return rc;
+  if (ldz < out_dim || ldy < out_dim) return fail(nullptr, XV_ERR_INVALID, "xv_gconv_forward: bad dimensions");
+  if (batch == 0 || total_out == 0) return XV_OK;
+  if ((rc = layer_ws_check("xv_gconv_forward", ws_dev, ws_bytes, gconv_forward_workspace_bytes(batch, total_out, bins, sf))) != XV_OK)
+    return rc;
+  return with_device(device, "xv_gconv_forward", [&] {
+    return launch_gconv_forward(x_dev, ldx, channels, bins, kh, kw, st, sf, offsets_dev, batch, total_in, total_out, w_dev, ldw,
+                                out_dim, bias_dev, gamma_dev, beta_dev, mean_dev, var_dev, act, z_dev, ldz, y_dev, ldy, ws_dev,
+                                to_stream(stream));
+  });
+}
+
+int xv_gconv_backward(int device, const float* gy_dev, int64_t ldgy, const float* x_dev, int64_t ldx, int channels, int bins, int kh,
+                      int kw, int st, int sf, const int32_t* offsets_dev, int64_t batch, int64_t total_in, int64_t total_out,
+                      const float* z_dev, int64_t ldz, const float* w_dev, int64_t ldw, int out_dim, const float* gamma_dev,
+                      const float* beta_dev, const float* mean_dev, const float* var_dev, int act, float* gx_dev, int64_t ldgx,
+                      float* gw_dev, float* gbias_dev, float* ggamma_dev, float* gbeta_dev, void* ws_dev, int64_t ws_bytes,
+                      void* stream) {
+  if (!gy_dev || !x_dev || !offsets_dev || !z_dev || !w_dev || !gw_dev)
+    return fail(nullptr, XV_ERR_INVALID, "xv_gconv_backward: null pointer");
+  int rc = gconv_check("xv_gconv_backward", channels, bins, kh, kw, st, sf, out_dim, batch, total_in, total_out, ldx, ldw, gamma_dev,
+                       beta_dev, mean_dev, var_dev, act);
+  if (rc != XV_OK) return rc;
+  if (gamma_dev && (!ggamma_dev || !gbeta_dev))
+    return fail(nullptr, XV_ERR_INVALID, "xv_gconv_backward: batch norm needs ggamma_dev and gbeta_dev");
+  if (ldgy < out_dim || ldz < out_dim || (gx_dev && ldgx < channels))
+    return fail(nullptr, XV_ERR_INVALID, "xv_gconv_backward: bad dimensions");
+  if (batch == 0 || total_out == 0) return XV_OK;
+  if (total_in < 1) return fail(nullptr, XV_ERR_INVALID, "xv_gconv_backward: output frames without input frames");
+  if ((rc = layer_ws_check("xv_gconv_backward", ws_dev, ws_bytes,
+                           gconv_workspace_bytes(batch, total_in, total_out, bins, kh, kw, st, sf, channels, out_dim))) != XV_OK)
+    return rc;
+  return with_device(device, "xv_gconv_backward", [&] {
+    return launch_gconv_backward(gy_dev, ldgy, x_dev, ldx, channels, bins, kh, kw, st, sf, offsets_dev, batch, total_in, total_out,
+                                 z_dev, ldz, w_dev, ldw, out_dim, gamma_dev, beta_dev, mean_dev, var_dev, act, gx_dev, ldgx, gw_dev,
+                                 gbias_dev, ggamma_dev, gbeta_dev, ws_dev, to_stream(stream));
+  });
+}
+
+namespace {
+
+int add_act_check(const char* op, int64_t rows, int out_dim, int64_t ldp, int64_t ldq, int64_t ldo, int act) {
+  if (rows > ((int64_t)1 << 28) || out_dim > 65536)
+    return fail(nullptr, XV_ERR_UNSUPPORTED, "%s: rows <= 2^28, out_dim <= 65536, got %lld, %d", op, (long long)rows, out_dim);
+  if (rows < 0 || out_dim < 1 || ldp < out_dim || ldq < out_dim || ldo < out_dim) return fail(nullptr, XV_ERR_INVALID, "%s: bad dimensions", op);
+  if (act < XV_SEG_ACT_NONE || act > XV_SEG_ACT_LRELU) return fail(nullptr, XV_ERR_INVALID, "%s: unknown activation %d", op, act);
+  return XV_OK;
+}
+
+}  // namespace
+
+int xv_add_act_forward(int device, const float* p_dev, int64_t ldp, const float* q_dev, int64_t ldq, int64_t rows, int out_dim, int act,
+                       float* y_dev, int64_t ldy, void* stream) {
+  const int rc = add_act_check("xv_add_act_forward", rows, out_dim, ldp, ldq, ldy, act);
+  if (rc != XV_OK) return rc;
+  if (rows == 0) return XV_OK;
+  if (!p_dev || !q_dev || !y_dev) return fail(nullptr, XV_ERR_INVALID, "xv_add_act_forward: null pointer");
+  return with_device(device, "xv_add_act_forward", [&] {
+    return launch_add_act(nullptr, 0, p_dev, ldp, q_dev, ldq, rows, out_dim, act, y_dev, ldy, to_stream(stream));
+  });
+}
+
+int xv_add_act_backward(int device, const float* gy_dev, int64_t ldgy, const float* p_dev, int64_t ldp, const float* q_dev, int64_t ldq,
+                        int64_t rows, int out_dim, int act, float* g_dev, int64_t ldg, void* stream) {
+  const int rc = add_act_check("xv_add_act_backward", rows, out_dim, ldp, ldq, ldg, act);
+  if (rc != XV_OK) return rc;
+  if (ldgy < out_dim) return fail(nullptr, XV_ERR_INVALID, "xv_add_act_backward: bad dimensions");
+  if (rows == 0) return XV_OK;
+  if (!gy_dev || !p_dev || !q_dev || !g_dev) return fail(nullptr, XV_ERR_INVALID, "xv_add_act_backward: null pointer");
+  return with_device(device, "xv_add_act_backward", [&] {
+    return launch_add_act(gy_dev, ldgy, p_dev, ldp, q_dev, ldq, rows, out_dim, act, g_dev, ldg, to_stream(stream));
+  });
+}
+
 // batch norm in training mode on a stored product z (include/xvec_hip.h, csrc/bn_batch.hip)
 int64_t xv_bn_batch_workspace(int64_t n, int out_dim) { return bn_batch_workspace_bytes(n, out_dim); }
 

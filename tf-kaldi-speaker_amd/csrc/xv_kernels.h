@@ -402,6 +402,26 @@ hipError_t launch_tconv_backward(const float* gy, int64_t ldgy, const float* x, 
                                  float* gx, int64_t ldgx, float* gw, float* gbias, float* ggamma, float* gbeta, void* ws,
                                  hipStream_t s);
 
+// one grid convolution of the ResNet on packed utterances ((kh, kw) window, (st, sf) strides, 'same' padding; rows are utterance,
+// frame, bin) + batch norm (inference mode) + activation, forward and backward, and the residual join y = act(p + q) with its
+// gradient (csrc/gconv_grad.hip, csrc/layer_lines.h).  offsets [batch + 1] on the device counts frames; total_in and total_out are
+// host bounds in frames.  bias and gbias may be null.  ws as sized by gconv_workspace_bytes (the forward uses its first
+// gconv_forward_workspace_bytes only).  launch_add_act: gy null is the forward.
+int64_t gconv_workspace_bytes(int64_t batch, int64_t total_in, int64_t total_out, int F_in, int kh, int kw, int st, int sf, int C,
+                              int N);
+int64_t gconv_forward_workspace_bytes(int64_t batch, int64_t total_out, int F_in, int sf);
+hipError_t launch_gconv_forward(const float* x, int64_t ldx, int C, int F_in, int kh, int kw, int st, int sf, const int32_t* offsets,
+                                int64_t batch, int64_t total_in, int64_t total_out, const float* w, int64_t ldw, int N,
+                                const float* bias, const float* gamma, const float* beta, const float* mm, const float* mv, int act,
+                                float* z, int64_t ldz, float* y, int64_t ldy, void* ws, hipStream_t s);
+hipError_t launch_gconv_backward(const float* gy, int64_t ldgy, const float* x, int64_t ldx, int C, int F_in, int kh, int kw, int st,
+                                 int sf, const int32_t* offsets, int64_t batch, int64_t total_in, int64_t total_out, const float* z,
+                                 int64_t ldz, const float* w, int64_t ldw, int N, const float* gamma, const float* beta,
+                                 const float* mm, const float* mv, int act, float* gx, int64_t ldgx, float* gw, float* gbias,
+                                 float* ggamma, float* gbeta, void* ws, hipStream_t s);
+hipError_t launch_add_act(const float* gy, int64_t ldgy, const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t rows, int N,
+                          int act, float* out, int64_t ldo, hipStream_t s);
+
 // batch norm in training mode on the stored product z [n, N] of a trained layer: batch statistics, y, the moving averages in place
 // (mm, mv: both or null), and the gradient through the statistics (csrc/bn_batch.hip, csrc/layer_lines.h)
 int64_t bn_batch_workspace_bytes(int64_t n, int N);

@@ -80,7 +80,7 @@ def stacked_names(frame_specs, params, metric=False):
     tail_train.trained_names."""
     out = []
     for spec in frame_specs:
-        out += [spec.kernel, spec.bias, spec.bn + "/gamma", spec.bn + "/beta"]
+        out += [spec.kernel] + ([spec.bias] if spec.bias else []) + [spec.bn + "/gamma", spec.bn + "/beta"]
     return out + tail_train._trained_names(params, metric)
 
 
@@ -112,8 +112,6 @@ def metric_trained_names(params):
 
 def metric_l2_assignment(params):
     return stacked_l2(frame_variables(params), params, True)
-
-
 
 
 class StatPool(object):
@@ -196,9 +194,7 @@ class StackedTrainer(object):
         self.tail = tail_train.TailTrainer(params, weights, num_classes, device, seed, kernel, bias, batch_norm, metric)
         num_slots = len(self.tail.layers[0].slots["kernel"])
         self.frame_layers = [self._layer(spec, *tail_train.layer_weights(spec, weights), device, num_slots) for spec in self.frame_specs]
-        for a, b, sa, sb in zip(self.frame_layers[:-1], self.frame_layers[1:], self.frame_specs[:-1], self.frame_specs[1:]):
-            if self._width(b) != a.out_dim:
-                raise ValueError(self._CHAIN % (sb.kernel, self._width(b), sa.kernel, a.out_dim))
+        self._check_chain()
         self.in_dim, self.channels = self._width(self.frame_layers[0]), self.frame_layers[-1].out_dim
         self.device = int(device)
         self.pool = self._make_pool(weights, num_slots)
@@ -210,6 +206,12 @@ class StackedTrainer(object):
         self._torch = losses._need_device()
         self.tail._fit_workspace(self.layers)
         self.num_steps = 0                                                   # adam's t, shared by every tensor
+
+    def _check_chain(self):
+        """Every frame layer takes the columns the layer in front of it gives (a trainer whose layers are no chain says how)."""
+        for a, b, sa, sb in zip(self.frame_layers[:-1], self.frame_layers[1:], self.frame_specs[:-1], self.frame_specs[1:]):
+            if self._width(b) != a.out_dim:
+                raise ValueError(self._CHAIN % (sb.kernel, self._width(b), sa.kernel, a.out_dim))
 
     def _make_pool(self, weights, num_slots):
         """The pooling stage between the frame layers and the tail, checked against the tail's input width: statistics pooling

@@ -288,6 +288,9 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     multi-tap convolutions included, on the packed features, in exact fp32 whatever `precision` says.  The checkpoints then hold
     the new convolution kernels in the shape the input had, and biases, gamma and beta; the moving statistics and every other
     variable are unchanged.
+    On a ResNet-18 conv_layers goes to resnet_train.ResNetTrainer (after resnet_train.check_supported): every 2-D convolution,
+    conv5, dense1 and dense2 are trained as well, the convolutions' kernels written in their HWIO shape; frame_layers alone stays
+    refused there.
     On a self_attention model frame_layers and conv_layers go to att_train.AttFrameTrainer / AttConvTrainer (after
     att_train.check_supported): the key and value networks and the query are trained and written as well.
     batch_norm="batch" (with any of the three; alone it is refused, the head has no batch norm) runs the batch norms of the
@@ -336,7 +339,12 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
     if attention:                                                        # the attention trainers of att_train.py, same steps
         from . import att_train
         att_train.check_supported(params, conv_layers, metric)           # before the trainer is touched
-    if conv_layers:
+    resnet = bool(conv_layers) and not attention and p.get("network_type") == "resnet_18"
+    if resnet:                                                           # resnet_train.py: the grid convolutions and the blocks
+        from . import resnet_train
+        resnet_train.check_supported(params, metric)                     # before the trainer is touched
+        segment_layers = frame_layers = True
+    elif conv_layers:
         from . import conv_train
         if not attention:
             conv_train.check_supported(params, metric)                   # before the trainer is touched
@@ -365,6 +373,8 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
         if attention:
             make = att_train.AttConvTrainer if conv_layers else att_train.AttFrameTrainer
             head = make(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm, metric)
+        elif resnet:
+            head = resnet_train.ResNetTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm, metric)
         elif conv_layers:
             head = conv_train.ConvTrainer(params, weights, num_classes, trainer._device_index, seed, kernel, bias, batch_norm, metric)
         elif frame_layers:

@@ -181,16 +181,16 @@ class Layer(object):
         with torch.cuda.device(self.device):
             self.w = torch.zeros((self.out_dim, self.ldw), dtype=torch.float32, device=dev)
             self.w[:, :self.in_dim] = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32)).to(dev)
-            self.b = losses._f32(bias, self.device, torch)
+            self.b = None if bias is None else losses._f32(bias, self.device, torch)     # None: a layer without a bias
             self.bn = None
             if bn is not None:
                 if any(tuple(np.shape(v)) != (self.out_dim,) for v in bn):
                     raise ValueError("batch norm: four vectors of %d elements expected" % self.out_dim)
                 self.bn = [losses._f32(v, self.device, torch) for v in bn]         # gamma, beta, moving_mean, moving_variance
             self.gw = torch.zeros_like(self.w)                                     # the padding columns stay zero
-            self.gb = torch.zeros_like(self.b)
-            self.ggamma = None if self.bn is None else torch.zeros_like(self.b)
-            self.gbeta = None if self.bn is None else torch.zeros_like(self.b)
+            self.gb = None if self.b is None else torch.zeros_like(self.b)
+            self.ggamma = None if self.bn is None else torch.zeros((self.out_dim,), dtype=torch.float32, device=dev)
+            self.gbeta = None if self.bn is None else torch.zeros((self.out_dim,), dtype=torch.float32, device=dev)
             self.slots = {name: [torch.zeros_like(t) for _ in range(num_slots)] for name, t, _ in self.trained()}
         self._x = self._z = self._ws = None
         self._scratch = self._bn_ws = self._mean = self._var = None
@@ -198,7 +198,7 @@ class Layer(object):
 
     def trained(self):
         """[(name, parameter, gradient)] in the order the optimizer takes them."""
-        out = [("kernel", self.w, self.gw), ("bias", self.b, self.gb)]
+        out = [("kernel", self.w, self.gw)] + ([] if self.b is None else [("bias", self.b, self.gb)])
         if self.bn is not None:
             out += [("gamma", self.bn[0], self.ggamma), ("beta", self.bn[1], self.gbeta)]
         return out
@@ -328,11 +328,14 @@ def layer_forward(layer, training, *args):
 
 
 def layer_weights(spec, weights):
-    """-> (kernel, bias, the four batch-norm vectors or None) of `spec` from the checkpoint; KeyError names what it lacks."""
-    missing = [k for k in (spec.kernel, spec.bias) + (tuple(spec.bn + "/" + s for s in _BN) if spec.bn else ()) if k not in weights]
+    """-> (kernel, bias, the four batch-norm vectors or None) of `spec` from the checkpoint; KeyError names what it lacks.
+    A spec without a bias (spec.bias None: the ResNet's grid convolutions) gives None in its place."""
+    wanted = (spec.kernel,) + ((spec.bias,) if spec.bias else ()) + (tuple(spec.bn + "/" + s for s in _BN) if spec.bn else ())
+    missing = [k for k in wanted if k not in weights]
     if missing:
         raise KeyError("the checkpoint lacks %s" % ", ".join(missing))
-    return weights[spec.kernel], weights[spec.bias], [weights[spec.bn + "/" + s] for s in _BN] if spec.bn else None
+    return (weights[spec.kernel], weights[spec.bias] if spec.bias else None,
+            [weights[spec.bn + "/" + s] for s in _BN] if spec.bn else None)
 
 
 def layer_tensors(specs, layers):
@@ -350,7 +353,8 @@ def layer_variables(specs, layers):
     out = collections.OrderedDict()
     for spec, layer in zip(specs, layers):
         out[spec.kernel] = layer.kernel()
-        out[spec.bias] = layer.b.cpu().numpy().copy()
+        if spec.bias:
+            out[spec.bias] = layer.b.cpu().numpy().copy()
         if spec.bn:
             for k, name in enumerate(_BN if layer.batch_stats else _BN[:2]):
                 out[spec.bn + "/" + name] = layer.bn[k].cpu().numpy().copy()

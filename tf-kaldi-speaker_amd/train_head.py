@@ -14,7 +14,8 @@ multi-tap convolution and the pooling node, through the gradient of statistics p
 three runs: the head first, then `--segment-layers --keep-head` on the directory the first run wrote, then
 `--frame-layers --keep-head` on the directory of the second.  `--conv-layers` (which implies the other two) trains every
 frame-level layer, the multi-tap convolutions included, on the packed features (conv_train.py): a fourth run, on the directory
-of the third.  `--batch-norm batch` (with any of the three) runs the batch norms of the trained layers in training mode, as
+of the third.  On a `resnet_18` model `--conv-layers` trains every 2-D convolution and residual block, conv5, dense1 and dense2
+(resnet_train.py, csrc/gconv_grad.hip); `--frame-layers` alone stays refused there.  `--batch-norm batch` (with any of the three) runs the batch norms of the trained layers in training mode, as
 the reference does: the statistics of the batch, the gradient through them, moving-average updates that the checkpoints then
 hold (tail_train.batch_stats_options); the default `moving` keeps the moving statistics constant.  On a `self_attention` model
 `--frame-layers` and `--conv-layers` also train the key and value networks and the query, through the gradient of the
@@ -47,7 +48,8 @@ def build_parser():
                         "implies --segment-layers.")
     parser.add_argument("--conv-layers", action="store_true", help="Train every frame-level layer, the multi-tap convolutions "
                         "(tdnn1 .. tdnn3; tdnn1 .. tdnn7 of the extended TDNN) included: nothing stays frozen but the moving "
-                        "statistics; implies --frame-layers and --segment-layers.")
+                        "statistics; implies --frame-layers and --segment-layers.  On a resnet_18 model: every 2-D convolution "
+                        "and residual block, conv5, dense1 and dense2 (resnet_train.py).")
     parser.add_argument("--batch-norm", choices=("moving", "batch"), default="moving", help="Batch norm of the trained layers: "
                         "moving = inference mode, the moving statistics stay as the checkpoint has them (default); batch = the "
                         "statistics of the batch, moving-average updates with params.batchnorm_momentum; needs --segment-layers, "
