@@ -1311,6 +1311,58 @@ int64_t xv_pack_rows(const void* const* src, const int64_t* nbytes, int n, void*
  * tensors (the weight source of model/trainer.py:277-295; tf-kaldi-speaker_amd/tf_checkpoint.py applies the LevelDB mask). */
 uint32_t xv_crc32c(uint32_t crc, const void* data, int64_t n);
 
+/* ---- training input: stage the bytes of a planned batch, decode them on the device (csrc/train_stage.cpp, csrc/train_batch.hip) ----
+ * A training batch is B chunks of `length` frames, chunk i being rows [start_i, start_i + length) of one archive record (what
+ * dataset/data_loader.py's workers cut out of dataset/kaldi_io.py:1118-1171 _read_compressed_submat).  The stager copies only
+ * the bytes those rows need into one caller-provided (pinned) buffer and describes them; the decode turns the staged bytes
+ * into the packed float32 batch [B * length, dim] the trainers take.  The host does no arithmetic on the features.
+ *
+ * One descriptor per chunk.  The staged payload of chunk i starts at byte payload_off (a multiple of 16) of the staged buffer:
+ *   XV_TRAIN_FM  rows x cols float32, row-major;   XV_TRAIN_DM  rows x cols float64, row-major;
+ *   XV_TRAIN_CM  cols x rows bytes, COLUMN-major (Kaldi's kOneByteWithColHeaders payload, cut to the staged rows), and at byte
+ *                header_off (a multiple of 8) the cols per-column headers of four uint16 each; gmin / grange are the record's
+ *                global header.
+ * `rows` is the staged row count and first_row the staged row that is frame 0 of the chunk (the stager stages exactly the
+ * chunk: first_row = 0, rows = length).  Output row i * length + t, column c < dim, is element (first_row + t, c):
+ *   FM: the float as it is.   DM: (float)value, one rounding.
+ *   CM: the rule of csrc/ark_io.cpp (Kaldi's CompressedMatrix), all in double, each operation rounded on its own:
+ *       p_k = (double)(float)(gmin + grange * 1.52590218966964e-05 * h_k), k = 0..3 (h the column's header);  v the byte;
+ *       x = p0 + (p1 - p0) / 64 * v          for v <= 64
+ *           p1 + (p2 - p1) / 128 * (v - 64)  for v <= 192
+ *           p2 + (p3 - p2) / 63 * (v - 192)  else;            out = (float)x, one rounding.
+ *     The device code is compiled without fused contraction and uses IEEE division, so every element has the bits
+ *     xv_ark_next_batch gives for the same record.
+ * Columns dim .. ld of the output are not written.  xv_train_batch_decode checks every descriptor on the host before the first
+ * HIP call (XV_ERR_INVALID: an unknown kind, payload_off not a multiple of 16 or header_off of 8, cols < 1, dim > cols or
+ * dim < 1, length < 1, first_row < 0, first_row + length > rows, a payload or header that reaches past staged_bytes, ld < dim,
+ * num_chunks < 1, num_chunks * ceil(length / 64) * ceil(dim / 64) >= 2^31, a null pointer; XV_ERR_WORKSPACE: ws_bytes below
+ * xv_train_batch_workspace), copies the descriptors into ws_dev in stream order and launches once: it never waits for the
+ * device, and the descriptor array may be reused as soon as it returns.
+ *
+ * xv_train_stage: rxfiles holds n '\n'-terminated rxfilenames `file` or `file:offset` (feats.scp's), the offset pointing at
+ * the record's "\0B" (a key in front of it is skipped); chunk i is rows [starts[i], starts[i] + length) of record i.  It reads
+ * each record's header, lays the payloads out in chunk order at 16-byte boundaries (for CM the column headers first) and fills
+ * chunks[i]; the layout depends on the records alone, never on `threads` (clamped to [1, 16]; they only pread).  A chunk that
+ * cannot be staged (a pipe or a range as rxfilename, a file that cannot be opened, a truncated record, an unknown kind, a
+ * record of fewer than starts[i] + length rows) gets status[i] = XV_ERR_INVALID (XV_ERR_UNSUPPORTED for pipes and ranges),
+ * kind 0 and no bytes; the message of the first such chunk goes to err (NUL-terminated).  *staged_bytes is the byte count of
+ * the layout.  Returns the number of chunks that were not staged, XV_ERR_WORKSPACE when dst_capacity is below *staged_bytes
+ * (nothing is copied then), or XV_ERR_INVALID for bad arguments. */
+#define XV_TRAIN_FM 1
+#define XV_TRAIN_DM 2
+#define XV_TRAIN_CM 3
+typedef struct {
+  int64_t payload_off, header_off;
+  int32_t kind, cols, rows, first_row;
+  float gmin, grange;
+} xv_train_chunk;
+int64_t xv_train_batch_workspace(int64_t num_chunks);
+int xv_train_batch_decode(int device, const void* staged_dev, int64_t staged_bytes, const xv_train_chunk* chunks_host,
+                          int64_t num_chunks, int length, int dim, float* out_dev, int64_t ld, void* ws_dev, int64_t ws_bytes,
+                          void* stream);
+int xv_train_stage(const char* rxfiles, int n, const int32_t* starts, int length, int threads, void* dst, int64_t dst_capacity,
+                   xv_train_chunk* chunks, int32_t* status, int64_t* staged_bytes, char* err, int64_t err_capacity);
+
 /* Trainer.close (model/trainer.py:270-275). */
 void xv_destroy(xv_handle* h);
 

@@ -31,6 +31,7 @@ XV_SEG_ACT_NONE, XV_SEG_ACT_RELU, XV_SEG_ACT_LRELU = 0, 1, 2
 XV_METRIC_SEMIHARD, XV_METRIC_ANGULAR_ALL, XV_METRIC_ANGULAR_HARD, XV_METRIC_GE2E_SOFTMAX, XV_METRIC_GE2E_CONTRASTIVE = 0, 1, 2, 3, 4
 XV_LOGREG_MAX_SYSTEMS = 8
 XV_LOGREG_MAX_THRESHOLDS = 8
+XV_TRAIN_FM, XV_TRAIN_DM, XV_TRAIN_CM = 1, 2, 3
 
 
 class ModelDesc(C.Structure):
@@ -84,6 +85,11 @@ class ReverbUtt(C.Structure):
 
 class ReverbNoise(C.Structure):
     _fields_ = [("off", C.c_int64), ("len", C.c_int64), ("ext_len", C.c_int64), ("snr_db", C.c_double), ("start_time", C.c_double)]
+
+
+class TrainChunk(C.Structure):
+    _fields_ = [("payload_off", C.c_int64), ("header_off", C.c_int64), ("kind", C.c_int32), ("cols", C.c_int32),
+                ("rows", C.c_int32), ("first_row", C.c_int32), ("gmin", C.c_float), ("grange", C.c_float)]
 
 
 class PlanInfo(C.Structure):
@@ -250,6 +256,10 @@ SIGNATURES = (
     ("xv_ark_format_vectors", i64, (vp, i32, vp, i32, i64, vp, i64)),
     ("xv_pack_rows", i64, (vp, vp, i32, vp, i32)),
     ("xv_crc32c", u32, (u32, vp, i64)),
+    # training input: the stager and the batch former
+    ("xv_train_batch_workspace", i64, (i64,)),
+    ("xv_train_batch_decode", i32, (i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp)),
+    ("xv_train_stage", i32, (cstr, i32, vp, i32, i32, vp, i64, vp, vp, vp, vp, i64)),
     # teardown and the error string
     ("xv_destroy", None, (vp,)),
     ("xv_last_error", cstr, (vp,)),

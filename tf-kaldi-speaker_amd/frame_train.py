@@ -294,6 +294,13 @@ class StackedTrainer(object):
         return self.tail._step(self, lambda mark: self._forward(x_dev, offsets, mark), self._backward, labels, learning_rate,
                                global_step, mark)
 
+    def optimizer_state(self):
+        """tail_train.optimizer_state of everything this trainer trains: the slots of every tensor and Adam's shared count."""
+        return tail_train.optimizer_state(self)
+
+    def load_optimizer_state(self, state):
+        tail_train.load_optimizer_state(self, state)
+
     def variables(self):
         """name -> float32 numpy of every trained variable under its TensorFlow name (layer.kernel() gives the kernels)."""
         out = tail_train.layer_variables(self.frame_specs, self.frame_layers)

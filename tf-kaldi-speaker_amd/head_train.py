@@ -265,6 +265,37 @@ def _conv_step(trainer, head, feats, labels, lr, step):
         return head.step(dev, np.arange(b + 1, dtype=np.int64) * t, labels, lr, global_step=step)
 
 
+def finish_epoch(params, dim, out_model_dir, variables, step, epoch, rule, valid_dir, valid_spklist, device, precision, metric):
+    """The tail of an epoch, of train_head and of train.train: write model-<step>.npz (model_io.save_model), judge the written
+    directory (Trainer.valid, or valid.metric_valid behind the metric door), scoring.pairwise_eer, rule.after, and one line each
+    in valid_loss and learning_rate in finetune.py's formats -> (valid loss, eer, the next learning rate, stop)."""
+    from . import scoring
+    from . import valid as valid_mod
+    from .trainer import Trainer
+    p = params.dict
+    nnet = os.path.join(out_model_dir, "nnet")
+    model_io.save_model(out_model_dir, p, dim, variables, step=step)
+    judge = Trainer(params, out_model_dir, dim, single_cpu=True, device=device, precision=precision)
+    if metric:
+        valid_loss, emb, labels = valid_mod.metric_valid(judge, valid_dir, valid_spklist,
+                                                         batch_type=p.get("batch_type", "softmax"), output_embeddings=True)
+    else:
+        judge.build("valid")
+        valid_loss, emb, labels = judge.valid(valid_dir, valid_spklist, batch_type=p.get("batch_type", "softmax"),
+                                              output_embeddings=True)
+    judge.close()
+    eer = scoring.pairwise_eer(emb, labels, device=device)[0]
+    new_lr, stop = rule.after(epoch, valid_loss)
+    if epoch == 0:
+        with open(os.path.join(nnet, "learning_rate"), "a") as f:
+            f.write("0 %.8f\n" % rule.rate(0))
+    with open(os.path.join(nnet, "learning_rate"), "a") as f:
+        f.write("%d %.8f\n" % (epoch + 1, new_lr))
+    with open(os.path.join(nnet, "valid_loss"), "a") as f:
+        f.write("%d %f %f\n" % (epoch, valid_loss, eer))
+    return valid_loss, eer, new_lr, stop
+
+
 METRIC_HEAD_ONLY = ("loss_func %s has no classifier layer: there is no head to train; give --segment-layers, --frame-layers or "
                     "--conv-layers")
 
@@ -307,9 +338,7 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
         raise ValueError("batch_norm must be moving or batch, got %r" % (batch_norm,))
     if batch_norm == "batch" and not (segment_layers or frame_layers or conv_layers):
         raise ValueError(BATCH_NORM_ALONE)
-    from . import scoring
     from . import valid as valid_mod
-    from .trainer import Trainer
     params = trainer.params
     p = params.dict
     metric = p.get("loss_func") in valid_mod.METRIC_LOSSES
@@ -386,7 +415,6 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
         # the metric door trains no head: whatever softmax/output/* the checkpoint holds is kept as it is
         frozen = dict(weights) if metric else {k: v for k, v in weights.items()
                                                if k not in (model_io.SOFTMAX_KERNEL, model_io.SOFTMAX_BIAS)}
-        nnet = os.path.join(out_model_dir, "nnet")
         history, step = [], 0
         for epoch in range(num_epochs):
             lr = rule.rate(epoch)
@@ -408,26 +436,8 @@ def train_head(trainer, train_dir, train_spklist, valid_dir, valid_spklist, out_
                 out[model_io.SOFTMAX_KERNEL] = head.kernel()
                 if head.bias() is not None:
                     out[model_io.SOFTMAX_BIAS] = head.bias()
-            model_io.save_model(out_model_dir, p, trainer.dim, out, step=step)
-            judge = Trainer(params, out_model_dir, trainer.dim, single_cpu=True, device=trainer._device_index,
-                            precision=precision or trainer._precision)
-            if metric:
-                valid_loss, emb, labels = valid_mod.metric_valid(judge, valid_dir, valid_spklist,
-                                                                 batch_type=p.get("batch_type", "softmax"), output_embeddings=True)
-            else:
-                judge.build("valid")
-                valid_loss, emb, labels = judge.valid(valid_dir, valid_spklist, batch_type=p.get("batch_type", "softmax"),
-                                                      output_embeddings=True)
-            judge.close()
-            eer = scoring.pairwise_eer(emb, labels, device=trainer._device_index)[0]
-            new_lr, stop = rule.after(epoch, valid_loss)
-            if epoch == 0:
-                with open(os.path.join(nnet, "learning_rate"), "a") as f:
-                    f.write("0 %.8f\n" % rule.rate(0))
-            with open(os.path.join(nnet, "learning_rate"), "a") as f:
-                f.write("%d %.8f\n" % (epoch + 1, new_lr))
-            with open(os.path.join(nnet, "valid_loss"), "a") as f:
-                f.write("%d %f %f\n" % (epoch, valid_loss, eer))
+            valid_loss, eer, new_lr, stop = finish_epoch(params, trainer.dim, out_model_dir, out, step, epoch, rule, valid_dir,
+                                                         valid_spklist, trainer._device_index, precision or trainer._precision, metric)
             history.append((epoch, step, valid_loss, eer, lr))
             if log is not None:
                 log("epoch %d valid loss %f eer %f next learning rate %.8f" % (epoch, valid_loss, eer, new_lr))

@@ -361,6 +361,39 @@ def layer_variables(specs, layers):
     return out
 
 
+def optimizer_state(trainer):
+    """What the reference's Saver keeps beside the variables: {"num_steps": Adam's shared count (int64 scalar), "<TensorFlow
+    name>/slot<k>": slot k of every tensor of trainer.tensors()} as numpy arrays, the slots in the layout the device holds them
+    in (a kernel's rows [N, ldw]).  sgd has no slots, momentum one per tensor, adam two."""
+    out = collections.OrderedDict(num_steps=np.array(trainer.num_steps, dtype=np.int64))
+    for name, _, _, slots in trainer.tensors():
+        for k, slot in enumerate(slots):
+            out["%s/slot%d" % (name, k)] = slot.cpu().numpy().copy()
+    return out
+
+
+def load_optimizer_state(trainer, state):
+    """Put optimizer_state()'s dict back: every slot of every tensor and the step count.  KeyError names what `state` lacks,
+    ValueError a slot of another shape or a name the trainer does not have; nothing is changed then."""
+    torch = losses._need_device()
+    wanted = {"%s/slot%d" % (name, k): slot for name, _, _, slots in trainer.tensors() for k, slot in enumerate(slots)}
+    missing = [k for k in list(wanted) + ["num_steps"] if k not in state]
+    if missing:
+        raise KeyError("the optimizer state lacks %s" % ", ".join(missing))
+    extra = [k for k in state if k not in wanted and k != "num_steps"]
+    if extra:
+        raise ValueError("the optimizer state holds %s, which this trainer does not train" % ", ".join(extra))
+    for k, slot in wanted.items():
+        if tuple(np.shape(state[k])) != tuple(slot.shape):
+            raise ValueError("%s: expected shape %s, got %s" % (k, tuple(slot.shape), tuple(np.shape(state[k]))))
+    for k, slot in wanted.items():
+        slot.copy_(torch.from_numpy(np.ascontiguousarray(state[k], dtype=np.float32)))
+    steps = int(state["num_steps"])
+    for t in (trainer, getattr(trainer, "tail", None), trainer.head):
+        if t is not None:
+            t.num_steps = steps
+
+
 def _no_mark(stage):
     pass
 
@@ -493,6 +526,13 @@ class TailTrainer(object):
             self._backward(gx, False)
             mark("segment_backward")
         return self._step(self, forward, backward, labels, learning_rate, global_step, mark)
+
+    def optimizer_state(self):
+        """tail_train.optimizer_state of this trainer."""
+        return optimizer_state(self)
+
+    def load_optimizer_state(self, state):
+        load_optimizer_state(self, state)
 
     def variables(self):
         """name -> float32 numpy of every trained variable under its TensorFlow name (kernels as [in, out])."""
